@@ -14,7 +14,7 @@ smoke: build
 	$(PY) -c "import __graft_entry__ as g; g.smoke()"
 
 bench: build      ## one JSON line: env-steps/s, roofline, cpu_baseline
-	$(PY) bench.py --gpus 1
+	$(PY) bench.py --gpus 1 --full
 
 golden:           ## regenerate tests/golden/*.npz by running the unmodified reference (needs /root/reference)
 	$(PY) oracle/make_golden.py

@@ -10,7 +10,10 @@ of 8192 minibatches of 64 (default_cfg of the reference, ppo_lag.py:45-52; KL ea
 disabled so the work per step is fixed).  N > 1: one process per GPU, 4096 envs per
 rank (weak scaling); the per-minibatch gradient all-reduce runs inside the persistent update kernel over
 IPC-mapped peer regions (xGMI), or through RCCL between kernels when peer mapping is unavailable.
-Prints ONE JSON line (rank 0) with the driver's fields plus
+Prints ONE JSON line (rank 0): the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall
+time of one timed step) with the workload, `phases` and, for N > 1, `per_rank` / `exchange`.  A plain run does only that:
+set-up, warm-up, the timed steps.  `--dump-outputs DIR` then writes what the last timed step computed (dump_outputs).
+`--full` adds what takes measurements of its own (the GAE scan timings inside the timed epochs, extra runs after them):
   `roofline`      GAE scan kernel at the headline size (HBM bound by its algorithmic bytes, 33 B per (env, step) + 8 B per
                   path end); the 17 MB buffer is Infinity-Cache resident, which the entry says; `achieved` = bytes / mean
                   per-dispatch duration (HIP events around every launch: the figure rocprofv3 --kernel-trace reports);
@@ -367,11 +370,12 @@ def run_epochs(algo, a, comm, dev, N, T, D, A, steps, warmup, time_gae):
     replicas_identical = None
     if world > 1:
         import torch.distributed as dist
-        # data-parallel replicas must hold identical bits under whatever exchange form ran: element-wise max == min over the ranks
-        th = eng.policy.theta.detach()
-        hi, lo = th.clone(), (-th).clone()
-        comm.all_reduce_max_(hi); comm.all_reduce_max_(lo)
-        replicas_identical = bool(torch.equal(hi, -lo))
+        if a.full:
+            # data-parallel replicas must hold identical bits under whatever exchange form ran: element-wise max == min over the ranks
+            th = eng.policy.theta.detach()
+            hi, lo = th.clone(), (-th).clone()
+            comm.all_reduce_max_(hi); comm.all_reduce_max_(lo)
+            replicas_identical = bool(torch.equal(hi, -lo))
         if px is None:
             form = "rccl all-reduce between kernels (spo_ppo_lag_grad -> all_reduce -> spo_clip_adam_then_grad)"
         else:
@@ -382,7 +386,7 @@ def run_epochs(algo, a, comm, dev, N, T, D, A, steps, warmup, time_gae):
                     "selftest_result": list(getattr(px, "last_selftest", ())) if px is not None else None,
                     "host_collectives_backend": dist.get_backend(), "host_collectives_world": dist.get_world_size(),
                     "dp_batch": a.dp_batch, "all_ranks_on_one_gpu": os.environ.get("SPO_BENCH_ONE_GPU", "0") == "1"}
-    return {"elapsed": float(tmax.item()), "roll": roll, "upd": upd, "last": last, "n_ep": n_ep, "eng": eng, "cfg": cfg,
+    return {"elapsed": float(tmax.item()), "roll": roll, "upd": upd, "last": last, "obs": obs, "n_ep": n_ep, "eng": eng, "cfg": cfg,
             "epoch": epoch, "gae_graph": gae_graph, "gae_disp": gae_disp, "per_rank": per_rank, "exchange": exchange,
             "replicas_identical": replicas_identical}
 
@@ -425,6 +429,69 @@ def _update_kernel_entry(us_step, upd_counters, world):
                     "x 4 cycles = simd_sum_floor; DESIGN.md 3.3"}
 
 
+DUMP_ARRAY_BYTES = 4 << 20       # per array: the 13 arrays of a dump stay under 64 MB at any size
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy (float32; `update_stats` float64) --
+    the parameters after the update (`theta`), the observation the next epoch starts from, the epoch's buffer as collect and GAE
+    left it, the update's per-minibatch losses (PPO-Lag) and [stop_iter, kl].  An array above DUMP_ARRAY_BYTES keeps a fixed
+    sample of its leading axis (envs; minibatch steps for `losses`): the first rows of a permutation seeded with 0, sorted, so
+    two builds run with the same arguments dump the same elements."""
+    eng, last = res["eng"], res["last"]
+    arrays = {"theta": eng.policy.theta, "next_obs": res["obs"]}
+    arrays.update({k: eng.buffer.data[k] for k in ("obs", "act", "log_prob", "value_r", "value_c", "adv_r", "adv_c",
+                                                    "target_value_r", "target_value_c")})
+    if last.get("losses"):
+        arrays["losses"] = torch.cat(last["losses"], 0)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        keep = max(DUMP_ARRAY_BYTES // (x.nbytes // x.shape[0]), 1)
+        if keep < x.shape[0]:
+            x = x[np.sort(np.random.default_rng(0).permutation(x.shape[0])[:keep])]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        total += x.nbytes
+    np.save(os.path.join(out_dir, "update_stats.npy"), np.array([last["stop_iter"], last["kl"]], np.float64))
+    assert total < 64 << 20, total
+
+
+def run_config5(a, comm, dev):
+    """BASELINE config 5 (--full): the MAPPO-L Runner on the config-5 shape (tools/ma_bench.py) with its roofline and CPU baseline."""
+    world = comm.world_size
+    try:
+        torch.cuda.empty_cache()
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import ma_bench
+        c5 = ma_bench.run(argparse.Namespace(threads=a.config5_threads, episode_length=64, hidden=128, episodes=2, agents=4),
+                          comm=comm, dev=dev)
+        # flops-based roofline of the training phase (85 % of the epoch: full-batch fp32 GEMM chains on in-tree MFMA kernels)
+        c5["roofline"] = {"bound": "mfma", "achieved": c5["train_gemm_tflops"] * world, "unit": "TFLOP/s",
+                          "peak": FP32_MATRIX_PEAK_TFLOPS * world, "frac": round(c5["train_gemm_tflops"] / FP32_MATRIX_PEAK_TFLOPS, 4),
+                          "note": "algorithmic GEMM flops of the training phase (per agent: learning_iters x 3 networks x forward + "
+                                  "backward = 3 x forward) / its wall time, against the dense FP32 matrix peak; tools/ma_bench.py"}
+        if world == 1 and comm.rank == 0 and not a.no_cpu_baseline:
+            # ADVICE r04: the GPU side runs 8 192 rollout threads, the CPU port a bounded sample -- so the port is timed at
+            # TWO sample sizes (its env-steps/s must not depend on the size for the ratio to mean anything) and once more
+            # with every host core, and all three figures are in the line next to the ratio
+            n_s = a.config5_cpu_sample_threads
+            c5["cpu_baseline"] = cpu_baseline_mappolag(n_s)
+            half = cpu_baseline_mappolag(max(n_s // 2, 1))
+            c5["cpu_baseline"]["value_at_half_the_sample"] = half["value"]
+            c5["speedup_vs_cpu_baseline"] = round(c5["env_steps_per_s"] / c5["cpu_baseline"]["value"], 1)
+            c5["speedup_note"] = (f"GPU: {a.config5_threads} rollout threads; CPU port: {n_s}-thread sample at the reference's 4 torch "
+                                  f"threads of {os.cpu_count()} logical cores (and at {max(n_s // 2, 1)} threads: same rate = the "
+                                  f"ratio carries to the full size)")
+            if a.config5_cpu_all_cores:     # opt-in: with ~200 torch threads on these small products the port takes minutes
+                allc = cpu_baseline_mappolag(n_s, threads=os.cpu_count() or 4)
+                c5["cpu_baseline"]["all_host_cores"] = {"value": allc["value"], "cores": allc["cores"], "sample": allc["sample"]}
+                c5["speedup_vs_cpu_baseline_all_host_cores"] = round(c5["env_steps_per_s"] / allc["value"], 1)
+        return c5
+    except Exception as e:  # pragma: no cover
+        return {"error": str(e)[:300]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -451,7 +518,14 @@ def main():
                     help="N > 1: 'local' = batch_size rows per RANK (global batch 64 x N, weak scaling, the headline); "
                          "'global' = batch_size is the GLOBAL minibatch, every rank takes 64 / N rows per step -- the reference's "
                          "arithmetic on the N x num_envs buffer (BASELINE config 4 with exact semantics, SURVEY.md 8(e))")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: rooflines, per-kernel entries, CPU baselines, BASELINE "
+                         "configs 3 and 5, the wide-network steps, the replica check of N > 1 (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # SPO_BENCH_ONE_GPU=1 (development aid): all ranks share cuda:0 with gloo for the host collectives, to exercise the
     # N > 1 code path -- including the in-kernel exchange through IPC-mapped regions -- on a single-GPU box.
@@ -472,54 +546,64 @@ def main():
     torch.cuda.set_device(dev)
     N, T, D, A = a.num_envs, a.num_steps, 60, 8
 
-    res = run_epochs(a.algo, a, comm, dev, N, T, D, A, a.steps, a.warmup, time_gae=True)
-    elapsed, roll, upd, last, n_ep, eng, cfg = (res[k] for k in ("elapsed", "roll", "upd", "last", "n_ep", "eng", "cfg"))
-    res_exchange, res_per_rank = res["exchange"], res["per_rank"]
-    res_replicas_identical = res.get("replicas_identical")
-
-    def run_config5():
-        try:
-            torch.cuda.empty_cache()
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import ma_bench
-            c5 = ma_bench.run(argparse.Namespace(threads=a.config5_threads, episode_length=64, hidden=128, episodes=2, agents=4),
-                              comm=comm, dev=dev)
-            # flops-based roofline of the training phase (85 % of the epoch: full-batch fp32 GEMM chains on in-tree MFMA kernels)
-            c5["roofline"] = {"bound": "mfma", "achieved": c5["train_gemm_tflops"] * world, "unit": "TFLOP/s",
-                              "peak": FP32_MATRIX_PEAK_TFLOPS * world, "frac": round(c5["train_gemm_tflops"] / FP32_MATRIX_PEAK_TFLOPS, 4),
-                              "note": "algorithmic GEMM flops of the training phase (per agent: learning_iters x 3 networks x forward + "
-                                      "backward = 3 x forward) / its wall time, against the dense FP32 matrix peak; tools/ma_bench.py"}
-            if world == 1 and comm.rank == 0 and not a.no_cpu_baseline:
-                # the GPU side runs 8 192 rollout threads, the CPU port a bounded sample -- so the port is timed at
-                # TWO sample sizes (its env-steps/s must not depend on the size for the ratio to mean anything) and once more
-                # with every host core, and all three figures are in the line next to the ratio
-                n_s = a.config5_cpu_sample_threads
-                c5["cpu_baseline"] = cpu_baseline_mappolag(n_s)
-                half = cpu_baseline_mappolag(max(n_s // 2, 1))
-                c5["cpu_baseline"]["value_at_half_the_sample"] = half["value"]
-                c5["speedup_vs_cpu_baseline"] = round(c5["env_steps_per_s"] / c5["cpu_baseline"]["value"], 1)
-                c5["speedup_note"] = (f"GPU: {a.config5_threads} rollout threads; CPU port: {n_s}-thread sample at the reference's 4 torch "
-                                      f"threads of {os.cpu_count()} logical cores (and at {max(n_s // 2, 1)} threads: same rate = the "
-                                      f"ratio carries to the full size)")
-                if a.config5_cpu_all_cores:     # opt-in: with ~200 torch threads on these small products the port takes minutes
-                    allc = cpu_baseline_mappolag(n_s, threads=os.cpu_count() or 4)
-                    c5["cpu_baseline"]["all_host_cores"] = {"value": allc["value"], "cores": allc["cores"], "sample": allc["sample"]}
-                    c5["speedup_vs_cpu_baseline_all_host_cores"] = round(c5["env_steps_per_s"] / allc["value"], 1)
-            return c5
-        except Exception as e:  # pragma: no cover
-            return {"error": str(e)[:300]}
+    res = run_epochs(a.algo, a, comm, dev, N, T, D, A, a.steps, a.warmup, time_gae=a.full)
+    if a.dump_outputs and comm.rank == 0:
+        dump_outputs(a.dump_outputs, res)
     # BASELINE config 5 on N > 1: every rank runs its shard of the MAPPO-L Runner (collective calls inside), so this sits
     # BEFORE the non-zero ranks leave; rank 0 reports it below.  (N = 1: after the CPO section, as before.)
-    config5 = run_config5() if (world > 1 and a.algo == "ppo_lag" and not a.no_config5) else None
+    config5 = run_config5(a, comm, dev) if (a.full and world > 1 and a.algo == "ppo_lag" and not a.no_config5) else None
     if comm.rank != 0:
         if world > 1:
             torch.distributed.destroy_process_group()
         return
+    elapsed, roll, upd, last, n_ep = (res[k] for k in ("elapsed", "roll", "upd", "last", "n_ep"))
     total_env_steps = world * N * T * a.steps
     value = total_env_steps / elapsed
     batch = 128 if a.algo == "cpo" else (64 // world if (a.dp_batch == "global" and world > 1) else 64)
     iters = 10 if a.algo == "cpo" else a.learning_iters
     n_mb = (N * T + batch - 1) // batch
+    us_step = upd / a.steps / (n_mb * iters) * 1e6
+    line = {
+        "metric": "env-steps/sec (collect+GAE+update) at num_envs=4096, 1/2/4/8 GPU",
+        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": (f"ppo_lag synthetic env (obs=60, act=8), num_envs={N} per GPU, num_steps={T}, "
+                                f"default_cfg batch 64 {'per rank' if a.dp_batch == 'local' or world == 1 else 'GLOBAL (64/N rows per rank)'} "
+                                f"x {a.learning_iters} learning iters (target_kl=inf: all iters run), "
+                                f"device-resident env, observation normalisation fused into the collect step") if a.algo == "ppo_lag" else
+                               (f"cpo synthetic env (obs=60, act=8), num_envs={N}, num_steps={T}, default_cfg "
+                                f"(15 CG iters, 33 FVPs, line search, critic fit batch 128 x 10 iters), device-resident env"),
+                   "global_envs": world * N,
+                   "parallelism": (f"dp{world} over num_envs, per-minibatch gradient all-reduce "
+                                   + ("inside the persistent update kernel over IPC-mapped peer regions (xGMI)"
+                                      if PEER_EXCHANGE_USED[0] else "via RCCL between kernels"))
+                   if world > 1 else "single GPU",
+                   "minibatch_steps_per_epoch": n_mb * iters},
+        "library": _lib_note(),
+        "exchange": res["exchange"],
+        "per_rank": ([{"rank": r, "ms_per_step": round(e / a.steps * 1e3, 2), "rollout_s_per_epoch": round(ro / a.steps, 4),
+                       "update_s_per_epoch": round(u / a.steps, 4),
+                       "update_us_per_minibatch_step": round(u / a.steps / (n_mb * iters) * 1e6, 3)}
+                      for r, (e, ro, u) in enumerate(res["per_rank"])] if world > 1 else None),
+        "phases": {"rollout_s_per_epoch": round(roll / a.steps, 4), "update_s_per_epoch": round(upd / a.steps, 4),
+                   "update_us_per_minibatch_step": round(us_step, 3),
+                   "stop_iter": last["stop_iter"], "kl": last["kl"], "episodes_per_epoch": n_ep},
+    }
+    if a.full:
+        line.update(full_sections(a, comm, dev, N, T, D, A, res, config5, value, us_step))
+    print(json.dumps(line))
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def full_sections(a, comm, dev, N, T, D, A, res, config5, value, us_step):
+    """--full: the line's fields beside the headline, measured after the timed epochs (rank 0): the GAE rooflines, the
+    reference-faithful early-stopping epoch, the FP32-matrix kernels, the CPU baselines, BASELINE configs 3 and 5 (N = 1; config 5
+    of N > 1 ran before the other ranks left and comes in as `config5`), the update kernel's floors and the wide-network steps."""
+    world = comm.world_size
+    eng, cfg = res["eng"], res["cfg"]
+    replicas_identical = res["replicas_identical"]
     seg_ends = int(eng.buffer.seg_end.sum().item())
     folded = bool(getattr(eng.buffer, "last_scan_folded", False))
     # folded form (the engine's): gamma * bootstrap already sits in the reward / cost arrays the scan reads -> exactly
@@ -656,7 +740,8 @@ def main():
     # BASELINE config 3 (CPO) in the same line: its own engine, env, timed epochs and CPU baseline (N = 1 only)
     config3 = None
     if world == 1 and a.algo == "ppo_lag" and not a.no_config3:
-        del res, eng
+        del eng
+        res.clear()                 # the timed run's engine (the epoch closure holds it too) leaves GPU memory
         torch.cuda.empty_cache()
         try:
             r3 = run_epochs("cpo", a, comm, dev, N, T, D, A, a.cpo_steps, 1, time_gae=False)
@@ -685,9 +770,8 @@ def main():
     # With --gpus N the 8 192 rollout threads are sharded over the ranks (the BASELINE row itself: strong scaling) and the section
     # already ran above, before the non-zero ranks left.
     if world == 1 and a.algo == "ppo_lag" and not a.no_config5:
-        config5 = run_config5()
+        config5 = run_config5(a, comm, dev)
 
-    us_step = upd / a.steps / (n_mb * iters) * 1e6
     upd_counters = None
     if a.algo == "ppo_lag":                      # (N > 1: rank 0's process)
         import ctypes
@@ -718,23 +802,7 @@ def main():
                           "critic_fit_cases": _critic_fit_cases()}
         except Exception as e:  # pragma: no cover
             wide_entry = {"error": str(e)[:300]}
-    line = {
-        "metric": "env-steps/sec (collect+GAE+update) at num_envs=4096, 1/2/4/8 GPU",
-        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": (f"ppo_lag synthetic env (obs=60, act=8), num_envs={N} per GPU, num_steps={T}, "
-                                f"default_cfg batch 64 {'per rank' if a.dp_batch == 'local' or world == 1 else 'GLOBAL (64/N rows per rank)'} "
-                                f"x {a.learning_iters} learning iters (target_kl=inf: all iters run), "
-                                f"device-resident env, observation normalisation fused into the collect step") if a.algo == "ppo_lag" else
-                               (f"cpo synthetic env (obs=60, act=8), num_envs={N}, num_steps={T}, default_cfg "
-                                f"(15 CG iters, 33 FVPs, line search, critic fit batch 128 x 10 iters), device-resident env"),
-                   "global_envs": world * N,
-                   "parallelism": (f"dp{world} over num_envs, per-minibatch gradient all-reduce "
-                                   + ("inside the persistent update kernel over IPC-mapped peer regions (xGMI)"
-                                      if PEER_EXCHANGE_USED[0] else "via RCCL between kernels"))
-                   if world > 1 else "single GPU",
-                   "minibatch_steps_per_epoch": n_mb * iters},
+    out = {
         "roofline": roofline,
         "roofline_32768_envs": mid,
         "roofline_hbm_streaming": stream,
@@ -748,22 +816,11 @@ def main():
         "config3_cpo": config3,
         "config5_mappolag": config5,
         "wide_minibatch_step": wide_entry,
-        "library": _lib_note(),
-        "exchange": res_exchange,
-        "replicas_identical_after_run": res_replicas_identical,
-        "per_rank": ([{"rank": r, "ms_per_step": round(e / a.steps * 1e3, 2), "rollout_s_per_epoch": round(ro / a.steps, 4),
-                       "update_s_per_epoch": round(u / a.steps, 4),
-                       "update_us_per_minibatch_step": round(u / a.steps / (n_mb * iters) * 1e6, 3)}
-                      for r, (e, ro, u) in enumerate(res_per_rank)] if world > 1 else None),
-        "phases": {"rollout_s_per_epoch": round(roll / a.steps, 4), "update_s_per_epoch": round(upd / a.steps, 4),
-                   "update_us_per_minibatch_step": round(us_step, 3),
-                   "stop_iter": last["stop_iter"], "kl": last["kl"], "episodes_per_epoch": n_ep},
+        "replicas_identical_after_run": replicas_identical,
     }
     if cpu:
-        line["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
-    print(json.dumps(line))
-    if world > 1:
-        torch.distributed.destroy_process_group()
+        out["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
+    return out
 
 
 if __name__ == "__main__":

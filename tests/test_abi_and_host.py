@@ -437,6 +437,10 @@ def test_bench_refuses_to_report_n_gpus_it_does_not_have():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE=1" in r.stderr and not r.stdout.strip()
+    # ms_per_step divides by --steps: a run without timed steps is refused before anything starts
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()
 
 
 @pytest.mark.parametrize("hidden", [[64, 64], [128, 128], [256, 96], [1024, 1024, 512], [32]])

@@ -3364,7 +3364,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu(dev, dp_batch):
     # the local-batch run also carries BASELINE config 5 on the N > 1 path: the MAPPO-L Runner sharded over the two ranks
     c5 = ["--config5-threads", "128"] if dp_batch == "local" else ["--no-config5"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--num-envs", "256",
-                        "--num-steps", "32", "--learning-iters", "2", "--no-cpu-baseline", "--no-config3", "--stream-envs",
+                        "--num-steps", "32", "--learning-iters", "2", "--full", "--no-cpu-baseline", "--no-config3", "--stream-envs",
                         "2048", "--dp-batch", dp_batch] + c5, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -3393,3 +3393,31 @@ def test_bench_self_launches_two_ranks_on_one_gpu(dev, dp_batch):
         assert c["env_steps_per_s"] > 0 and c["parallelism"].startswith("dp2 over rollout threads")
     else:
         assert d["config5_mappolag"] is None
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline fields only (no --full sections), times exactly --steps epochs and,
+    with --dump-outputs, writes what the last timed epoch computed as float32 / float64 .npy files under 64 MB: the parameters
+    after the update, the next observation, the epoch's buffer after collect and GAE, the losses of every minibatch step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SPO_BENCH_ONE_GPU")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--num-envs", "256", "--num-steps", "32", "--learning-iters", "2", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(256 * 32 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert not {"roofline", "cpu_baseline", "config3_cpo", "config5_mappolag", "wide_minibatch_step"} & set(d), sorted(d)
+    files = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert {"theta", "next_obs", "obs", "act", "adv_r", "target_value_r", "losses", "update_stats"} <= set(files), sorted(files)
+    assert all(x.dtype in (np.float32, np.float64) for x in files.values())
+    assert sum(x.nbytes for x in files.values()) < 64 << 20
+    assert files["adv_r"].shape == (256, 32) and files["losses"].shape == (2 * 256 * 32 // 64, 3)
+    assert files["update_stats"][0] == 2 and np.isfinite(files["theta"]).all() and np.isfinite(files["losses"]).all()

@@ -1,5 +1,5 @@
 export HSA_ENABLE_IPC_MODE_LEGACY=0 SPO_BENCH_ONE_GPU=1
-run() { timeout 900 python bench.py --gpus 2 --steps $3 --warmup 1 --learning-iters $2 --no-cpu-baseline --no-config3 --no-config5 --no-wide 2>/dev/null | python -c "
+run() { timeout 900 python bench.py --full --gpus 2 --steps $3 --warmup 1 --learning-iters $2 --no-cpu-baseline --no-config3 --no-config5 --no-wide 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,8 +6,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r04
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp && rm -rf /tmp/prof /tmp/profc /tmp/pmcf /tmp/pmcw
-CMD_PPO="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
-CMD_CPO="python bench.py --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
+CMD_PPO="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
+CMD_CPO="python bench.py --full --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
 # the bench command under the profiler: kernel trace + stats, and the line that profiled run printed
 ( cd $GRAFT_REPO_ROOT && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- $CMD_PPO > $O/bench_profiled_line.json 2> /tmp/prof.log )
 ( cd $GRAFT_REPO_ROOT && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profc -- $CMD_CPO > $O/bench_cpo_profiled_line.json 2> /tmp/profc.log )
@@ -25,4 +25,4 @@ timeout 200 python tools/update_ab.py > $O/update_ab.txt 2>&1; tail -1 $O/update
 timeout 100 python tools/kl_ab.py > $O/kl_ab.txt 2>&1; tail -1 $O/kl_ab.txt
 python tools/phase_profile_h.py > $O/update_phase_cycles_h.txt 2>&1; tail -4 $O/update_phase_cycles_h.txt
 ( timeout 300 python tools/p2p_loopback_bench.py 2 4 8 2>&1 | grep '^{' | sed 's/^/default   /'; SPO_P2P_ALGO=doubling timeout 300 python tools/p2p_loopback_bench.py 8 2>&1 | grep '^{' | sed 's/^/doubling  /'; SPO_P2P_ALGO=twophase timeout 300 python tools/p2p_loopback_bench.py 2 4 2>&1 | grep '^{' | sed 's/^/twophase  /' ) > $O/p2p_loopback_final.txt; cat $O/p2p_loopback_final.txt
-SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json
+SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json

@@ -7,8 +7,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r05
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp && rm -rf /tmp/prof /tmp/profc /tmp/pmcf /tmp/pmcw /tmp/profk
-CMD_PPO="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
-CMD_CPO="python bench.py --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
+CMD_PPO="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
+CMD_CPO="python bench.py --full --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
 CMD_KS="python tools/ks_bench.py 376,17"
 # the bench command under the profiler: kernel trace + stats, and the line that profiled run printed
 ( cd $GRAFT_REPO_ROOT && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- $CMD_PPO > $O/bench_profiled_line.json 2> /tmp/prof.log )
@@ -40,7 +40,7 @@ python tools/phase_profile_h.py > $O/update_phase_cycles_h.txt 2>&1; tail -4 $O/
   if [ -f $V ]; then echo "-- instrumented build (-DSPO_KS_PROF=1)"; SPO_LIB_PATH=$V SPO_LIB_OVERRIDE=1 SPO_KS_PROF=1 timeout 120 python tools/ks_bench.py 60,20 376,17; fi
 } 2>&1 | grep -v "amdgpu.ids\|WARNING" > $O/feature_split_bench.txt; cat $O/feature_split_bench.txt
 ( timeout 300 python tools/p2p_loopback_bench.py 2 4 8 2>&1 | grep '^{' | sed 's/^/default   /'; SPO_P2P_ALGO=doubling timeout 300 python tools/p2p_loopback_bench.py 8 2>&1 | grep '^{' | sed 's/^/doubling  /'; SPO_P2P_ALGO=twophase timeout 300 python tools/p2p_loopback_bench.py 2 4 2>&1 | grep '^{' | sed 's/^/twophase  /'; SPO_P2P_HELPER=2 SPO_P2P_ALGO=doubling timeout 300 python tools/p2p_loopback_bench.py 2 4 8 2>&1 | grep '^{' | sed 's/^/helper-rd /' ) > $O/p2p_loopback.txt; cat $O/p2p_loopback.txt
-SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json
+SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json
 # counter passes over the other kernels
 bash tools/update_pmc.sh > $O/update_pmc.log 2>&1; cp $O/update_pmc/summary.json $O/update_kernel_pmc.json
 bash tools/kl_pmc.sh > $O/kl_pmc.log 2>&1; cp $O/kl_pmc/summary.json $O/kl_kernel_pmc.json; tail -2 $O/kl_pmc.log

@@ -7,8 +7,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r06
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp && rm -rf /tmp/prof /tmp/profc /tmp/pmcf /tmp/pmcw /tmp/profk
-CMD_PPO="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
-CMD_CPO="python bench.py --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
+CMD_PPO="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-config3 --no-config5 --no-wide"
+CMD_CPO="python bench.py --full --algo cpo --steps 2 --warmup 1 --no-cpu-baseline"
 CMD_KS="python tools/ks_bench.py 376,17"
 ( cd $GRAFT_REPO_ROOT && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- $CMD_PPO > $O/bench_profiled_line.json 2> /tmp/prof.log )
 ( cd $GRAFT_REPO_ROOT && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/profc -- $CMD_CPO > $O/bench_cpo_profiled_line.json 2> /tmp/profc.log )
@@ -39,7 +39,7 @@ SPO_UPDATE_FORM=2 python tools/phase_profile_h.py > $O/update_phase_cycles_h.txt
   timeout 120 python tools/ks_cfit_bench.py 376,17 200,8
 } 2>&1 | grep -v "amdgpu.ids\|WARNING" > $O/feature_split_bench.txt; cat $O/feature_split_bench.txt
 bash tools/r06_loopback.sh > /dev/null 2>&1; cat $O/p2p_loopback.txt
-HSA_ENABLE_IPC_MODE_LEGACY=0 SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json
+HSA_ENABLE_IPC_MODE_LEGACY=0 SPO_BENCH_ONE_GPU=1 timeout 500 python bench.py --full --gpus 2 --steps 1 --warmup 1 --no-cpu-baseline --config5-threads 1024 > $O/bench_dp2_one_gpu.json 2> $O/bench_dp2_one_gpu.err; tail -c 300 $O/bench_dp2_one_gpu.json
 # the wide path's row-group gradient kernel (item 6) and the feature-split gradient launch (item 4b); tests left to tools/r06_final.sh
 sed -e '/pytest/d' tools/r06_rows.sh > /tmp/r06_rows_notests.sh; bash /tmp/r06_rows_notests.sh > /dev/null 2>&1; cat $O/wide_step.txt | cut -c1-200
 { timeout 300 python tools/ks_grad_bench.py 376,17 130,8; echo "-- SPO_WIDE_ROWS=0"; SPO_WIDE_ROWS=0 timeout 300 python tools/ks_grad_bench.py 376,17 130,8; } 2>&1 | grep -v "amdgpu.ids\|WARNING" > $O/dp_feature_split_step.txt; cat $O/dp_feature_split_step.txt
