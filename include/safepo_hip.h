@@ -297,6 +297,51 @@ int spo_update_iter_ex(float* theta, float* adam_m, float* adam_v, int64_t adam_
                        const spo_ppo_cfg* cfg_host, int actor_loss, const float* old_mean, const float* old_std,
                        float kl_bound, float pg_coef, int actor_only, float* losses_out, void* sync_ws, void* stream);
 
+/* ---- Data-parallel FOCOPS / CUP: the split form of spo_update_iter_ex (kernel / all-reduce / optimiser per minibatch step).
+ * The KL-penalty loss couples every row of a minibatch through F = mean_i(ind_i) (focops.py:326-337: a [B] tensor minus a [B,1]
+ * tensor, the mean of a BxB matrix).  Its gradient is linear in F: g_actor = g_KL + F * g_PG with
+ *   g_KL = (1/n) sum_i ind_i grad(KL_i),   g_PG = -(pg_coef/n) sum_j grad(ratio_j * adv_j),
+ * both row sums, so every rank emits its local parts and one sum all-reduce gives every rank the global F.
+ * spo_kl_penalty_grad -- gradient of one local minibatch of n_idx rows (perm indices idx[n_idx], n_idx <= cfg.batch), the
+ *   arguments of spo_update_iter_ex otherwise (replaces focops.py:326-347 / cup.py:370-386 up to clip_grad_norm_):
+ *   flat_grad float[spo_param_count]: the critics' gradients (mean over the local rows, L2 term and value coefficient included,
+ *     as spo_ppo_lag_grad; not written with actor_only) and g_KL in the actor's block (log_std included);
+ *   pg_grad float[actor_size]: g_PG taken with F = 1, actor block only (index 0 = log_std[0], the actor's first parameter);
+ *   sums float[SPO_KLPEN_SUMS]: {loss_r, loss_c (local minibatch, with L2), count of ind, sum ind*KL, sum ratio*adv, rows}
+ *     (with actor_only [0] and [1] are not written).
+ *   Every part is a sum over rows, so the sum over the ranks of [flat_grad | pg_grad | sums] (one contiguous buffer) carries the
+ *   global minibatch.  Any cfg.batch (no 64-row limit: nothing couples the rows inside a pass).
+ * spo_clip_adam_ex -- the optimiser step on the all-reduced buffer, one workgroup (replaces the clip_grad_norm_ + Adam steps of
+ *   focops.py:338-347, cup.py:385-386 and of CUP's first stage, cup.py:300-351): grad_scale multiplies every gradient (1/world);
+ *   pg_grad != NULL: the actor's gradient is flat_grad + F * pg_grad, F = sums[2] / sums[5]; actor_only: clip norm and Adam over
+ *   the actor's parameters only (cup.py:385); separate Adam clocks for the critics and the actor (spo_update_iter_ex).  Adds no
+ *   L2 term (the gradient kernels did).  losses3 (optional, needs sums) receives the global minibatch's losses:
+ *   {sums[0] * grad_scale, sums[1] * grad_scale (not with actor_only), (sums[3] - pg_coef * F * sums[4]) / sums[5] (pg_grad only)}.
+ *   pg_grad == NULL, equal clocks, actor_only == 0: bit-identical to spo_clip_adam.
+ * spo_clip_adam_ex_then_kl_grad -- one host call per step: spo_clip_adam_ex (step k) then spo_kl_penalty_grad (step k+1) into the
+ *   same buffers (next_idx == NULL: only the optimiser step).
+ * spo_clip_adam_ex_then_grad -- the same for the clipped surrogate (CUP's first stage, cup.py:300-351): spo_clip_adam_ex without
+ *   the combine (step k), then spo_ppo_lag_grad (step k+1) into flat_grad / next_losses3. */
+#define SPO_KLPEN_SUMS 8
+int spo_kl_penalty_grad(const float* theta, const float* obs, const float* act, const float* logp_old, const float* target_r,
+                        const float* target_c, const float* adv, const int32_t* idx, int n_idx, const spo_ppo_cfg* cfg_host,
+                        const float* old_mean, const float* old_std, float kl_bound, float pg_coef, int actor_only,
+                        float* flat_grad, float* pg_grad, float* sums, void* stream);
+int spo_clip_adam_ex(float* theta, float* adam_m, float* adam_v, const float* flat_grad, const float* pg_grad, const float* sums,
+                     int64_t adam_step_critics_host, int64_t adam_step_actor_host, float grad_scale, float pg_coef,
+                     int actor_only, const spo_ppo_cfg* cfg_host, float* losses3, void* stream);
+int spo_clip_adam_ex_then_grad(float* theta, float* adam_m, float* adam_v, float* flat_grad, int64_t adam_step_critics_host,
+                               int64_t adam_step_actor_host, float grad_scale, int actor_only, const float* obs, const float* act,
+                               const float* logp_old, const float* target_r, const float* target_c, const float* adv,
+                               const int32_t* next_idx, int next_n_idx, const spo_ppo_cfg* cfg_host, float* next_losses3,
+                               void* stream);
+int spo_clip_adam_ex_then_kl_grad(float* theta, float* adam_m, float* adam_v, float* flat_grad, float* pg_grad, float* sums,
+                                  int64_t adam_step_critics_host, int64_t adam_step_actor_host, float grad_scale,
+                                  const float* obs, const float* act, const float* logp_old, const float* target_r,
+                                  const float* target_c, const float* adv, const float* old_mean, const float* old_std,
+                                  float kl_bound, float pg_coef, int actor_only, const int32_t* next_idx, int next_n_idx,
+                                  const spo_ppo_cfg* cfg_host, float* losses3, void* stream);
+
 /* ---- (e) multi-GPU, in-kernel form (SURVEY.md 8(e) "direct all-reduce over the xGMI mesh, fused as the epilogue of
  * the backward kernel").  Each rank owns one exchange region (uncached device memory, spo_p2p_alloc) and maps its
  * peers' regions through the 64-byte IPC handle (spo_p2p_open; exchange the handles with any host collective).
@@ -657,6 +702,23 @@ int spo_wide_actor_loss(int mode, const float* mean, const float* log_std, const
                         const float* adv, const float* old_mean, const float* old_std, int64_t rows, int64_t rows_total,
                         int act_dim, float p0, float p1, float* d_mean, double* sums_inout, int accumulate, float* loss_out,
                         float* d_log_std_out, double* partial_ws, int partial_capacity, void* stream);
+/* Data-parallel FOCOPS / CUP on the wide path (the split form of spo_kl_penalty_grad / spo_clip_adam_ex for shapes outside the
+ * persistent kernels; replaces focops.py:326-347 and cup.py:370-386 under torchrun).  The KL-penalty loss of spo_wide_actor_loss
+ * mode 2 needs F = mean_i(ind_i) of the minibatch before its cotangent; the gradient is linear in F, g = g_KL + F * g_PG, so:
+ * spo_wide_kl_penalty_split -- one unchunked local minibatch of `rows` rows: d_mean_kl[rows, act_dim] = ind_i d(KL_i)/d(mean) / rows,
+ *   d_mean_pg[rows, act_dim] = -(pg_coef / rows) d(ratio_i adv_i)/d(mean) (F taken as 1), the two parts of d(log_std) into
+ *   d_log_std_kl[act_dim] / d_log_std_pg[act_dim], and sums float[SPO_KLPEN_SUMS] = {0, 0, count of ind, sum ind*KL,
+ *   sum ratio*adv, rows} (spo_kl_penalty_grad's layout).  partial_ws: double[>= 256 * (3 + 2 * SPO_WIDE_MAX_ACT)].  The caller
+ *   backpropagates both cotangents (the PG one into a buffer of its own) and all-reduces gradients + sums.
+ * spo_wide_kl_penalty_combine -- after the all-reduce: grad[begin, n_params) *= grad_scale, with grad[i] += F * pg_grad[i] for
+ *   i >= actor_begin first (pg_grad indexed like grad), F = sums[2] / sums[5]; loss_out (optional) = the global minibatch's
+ *   actor loss (sums[3] - pg_coef * F * sums[4]) / sums[5].  Then spo_wide_clip_adam_ex (which adds the critics' L2 term). */
+int spo_wide_kl_penalty_split(const float* mean, const float* log_std, const float* act, const float* logp_old, const float* adv,
+                              const float* old_mean, const float* old_std, int64_t rows, int act_dim, float kl_bound, float pg_coef,
+                              float* d_mean_kl, float* d_mean_pg, float* d_log_std_kl, float* d_log_std_pg, float* sums,
+                              double* partial_ws, int partial_capacity, void* stream);
+int spo_wide_kl_penalty_combine(float* grad, const float* pg_grad, const float* sums, int64_t n_params, int64_t begin,
+                                int64_t actor_begin, float grad_scale, float pg_coef, float* loss_out, void* stream);
 int spo_wide_critic_loss(const float* v_r, const float* v_c, const float* tgt_r, const float* tgt_c, int64_t rows, float* d_vr,
                          float* d_vc, float* losses2, double* partial_ws, int partial_capacity, void* stream);
 int64_t spo_mlp_jvp_scratch_floats(const spo_mlp_net* net, int64_t rows);

@@ -3215,6 +3215,83 @@ __global__ void wide_actor_loss_finish_kernel(const double* __restrict__ partial
   if (k >= 2 && d_log_std_out) d_log_std_out[k - 2] = (float)s;
 }
 
+// Split KL-penalty form (data-parallel FOCOPS / CUP on the wide path, spo_wide_kl_penalty_split): the fraction F = mean_i(ind_i)
+// belongs to the GLOBAL minibatch, and the gradient is linear in it, g = g_KL + F g_PG.  One pass emits both cotangents --
+// d_mean_kl = ind_i d(KL_i)/d(mean) / n, d_mean_pg = -(pg_coef / n) d(ratio_i adv_i)/d(mean) (F taken as 1) -- the two parts of
+// d(log_std), and the row sums (count of ind, sum ind*KL, sum ratio*adv); the caller all-reduces and combines with the global F.
+constexpr int WAS_NS = 3 + 2 * SPO_WIDE_MAX_ACT;   // partial row: sum ind*KL, count, sum ratio*adv, d(log_std) KL[A], PG[A]
+__global__ __launch_bounds__(256) void wide_klpen_split_kernel(WaArgs a, float* __restrict__ d_mean_pg) {
+  __shared__ double red[4][WAS_NS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int A = a.A, G = a.G, k = lane & (G - 1), sub = lane / G, rpw = 64 / G;
+  const bool on = k < A;
+  const float ls = on ? a.log_std[k] : 0.f;
+  const float sd = __expf(ls), ivar = 1.f / (sd * sd);
+  const float iso = on ? 1.f / a.old_std[k] : 1.f;
+  const float sr = sd * iso;
+  const float vrat = sr * sr, lvrat = logf(vrat);
+  double s_kl = 0.0, s_cnt = 0.0, s_ra = 0.0, s_dk = 0.0, s_dp = 0.0;
+  const int64_t wave_g = (int64_t)blockIdx.x * 4 + wave, nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t r0 = wave_g * rpw; r0 < a.B; r0 += nwaves * rpw) {
+    const int64_t r = r0 + sub;
+    const bool rv = r < a.B;
+    const int64_t rr = rv ? r : a.B - 1;
+    const float mu = on ? a.mean[rr * A + k] : 0.f;
+    const float ac = on ? a.act[rr * A + k] : 0.f;
+    const float dif = ac - mu;
+    const float term = on ? -(dif * dif) * (0.5f * ivar) - ls - LOG_SQRT_2PI_F : 0.f;
+    const float lp = group_sum_f(term, G);
+    const float dm = on ? (mu - a.old_mean[rr * A + k]) * iso : 0.f;
+    const float kl = group_sum_f(on ? 0.5f * (vrat + dm * dm - 1.f - lvrat) : 0.f, G);
+    const float ad = a.adv[rr];
+    const float ratio = __expf(lp - a.logp_old[rr]);
+    const float ind = (kl <= a.p0) ? 1.f : 0.f;
+    const float dlp = -(a.p1 * ad * ratio) * a.inv_n;
+    const float wk = ind * a.inv_n;
+    if (rv && k == 0) { s_kl += (double)(ind * kl); s_cnt += (double)ind; s_ra += (double)(ratio * ad); }
+    if (rv && on) {
+      const float z = dif * ivar;
+      a.d_mean[r * A + k] = wk * dm * iso;
+      d_mean_pg[r * A + k] = dlp * z;
+      s_dk += (double)(wk * (vrat - 1.f));
+      s_dp += (double)(dlp * (dif * z - 1.f));
+    }
+  }
+  s_kl = wave_sum_d(s_kl); s_cnt = wave_sum_d(s_cnt); s_ra = wave_sum_d(s_ra);
+  s_dk = stride_sum_d(s_dk, G); s_dp = stride_sum_d(s_dp, G);
+  if (lane == 0) { red[wave][0] = s_kl; red[wave][1] = s_cnt; red[wave][2] = s_ra; }
+  if (lane < G && lane < A) { red[wave][3 + lane] = s_dk; red[wave][3 + A + lane] = s_dp; }
+  __syncthreads();
+  if (tid < 3 + 2 * A) a.partial[(int64_t)blockIdx.x * WAS_NS + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+// sums (float, the layout of spo_kl_penalty_grad's): [0], [1] = 0 (the wide path's critic losses stay in its loss log), [2] count,
+// [3] sum ind*KL, [4] sum ratio*adv, [5] rows; d(log_std) KL / PG parts into their gradient buffers
+__global__ void wide_klpen_split_finish_kernel(const double* __restrict__ partial, int nblocks, int A, int64_t rows,
+                                               float* __restrict__ sums, float* __restrict__ d_ls_kl, float* __restrict__ d_ls_pg) {
+  const int k = threadIdx.x;
+  if (k >= 3 + 2 * A) return;
+  double s = 0.0;
+  for (int b = 0; b < nblocks; ++b) s += partial[(int64_t)b * WAS_NS + k];
+  if (k == 0) { sums[3] = (float)s; sums[0] = 0.f; sums[1] = 0.f; sums[5] = (float)rows; }
+  else if (k == 1) sums[2] = (float)s;
+  else if (k == 2) sums[4] = (float)s;
+  else if (k < 3 + A) d_ls_kl[k - 3] = (float)s;
+  else d_ls_pg[k - 3 - A] = (float)s;
+}
+// after the all-reduce: grad[begin, n) *= scale with grad[actor_begin, n) += F * pg[actor_begin, n) first, F = sums[2] / sums[5];
+// loss_out = the global minibatch's actor loss
+__global__ __launch_bounds__(256) void wide_klpen_combine_kernel(float* __restrict__ g, const float* __restrict__ pg,
+                                                                 const float* __restrict__ sums, int64_t begin, int64_t actor_begin,
+                                                                 int64_t n, float scale, float pg_coef, float* __restrict__ loss_out) {
+  const float frac = sums[2] / sums[5];
+  for (int64_t i = begin + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float v = g[i];
+    if (i >= actor_begin) v = v + frac * pg[i];
+    g[i] = v * scale;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && loss_out) loss_out[0] = (sums[3] - pg_coef * frac * sums[4]) / sums[5];
+}
+
 __global__ __launch_bounds__(256) void wide_critic_loss_kernel(const float* __restrict__ v_r, const float* __restrict__ v_c,
                                                                const float* __restrict__ tgt_r, const float* __restrict__ tgt_c, int64_t B,
                                                                float inv_n, float* __restrict__ d_vr, float* __restrict__ d_vc,
@@ -3379,6 +3456,44 @@ extern "C" int spo_wide_actor_loss(int mode, const float* mean, const float* log
   hipLaunchKernelGGL(wide_actor_loss_finish_kernel, dim3(1), dim3(128), 0, st, partial_ws, (int)blocks, act_dim, sums_inout, accumulate,
                      loss_scale, loss_out, d_log_std_out);
   SPO_LAUNCH_CHECK("spo_wide_actor_loss");
+  return 0;
+}
+
+extern "C" int spo_wide_kl_penalty_split(const float* mean, const float* log_std, const float* act, const float* logp_old,
+                                         const float* adv, const float* old_mean, const float* old_std, int64_t rows, int act_dim,
+                                         float kl_bound, float pg_coef, float* d_mean_kl, float* d_mean_pg, float* d_log_std_kl,
+                                         float* d_log_std_pg, float* sums, double* partial_ws, int partial_capacity, void* stream) {
+  SPO_REQUIRE(mean && log_std && act && logp_old && adv && old_mean && old_std && d_mean_kl && d_mean_pg && d_log_std_kl &&
+                  d_log_std_pg && sums && partial_ws, "wide_kl_penalty_split: null pointer");
+  SPO_REQUIRE(rows > 0, "wide_kl_penalty_split: bad rows %lld", (long long)rows);
+  SPO_REQUIRE(act_dim >= 1 && act_dim <= SPO_WIDE_MAX_ACT, "wide_kl_penalty_split: act_dim %d outside [1,%d]", act_dim, SPO_WIDE_MAX_ACT);
+  const int G = pow2ceil(act_dim);
+  const int64_t rpb = 4 * (64 / G);
+  int64_t blocks = (rows + rpb - 1) / rpb;
+  if (blocks > 256) blocks = 256;
+  SPO_REQUIRE((int64_t)partial_capacity >= blocks * WAS_NS, "wide_kl_penalty_split: partial workspace too small (%d < %lld)",
+              partial_capacity, (long long)(blocks * WAS_NS));
+  hipStream_t st = (hipStream_t)stream;
+  WaArgs a{mean, log_std, act, logp_old, adv, old_mean, old_std, rows, act_dim, G, kl_bound, pg_coef, 1.f / (float)rows, nullptr,
+           d_mean_kl, partial_ws};
+  hipLaunchKernelGGL(wide_klpen_split_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, d_mean_pg);
+  hipLaunchKernelGGL(wide_klpen_split_finish_kernel, dim3(1), dim3(192), 0, st, partial_ws, (int)blocks, act_dim, rows, sums,
+                     d_log_std_kl, d_log_std_pg);
+  SPO_LAUNCH_CHECK("spo_wide_kl_penalty_split");
+  return 0;
+}
+
+extern "C" int spo_wide_kl_penalty_combine(float* grad, const float* pg_grad, const float* sums, int64_t n_params, int64_t begin,
+                                           int64_t actor_begin, float grad_scale, float pg_coef, float* loss_out, void* stream) {
+  SPO_REQUIRE(grad && pg_grad && sums, "wide_kl_penalty_combine: null pointer");
+  SPO_REQUIRE(n_params > 0 && begin >= 0 && begin <= actor_begin && actor_begin < n_params,
+              "wide_kl_penalty_combine: bad ranges (begin %lld, actor_begin %lld, n_params %lld)", (long long)begin,
+              (long long)actor_begin, (long long)n_params);
+  int64_t blocks = (n_params - begin + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(wide_klpen_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, pg_grad, sums, begin,
+                     actor_begin, n_params, grad_scale, pg_coef, loss_out);
+  SPO_LAUNCH_CHECK("spo_wide_kl_penalty_combine");
   return 0;
 }
 

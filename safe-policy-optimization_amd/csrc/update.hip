@@ -121,6 +121,9 @@ struct UpdArgs {
   int spec_mode;                       // main + helper form: 1 = the clip verdict is validated AFTER the next step's forward
                                        // while the previous step was not clipped (SPO_UPDATE_SPEC, default), 0 = never
   int grid_ranks;                      // exchange self-test only: 2 = both ranks in one grid (spo_p2p_selftest_one_grid)
+  // split KL-penalty gradient (AMODE == 1, !PERSIST: spo_kl_penalty_grad): the policy-gradient part of the actor's gradient
+  // [actor_size] (written by the fourth workgroup); the local sums go to `losses` (SPO_KLPEN_SUMS floats)
+  float* pg_grad;
 };
 constexpr int NPHASE = 10;
 constexpr int UPD_BACKUP_ROWS = 32;      // float4 rows per lane of the 512-thread kernels' backup scratch (main+helper form: 3*NT1 + 12 + 8)
@@ -626,6 +629,11 @@ __device__ __forceinline__ void xr_rd16_flat(const u64* regions, int me, int R, 
 //            KL_i = KL(N(mu_i, sigma) || N(mu_old_i, sigma_old)).sum(-1),  ind_i = [KL_i <= kl_bound].
 //        (The reference subtracts a [B] tensor from a [B,1] tensor, so its loss is the mean of a BxB matrix: that is
 //        exactly the product of means above.  CUP has no indicator: kl_bound = +inf, pg_coef = -lambda * coef.)
+//        Split form (AMODE == 1, !PERSIST; data-parallel FOCOPS / CUP, spo_kl_penalty_grad): the fraction F = mean_i(ind_i)
+//        is a property of the GLOBAL minibatch, so nothing here needs it.  The gradient is linear in F,
+//        g = g_KL + F * g_PG, and both parts are row sums: the actor workgroup emits g_KL (its loss without the PG term), a
+//        fourth workgroup runs the same actor with the PG cotangent only (F taken as 1) into pg_grad, and both emit their
+//        row sums (count, sum ind*KL, sum ratio*adv) -- the caller all-reduces everything and spo_clip_adam_ex forms g.
 // XR: data-parallel form of the persistent kernel -- every rank runs it on its own env shard and the per-step
 //     gradient all-reduce happens inside the step (xr_allreduce above) instead of kernel / RCCL / kernel.
 // XR = 1: reduce-scatter + all-gather (any world); 2: recursive doubling (power-of-two worlds).  Separate instantiations:
@@ -652,7 +660,9 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
   // persistent form launches 8*(n-1)+1 blocks and only blocks 0, 8, 16 work -- the networks then share one
   // XCD's L2 and the per-step granule exchange is ~0.1-0.3 us faster.  Any other placement is just slower.
   float* const st_m = a.adam_m; float* const st_v = a.adam_v;
-  const int net = a.first_net + wg;
+  constexpr bool KLS = (AMODE == 1 && !PERSIST);                   // split KL-penalty gradient (above)
+  const bool pg_wg = KLS && (a.first_net + wg == 3);                // ... its fourth workgroup: the actor, PG cotangent
+  const int net = pg_wg ? 2 : a.first_net + wg;
   const int D = a.cfg.obs_dim, A = a.cfg.act_dim, B = a.cfg.batch;
   const NetGeom g = net_geom(D, A, net);
   const bool is_actor = (net == 2);
@@ -784,6 +794,7 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
 
   f4 aW1[NT1], aW2[4], aW3, dls;
   float db1 = 0.f, db2 = 0.f, db3 = 0.f, lsum = 0.f;
+  float csum = 0.f;                         // split KL-penalty form: count of the rows inside the KL bound
   float iso[4] = {1.f, 1.f, 1.f, 1.f};      // 1 / sigma_old for my 4 action rows (KL-penalty loss)
   if (AMODE == 1 && is_actor) {
 #pragma unroll
@@ -819,6 +830,7 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
       for (int nt = 0; nt < 4; ++nt) aW2[nt] = f4{0.f, 0.f, 0.f, 0.f};
       aW3 = dls = f4{0.f, 0.f, 0.f, 0.f};
       db1 = db2 = db3 = lsum = 0.f;
+      if (KLS) csum = 0.f;
     }
 
     // std = exp(log_std) from the LDS mirror of log_std (a parameter: changes every step)
@@ -875,16 +887,25 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
       lp = quad_row_sum(lp);
       const float kl = quad_row_sum(klp);            // .sum(-1, keepdim=True)
       const float ind = (kl <= a.kl_bound) ? 1.f : 0.f;
-      const float cnt = wave_sum_lane63((q == 0 && cv) ? ind : 0.f);
-      if (lane == 63) red[104 + wave] = cnt;
-      __syncthreads();                               // actor workgroup only (block-uniform branch)
-      const float frac = ((red[104] + red[105]) + (red[106] + red[107])) * inv_n;
+      float frac = 1.f;
+      if (KLS) {
+        csum += (q == 0 && cv) ? ind : 0.f;
+      } else {
+        const float cnt = wave_sum_lane63((q == 0 && cv) ? ind : 0.f);
+        if (lane == 63) red[104 + wave] = cnt;
+        __syncthreads();                             // actor workgroup only (block-uniform branch)
+        frac = ((red[104] + red[105]) + (red[106] + red[107])) * inv_n;
+      }
       const float adv = cur.t1;
       const float ratio = __expf(lp - cur.t0);
-      const float pg = a.pg_coef * frac;
+      // split form: the KL workgroup has no PG term, the PG workgroup no KL term (and F = 1)
+      const float pg = KLS ? (pg_wg ? a.pg_coef : 0.f) : a.pg_coef * frac;
       const float dlp = cv ? -(pg * adv * ratio) * inv_n : 0.f;
-      const float wk = cv ? ind * inv_n : 0.f;
-      lsum += ((q == 0 && cv) ? 1.f : 0.f) * (pg * ratio * adv - ind * kl);     // loss = -mean(this)
+      const float wk = (cv && !pg_wg) ? ind * inv_n : 0.f;
+      if (KLS)                                       // raw row sums: sum ratio*adv (PG) / sum ind*KL (KL)
+        lsum += ((q == 0 && cv) ? 1.f : 0.f) * (pg_wg ? ratio * adv : ind * kl);
+      else
+        lsum += ((q == 0 && cv) ? 1.f : 0.f) * (pg * ratio * adv - ind * kl);   // loss = -mean(this)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float z = dif[r] * ivar[r];
@@ -984,6 +1005,10 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
       // per-wave partials of the scalar reductions ride on the same barrier
       const float ls = wave_sum_lane63(lsum);
       if (lane == 63) red[wave] = ls;
+      if (KLS) {
+        const float cs = wave_sum_lane63(csum);
+        if (lane == 63) red[104 + wave] = cs;
+      }
       if (is_actor) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1189,28 +1214,44 @@ __device__ __forceinline__ void ppo_update_body(const UpdArgs& a, const int wg) 
     const float my_sq = (red[4] + red[5]) + (red[6] + red[7]);
     if (tid == 0) {
       const float loss = is_actor ? -loss_data : loss_data + l2 * ((red[8] + red[9]) + (red[10] + red[11]));
-      a.losses[s * 3 + net] = loss;
+      if (!KLS) {
+        a.losses[s * 3 + net] = loss;
+      } else if (!is_actor) {
+        a.losses[net] = loss;                         // sums[0..1]: the critics' losses of the local minibatch
+      } else {
+        const float rsum = (red[0] + red[1]) + (red[2] + red[3]);
+        if (pg_wg) {
+          a.losses[4] = rsum;                         // sum ratio*adv
+        } else {
+          if (a.first_net == 2) { a.losses[0] = 0.f; a.losses[1] = 0.f; }   // actor only: no critic losses (the sum stays 0)
+          a.losses[2] = (red[104] + red[105]) + (red[106] + red[107]);     // count of ind
+          a.losses[3] = rsum;                         // sum ind*KL
+          a.losses[5] = (float)ncols;                 // rows
+        }
+      }
     }
 
     if (!PERSIST) {
-      // split form: emit the flat gradient (reference parameter order) and stop
+      // split form: emit the flat gradient (reference parameter order) and stop; the PG workgroup of the split KL-penalty form
+      // writes the actor's block into pg_grad instead (indices relative to the actor's first parameter, log_std)
+      float* const fg = pg_wg ? a.pg_grad - ls_off : a.flat_grad;
 #pragma unroll
       for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (16 * nt + j < D) a.flat_grad[g.w1() + (orow + r) * D + 16 * nt + j] = aW1[nt][r];
+          if (16 * nt + j < D) fg[g.w1() + (orow + r) * D + 16 * nt + j] = aW1[nt][r];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) a.flat_grad[g.w2() + (orow + r) * HID + 16 * nt + j] = aW2[nt][r];
+        for (int r = 0; r < 4; ++r) fg[g.w2() + (orow + r) * HID + 16 * nt + j] = aW2[nt][r];
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (4 * q + r < OUT) a.flat_grad[g.w3() + (4 * q + r) * HID + 16 * wave + j] = aW3[r];
-      if (own_b) { a.flat_grad[g.b1() + 16 * wave + j] = db1; a.flat_grad[g.b2() + 16 * wave + j] = db2; }
-      if (own_b3) a.flat_grad[g.b3() + j] = db3;
+        if (4 * q + r < OUT) fg[g.w3() + (4 * q + r) * HID + 16 * wave + j] = aW3[r];
+      if (own_b) { fg[g.b1() + 16 * wave + j] = db1; fg[g.b2() + 16 * wave + j] = db2; }
+      if (own_b3) fg[g.b3() + j] = db3;
       if (own_ls) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) if (4 * q + r < A) a.flat_grad[ls_off + 4 * q + r] = dls[r];
+        for (int r = 0; r < 4; ++r) if (4 * q + r < A) fg[ls_off + 4 * q + r] = dls[r];
       }
       return;
     }
@@ -2811,6 +2852,49 @@ __global__ __launch_bounds__(1024) void clip_adam_kernel(AdamArgs a) {
   }
 }
 
+// The same step with the options of spo_update_iter_ex (spo_clip_adam_ex): separate optimiser clocks for the critics and the
+// actor, an optional parameter range [lo, P) (CUP's actor-only stage: clip norm and Adam over the actor alone, cup.py:385), and
+// the split KL-penalty combine g_actor = g_KL + F * g_PG with F = count / rows from the all-reduced sums.  No combine, lo == 0
+// and equal clocks: every operation of clip_adam_kernel in its order, so the result is the same bits.
+struct AdamExArgs {
+  float* theta; float* m; float* v; const float* grad; const float* pg; const float* sums; float* losses3;
+  int64_t P, lo, actor_begin; float gscale, pg_coef;
+  float max_norm, lr_actor, lr_critic, b1, b2, eps; double pow_b1, pow_b2, pow_b1_actor, pow_b2_actor;
+};
+__global__ __launch_bounds__(1024) void clip_adam_ex_kernel(AdamExArgs a) {
+  __shared__ float sh[16];
+  const int tid = threadIdx.x;
+  const float frac = a.pg ? a.sums[2] / a.sums[5] : 0.f;                // F of the global minibatch
+  auto grad_at = [&](int64_t i) -> float {
+    float g = a.grad[i];
+    if (a.pg && i >= a.actor_begin) g = g + frac * a.pg[i - a.actor_begin];
+    return g * a.gscale;
+  };
+  float sq = 0.f;
+  for (int64_t i = a.lo + tid; i < a.P; i += 1024) { const float g = grad_at(i); sq += g * g; }
+  sq = wave_sum(sq);
+  if ((tid & 63) == 0) sh[tid >> 6] = sq;
+  __syncthreads();
+  float tot = 0.f;
+  for (int k = 0; k < 16; ++k) tot += sh[k];
+  float coef = a.max_norm / (sqrtf(tot) + 1e-6f);
+  coef = coef > 1.f ? 1.f : coef;
+  float ss_a, ss_c, bc2s_a, bc2s_c;
+  adam_scalars(a.lr_actor, a.pow_b1_actor * (double)a.b1, a.pow_b2_actor * (double)a.b2, ss_a, bc2s_a);
+  adam_scalars(a.lr_critic, a.pow_b1 * (double)a.b1, a.pow_b2 * (double)a.b2, ss_c, bc2s_c);
+  for (int64_t i = a.lo + tid; i < a.P; i += 1024) {
+    const float g = grad_at(i) * coef;
+    const bool act = i >= a.actor_begin;
+    const AdamOut o = adam1(a.theta[i], g, a.m[i], a.v[i], a.b1, a.b2, a.eps, act ? ss_a : ss_c, act ? bc2s_a : bc2s_c);
+    a.theta[i] = o.p; a.m[i] = o.m; a.v[i] = o.v;
+  }
+  if (tid == 0 && a.losses3 && a.sums) {
+    // losses of the global minibatch: the critics' = mean over the ranks of the local ones; the actor's from the global sums
+    if (a.lo == 0) { a.losses3[0] = a.sums[0] * a.gscale; a.losses3[1] = a.sums[1] * a.gscale; }
+    if (a.pg) a.losses3[2] = (a.sums[3] - a.pg_coef * frac * a.sums[4]) / a.sums[5];
+  }
+}
+
 // Self-test of the exchange protocol on the same grid shape as the real kernel: every (rank, network) workgroup
 // pushes small-integer patterns and checks the reduced values; result[0] = mismatches, result[1] = timeout flag.
 __global__ __launch_bounds__(256, 1) void xr_selftest_kernel(int rank, int world, unsigned step0, int iters, int* result,
@@ -3568,4 +3652,78 @@ extern "C" int spo_clip_adam(float* theta, float* adam_m, float* adam_v, const f
   hipLaunchKernelGGL(clip_adam_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
   SPO_LAUNCH_CHECK("spo_clip_adam");
   return 0;
+}
+
+// Data-parallel FOCOPS / CUP (focops.py:326-347, cup.py:370-386; include/safepo_hip.h): the split KL-penalty gradient of one
+// local minibatch -- the critics' and the KL part of the actor's gradient into flat_grad, the PG part into pg_grad, the row sums
+// into sums -- on 4 workgroups (2 with actor_only: the actor twice).
+extern "C" int spo_kl_penalty_grad(const float* theta, const float* obs, const float* act, const float* logp_old,
+                                   const float* target_r, const float* target_c, const float* adv, const int32_t* idx,
+                                   int n_idx, const spo_ppo_cfg* cfg_host, const float* old_mean, const float* old_std,
+                                   float kl_bound, float pg_coef, int actor_only, float* flat_grad, float* pg_grad,
+                                   float* sums, void* stream) {
+  if (int rc = check_cfg(cfg_host)) return rc;
+  SPO_REQUIRE(theta && obs && act && logp_old && adv && idx && old_mean && old_std && flat_grad && pg_grad && sums,
+              "kl_penalty_grad: null pointer");
+  SPO_REQUIRE(actor_only || (target_r && target_c), "kl_penalty_grad: critic targets are NULL");
+  SPO_REQUIRE(n_idx > 0 && n_idx <= cfg_host->batch, "kl_penalty_grad: bad n_idx %d (batch %d)", n_idx, cfg_host->batch);
+  UpdArgs a{};
+  a.theta = const_cast<float*>(theta);
+  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
+  a.perm = idx; a.M = n_idx; a.cfg = *cfg_host; a.losses = sums;
+  a.first_net = actor_only ? 2 : 0; a.n_nets = actor_only ? 1 : 3; a.flat_grad = flat_grad; a.mean_count = n_idx;
+  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef; a.pg_grad = pg_grad;
+  if (int rc = launch_update<false, 1>(a, a.n_nets + 1, (hipStream_t)stream)) return rc;
+  SPO_LAUNCH_CHECK("spo_kl_penalty_grad");
+  return 0;
+}
+
+extern "C" int spo_clip_adam_ex(float* theta, float* adam_m, float* adam_v, const float* flat_grad, const float* pg_grad,
+                                const float* sums, int64_t adam_step_critics_host, int64_t adam_step_actor_host,
+                                float grad_scale, float pg_coef, int actor_only, const spo_ppo_cfg* cfg_host, float* losses3,
+                                void* stream) {
+  if (int rc = check_cfg(cfg_host)) return rc;
+  SPO_REQUIRE(theta && adam_m && adam_v && flat_grad, "clip_adam_ex: null pointer");
+  SPO_REQUIRE(adam_step_critics_host >= 0 && adam_step_actor_host >= 0, "clip_adam_ex: bad optimiser step counts");
+  SPO_REQUIRE(!pg_grad || sums, "clip_adam_ex: the KL-penalty combine needs the sums");
+  SPO_REQUIRE(!losses3 || sums, "clip_adam_ex: losses3 needs the sums");
+  const int D = cfg_host->obs_dim, A = cfg_host->act_dim;
+  const int64_t actor_begin = spo_param_offset(D, A, 2);
+  AdamExArgs a{theta, adam_m, adam_v, flat_grad, pg_grad, sums, losses3, spo_param_count(D, A), actor_only ? actor_begin : 0,
+               actor_begin, grad_scale, pg_coef, cfg_host->max_grad_norm, cfg_host->lr_actor, cfg_host->lr_critic,
+               cfg_host->beta1, cfg_host->beta2, cfg_host->adam_eps,
+               pow((double)cfg_host->beta1, (double)adam_step_critics_host), pow((double)cfg_host->beta2, (double)adam_step_critics_host),
+               pow((double)cfg_host->beta1, (double)adam_step_actor_host), pow((double)cfg_host->beta2, (double)adam_step_actor_host)};
+  hipLaunchKernelGGL(clip_adam_ex_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  SPO_LAUNCH_CHECK("spo_clip_adam_ex");
+  return 0;
+}
+
+// One host call per data-parallel FOCOPS / CUP step: spo_clip_adam_ex (step k), then spo_kl_penalty_grad (step k+1) into the
+// same buffers (next_idx == NULL: only the optimiser step).
+extern "C" int spo_clip_adam_ex_then_kl_grad(float* theta, float* adam_m, float* adam_v, float* flat_grad, float* pg_grad,
+                                             float* sums, int64_t adam_step_critics_host, int64_t adam_step_actor_host,
+                                             float grad_scale, const float* obs, const float* act, const float* logp_old,
+                                             const float* target_r, const float* target_c, const float* adv,
+                                             const float* old_mean, const float* old_std, float kl_bound, float pg_coef,
+                                             int actor_only, const int32_t* next_idx, int next_n_idx,
+                                             const spo_ppo_cfg* cfg_host, float* losses3, void* stream) {
+  if (int rc = spo_clip_adam_ex(theta, adam_m, adam_v, flat_grad, pg_grad, sums, adam_step_critics_host, adam_step_actor_host,
+                                grad_scale, pg_coef, actor_only, cfg_host, losses3, stream)) return rc;
+  if (next_idx == nullptr || next_n_idx <= 0) return 0;
+  return spo_kl_penalty_grad(theta, obs, act, logp_old, target_r, target_c, adv, next_idx, next_n_idx, cfg_host, old_mean,
+                             old_std, kl_bound, pg_coef, actor_only, flat_grad, pg_grad, sums, stream);
+}
+
+// CUP's first stage under data parallelism: spo_clip_adam_ex (step k, no combine) then spo_ppo_lag_grad (step k+1).
+extern "C" int spo_clip_adam_ex_then_grad(float* theta, float* adam_m, float* adam_v, float* flat_grad, int64_t adam_step_critics_host,
+                                          int64_t adam_step_actor_host, float grad_scale, int actor_only, const float* obs,
+                                          const float* act, const float* logp_old, const float* target_r, const float* target_c,
+                                          const float* adv, const int32_t* next_idx, int next_n_idx, const spo_ppo_cfg* cfg_host,
+                                          float* next_losses3, void* stream) {
+  if (int rc = spo_clip_adam_ex(theta, adam_m, adam_v, flat_grad, nullptr, nullptr, adam_step_critics_host, adam_step_actor_host,
+                                grad_scale, 0.f, actor_only, cfg_host, nullptr, stream)) return rc;
+  if (next_idx == nullptr || next_n_idx <= 0) return 0;
+  return spo_ppo_lag_grad(theta, obs, act, logp_old, target_r, target_c, adv, next_idx, next_n_idx, next_n_idx, cfg_host, flat_grad,
+                          next_losses3, stream);
 }

@@ -64,6 +64,7 @@ P = c_void_p
 ACTOR_LOSS_CLIP, ACTOR_LOSS_KL_PENALTY = 0, 1      # include/safepo_hip.h SPO_ACTOR_LOSS_*
 MAX_OBS, MAX_ACT, CPO_MAX_OBS, WIDE_MAX_ACT = 128, 16, 64, 64   # SPO_MAX_OBS, SPO_MAX_ACT, cpo.hip's limit, SPO_WIDE_MAX_ACT
 WIDE_ACTOR_CLIP, WIDE_ACTOR_SURR, WIDE_ACTOR_KLPEN = 0, 1, 2     # spo_wide_actor_loss modes
+KLPEN_SUMS = 8                                     # include/safepo_hip.h SPO_KLPEN_SUMS (floats of spo_kl_penalty_grad's sums)
 GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GAE_PARTIAL_STRIDE (doubles per workgroup)
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -122,6 +123,13 @@ PROTOTYPES = {
     "spo_critic_fit_iter": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,
                                    c_float, c_float, c_int, P, P, P]),
+    "spo_kl_penalty_grad": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, c_float, c_float, c_int, P, P, P, P]),
+    "spo_clip_adam_ex": (c_int, [P] * 6 + [c_int64, c_int64, c_float, c_float, c_int, POINTER(PpoCfg), P, P]),
+    "spo_clip_adam_ex_then_grad": (c_int, [P] * 4 + [c_int64, c_int64, c_float, c_int] + [P] * 7 + [c_int, POINTER(PpoCfg), P, P]),
+    "spo_wide_kl_penalty_split": (c_int, [P] * 7 + [c_int64, c_int, c_float, c_float] + [P] * 6 + [c_int, P]),
+    "spo_wide_kl_penalty_combine": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, c_float, P, P]),
+    "spo_clip_adam_ex_then_kl_grad": (c_int, [P] * 6 + [c_int64, c_int64, c_float] + [P] * 8 + [c_float, c_float, c_int, P, c_int,
+                                                                                                POINTER(PpoCfg), P, P]),
     "spo_p2p_region_bytes": (c_int64, []),
     "spo_debug_xr_profile": (c_int, [P, c_int]),
     "spo_p2p_alloc": (c_int, [POINTER(c_void_p), P]),

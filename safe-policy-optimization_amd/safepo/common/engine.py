@@ -474,10 +474,9 @@ class PPOLagEngine:
                          kl_bound: float = float("inf"), pg_coef: float = 0.0, actor_only: bool = False) -> torch.Tensor:
         """One pass over the data on the persistent kernel with the FOCOPS / CUP options of spo_update_iter_ex
         (include/safepo_hip.h): KL-penalty actor loss against the last snapshot_old_distribution(), actor-only
-        optimisation, separate optimiser step counts.  Single GPU only."""
-        if self.comm.world_size != 1:
-            raise NotImplementedError("focops / cup run on one GPU in this build (no data-parallel form of the "
-                                      "KL-penalty minibatch step)")
+        optimisation, separate optimiser step counts.  Data-parallel: _learning_iter_ex_split."""
+        if self.comm.world_size > 1:
+            return self._learning_iter_ex_split(perm, adv, actor_loss, kl_bound, pg_coef, actor_only)
         cfg = self._cfg_struct()
         perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
         adv = _abi.require_gpu_tensor(adv, "adv", torch.float32)
@@ -496,6 +495,72 @@ class PPOLagEngine:
             self.adam_step_actor_extra += n_mb
         else:
             self.adam_step += n_mb
+        return losses
+
+    def _learning_iter_ex_split(self, perm: torch.Tensor, adv: torch.Tensor, actor_loss: int, kl_bound: float, pg_coef: float,
+                                actor_only: bool) -> torch.Tensor:
+        """learning_iter_ex under data parallelism: per minibatch step the local gradient, ONE sum all-reduce, the optimiser step
+        on the reduced buffer, identical on every rank.  The KL-penalty loss couples the rows of the global minibatch through
+        the fraction F of rows inside the KL bound; its gradient is linear in F, so the gradient kernel emits the KL part, the
+        policy-gradient part and the row sums separately (spo_kl_penalty_grad) into one contiguous buffer
+        [flat_grad P | g_PG Pa | sums], and spo_clip_adam_ex forms g_KL + F * g_PG with the global F after the all-reduce.  The
+        clipped surrogate of CUP's first stage has no coupling: spo_ppo_lag_grad, then spo_clip_adam_ex with the two optimiser
+        clocks.  The in-kernel exchange (self.p2p) is PPO-Lag's; this path does not use it."""
+        cfg = self._cfg_struct()
+        perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+        adv = _abi.require_gpu_tensor(adv, "adv", torch.float32)
+        d, M, B = self.buffer.data, self.M, cfg.batch
+        n_mb = (M + B - 1) // B
+        losses = torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=self.dev)
+        P = self.policy.theta.numel()
+        Pa = P - self.policy.log_std_offset
+        buf = getattr(self, "_split_buf", None)
+        if buf is None or buf.numel() != P + Pa + _abi.KLPEN_SUMS:
+            buf = self._split_buf = torch.zeros(P + Pa + _abi.KLPEN_SUMS, dtype=torch.float32, device=self.dev)
+        lib, st, reduce_ = self.lib, _abi.stream_ptr(), self.comm.all_reduce_sum_
+        p_th, p_m, p_v = _abi.ptr(self.policy.theta), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v)
+        p_fg, p_pg, p_sums = buf.data_ptr(), buf.data_ptr() + 4 * P, buf.data_ptr() + 4 * (P + Pa)
+        p_obs, p_act, p_lp = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+        p_tr, p_tc, p_adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(adv)
+        p_perm, p_loss = perm.data_ptr(), losses.data_ptr()
+        scale, ao = 1.0 / self.comm.world_size, int(bool(actor_only))
+        klpen = actor_loss == _abi.ACTOR_LOSS_KL_PENALTY
+        # what is exchanged: actor only -- from the actor's block on (the critics' block of flat_grad is not written); the
+        # clipped surrogate -- flat_grad alone
+        red_lo = self.policy.log_std_offset if actor_only else 0
+        red = buf[red_lo:] if klpen else buf[red_lo:P]
+        n0 = min(B, M)
+        if klpen:
+            _abi.check(lib.spo_kl_penalty_grad(
+                p_th, p_obs, p_act, p_lp, p_tr, p_tc, p_adv, p_perm, n0, cfg, _abi.ptr(self.mean_old), _abi.ptr(self.std_old),
+                float(kl_bound), float(pg_coef), ao, p_fg, p_pg, p_sums, st), "spo_kl_penalty_grad")
+        else:
+            _abi.check(lib.spo_ppo_lag_grad(p_th, p_obs, p_act, p_lp, p_tr, p_tc, p_adv, p_perm, n0, n0, cfg, p_fg, p_loss, st),
+                       "spo_ppo_lag_grad")
+        for k in range(n_mb):
+            step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
+            reduce_(red)
+            # one host call: the optimiser step k, then the gradient of step k + 1 into the same buffer
+            nlo = (k + 1) * B
+            nxt, n_nxt = (p_perm + 4 * nlo, min(B, M - nlo)) if nlo < M else (None, 0)
+            if klpen:
+                _abi.check(lib.spo_clip_adam_ex_then_kl_grad(
+                    p_th, p_m, p_v, p_fg, p_pg, p_sums, step_c, step_a, scale, p_obs, p_act, p_lp, p_tr, p_tc, p_adv,
+                    _abi.ptr(self.mean_old), _abi.ptr(self.std_old), float(kl_bound), float(pg_coef), ao, nxt, n_nxt, cfg,
+                    p_loss + 12 * k, st), "spo_clip_adam_ex_then_kl_grad")
+            else:
+                _abi.check(lib.spo_clip_adam_ex_then_grad(
+                    p_th, p_m, p_v, p_fg, step_c, step_a, scale, ao, p_obs, p_act, p_lp, p_tr, p_tc, p_adv, nxt, n_nxt, cfg,
+                    p_loss + 12 * (k + 1) if nxt is not None else None, st), "spo_clip_adam_ex_then_grad")
+            if actor_only:
+                self.adam_step_actor_extra += 1
+            else:
+                self.adam_step += 1
+        if not klpen:                      # the gradient kernel's local losses -> the global minibatches'
+            self.comm.all_reduce_sum_(losses)
+            losses *= scale
+        if actor_only:
+            losses[:, :2] = float("nan")   # (as spo_update_iter_ex: only the actor's column)
         return losses
 
     def _kl_stopped_loop(self, perm_fn, it0: int, run_iter):
@@ -931,6 +996,8 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
         w, lib, st = self.wide, self.lib, _abi.stream_ptr
         cfg = self._cfg_struct() if cfg is None else cfg
         klpen = actor_loss == _abi.ACTOR_LOSS_KL_PENALTY
+        if klpen and self.comm.world_size > 1:
+            return self._minibatch_step_ex_split(idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, cfg)
         got = self._gather(idx, adv_all, extra=(self.mean_old,) if klpen else ())
         obs, act, logp_old, tgt_r, tgt_c, adv = got[:6]
         n = obs.shape[0]
@@ -970,11 +1037,55 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
                                              None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
                                              st()), "spo_wide_clip_adam_ex")
 
+    def _minibatch_step_ex_split(self, idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, cfg) -> None:
+        """The KL-penalty step (FOCOPS, CUP's second stage) under data parallelism on the wide kernels: the split form of
+        PPOLagEngine._learning_iter_ex_split.  spo_wide_kl_penalty_split gives the KL and the policy-gradient cotangents (F taken
+        as 1), both parts of d(log_std) and the row sums; the actor is backpropagated twice (the PG part into a buffer of its
+        own); one all-reduce of [flat_grad P | g_PG P | sums]; spo_wide_kl_penalty_combine forms g_KL + F g_PG with the global F
+        and the global actor loss; spo_wide_clip_adam_ex (critics' L2 term, joint or actor-only clip, two clocks)."""
+        w, lib, st = self.wide, self.lib, _abi.stream_ptr
+        P, A, off_ls = w.P, self.A, w.off_ls
+        buf = getattr(self, "_split_buf", None)
+        if buf is None or buf.numel() != 2 * P + _abi.KLPEN_SUMS:
+            # (the critics' block of the PG part is never written: it stays 0)
+            buf = self._split_buf = torch.zeros(2 * P + _abi.KLPEN_SUMS, dtype=torch.float32, device=self.dev)
+            self._split_part = torch.zeros(256 * (3 + 2 * _abi.WIDE_MAX_ACT), dtype=torch.float64, device=self.dev)
+        g, pgb, sums, part2 = buf[:P], buf[P:2 * P], buf[2 * P:], self._split_part
+        obs, act, logp_old, tgt_r, tgt_c, adv, old_mean = self._gather(idx, adv_all, extra=(self.mean_old,))
+        n = obs.shape[0]
+        nets = "a" if actor_only else "rca"
+        fw = w.forward_multi(nets, obs, slot=1)
+        mu, ws_a = fw[-1]
+        wss, d_outs = [ws for _, ws in fw], []
+        part, cap = self.loss_partials, self.loss_partials.numel()
+        if not actor_only:
+            (v_r, _), (v_c, _) = fw[0], fw[1]
+            d_vr = torch.empty(n, dtype=torch.float32, device=self.dev)
+            d_vc = torch.empty_like(d_vr)
+            _abi.check(lib.spo_wide_critic_loss(_abi.ptr(v_r), _abi.ptr(v_c), _abi.ptr(tgt_r), _abi.ptr(tgt_c), n, _abi.ptr(d_vr),
+                                                _abi.ptr(d_vc), _abi.ptr(losses_out), _abi.ptr(part), cap, st()), "spo_wide_critic_loss")
+            d_outs = [d_vr, d_vc]
+        d_kl = torch.empty((n, A), dtype=torch.float32, device=self.dev)
+        d_pg = torch.empty_like(d_kl)
+        _abi.check(lib.spo_wide_kl_penalty_split(
+            _abi.ptr(mu), _abi.ptr(self.policy.theta[off_ls:]), _abi.ptr(act), _abi.ptr(logp_old), _abi.ptr(adv), _abi.ptr(old_mean),
+            _abi.ptr(self.std_old), n, A, float(kl_bound), float(pg_coef), _abi.ptr(d_kl), _abi.ptr(d_pg), _abi.ptr(g[off_ls:]),
+            _abi.ptr(pgb[off_ls:]), _abi.ptr(sums), _abi.ptr(part2), part2.numel(), st()), "spo_wide_kl_penalty_split")
+        w.backward_multi(nets, obs, wss, d_outs + [d_kl], g)
+        w.backward_multi("a", obs, [ws_a], [d_pg], pgb)
+        lo = off_ls if actor_only else 0
+        self.comm.all_reduce_sum_(buf[lo:])
+        _abi.check(lib.spo_wide_kl_penalty_combine(_abi.ptr(g), _abi.ptr(pgb), _abi.ptr(sums), P, lo, off_ls,
+                                                   1.0 / self.comm.world_size, float(pg_coef), _abi.ptr(losses_out[2:]), st()),
+                   "spo_wide_kl_penalty_combine")
+        step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
+        _abi.check(lib.spo_wide_clip_adam_ex(_abi.ptr(self.policy.theta), _abi.ptr(g), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v), P,
+                                             w.off_c, off_ls, off_ls, cfg, step_c, step_a, lo, P, lo, 0,
+                                             None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
+                                             st()), "spo_wide_clip_adam_ex")
+
     def learning_iter_ex(self, perm: torch.Tensor, adv: torch.Tensor, actor_loss: int = 0,
                          kl_bound: float = float("inf"), pg_coef: float = 0.0, actor_only: bool = False) -> torch.Tensor:
-        if self.comm.world_size != 1:            # (as PPOLagEngine.learning_iter_ex: the indicator fraction of the KL-penalty loss
-            raise NotImplementedError("focops / cup run on one GPU in this build (no data-parallel form of the "   # couples the
-                                      "KL-penalty minibatch step)")                                             # global minibatch)
         cfg = self._cfg_struct()
         adv = _abi.require_gpu_tensor(adv, "adv", torch.float32)
         M = self.M
@@ -1016,4 +1127,9 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
                 self.adam_step_actor_extra += 1
             else:
                 self.adam_step += 1
+        if self.comm.world_size > 1 and actor_loss == _abi.ACTOR_LOSS_KL_PENALTY:
+            # the split step wrote the global minibatch's actor loss; the critics' losses are the ranks' own
+            crit = self._mean_over_ranks_(losses[:, :2].contiguous())
+            losses[:, :2] = crit
+            return losses
         return self._mean_over_ranks_(losses)

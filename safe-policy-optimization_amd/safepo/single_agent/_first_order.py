@@ -97,6 +97,8 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
         tab = getattr(engine, "exchange_autotune", None)
         dict_args["gradient_exchange"] = (tab or {}).get("chosen") or ("in-kernel, default policy" if getattr(engine, "p2p", None) is not None
                                                                         else "kernel / all-reduce / kernel")
+        if variant in ("focops", "cup"):             # (PPOLagEngine._learning_iter_ex_split, WidePPOLagEngine._minibatch_step_ex_split)
+            dict_args["gradient_exchange"] = "kernel / all-reduce / kernel (split KL-penalty gradient)"
     is_root = comm.rank == 0
     log_dir = args.log_dir if is_root else os.path.join(args.log_dir, f"rank{comm.rank}")
     logger = EpochLogger(log_dir=log_dir, seed=str(args.seed), verbose=is_root)

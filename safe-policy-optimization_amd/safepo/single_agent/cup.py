@@ -1,7 +1,10 @@
 """CUP (Constrained Update Projection): reference safepo/single_agent/cup.py.  Stage one is the PPO update on adv_r
 (cup.py:300-352); stage two trains the actor alone on  nu*coef*ratio*adv_c + KL(pi || pi_after_stage_one)
 (cup.py:354-405) with its own clip_grad_norm_ over the actor's parameters.  Both stages run on the persistent update
-kernel (spo_update_iter_ex); the multiplier is bounded by CUP_NU.
+kernel (spo_update_iter_ex); the multiplier is bounded by CUP_NU.  Data-parallel (torchrun): stage one as a clipped-surrogate
+gradient (spo_ppo_lag_grad) + all-reduce + spo_clip_adam_ex with the two optimiser clocks, stage two as the split KL-penalty
+gradient (spo_kl_penalty_grad, F = 1) + all-reduce + spo_clip_adam_ex over the actor alone (PPOLagEngine._learning_iter_ex_split;
+the wide-network kernels' form: WidePPOLagEngine._minibatch_step_ex_split).
 """
 from __future__ import annotations
 

@@ -2,6 +2,10 @@
 The ppo_lag epoch loop with (a) the multiplier bounded by FOCOPS_NU, (b) the actor loss
     ((KL(pi || pi_old) - (1/FOCOPS_LAM) * ratio * adv) * [KL <= target_kl]).mean()          (focops.py:326-337)
 evaluated in the persistent update kernel (spo_update_iter_ex, SPO_ACTOR_LOSS_KL_PENALTY).
+Data-parallel (torchrun): the split form -- the KL and policy-gradient parts of the actor's gradient and the row sums from
+spo_kl_penalty_grad, one all-reduce, spo_clip_adam_ex with the global fraction of rows inside the bound (engine
+PPOLagEngine._learning_iter_ex_split; outside the persistent kernels' shapes spo_wide_kl_penalty_split /
+spo_wide_kl_penalty_combine, WidePPOLagEngine._minibatch_step_ex_split).
 """
 from __future__ import annotations
 
