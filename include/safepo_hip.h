@@ -645,6 +645,36 @@ int spo_wide_rows_clip_adam_dev_log(float* parts, int64_t rows, float* theta, fl
                                     const spo_ppo_cfg* cfg, double* pow4_dev, float* losses3_out, float* scalars4_out,
                                     double* partial_ws, int partial_capacity, float* loss_log_dev, int64_t* cursor_dev,
                                     int64_t cursor_step, void* stream);
+/* The KL-penalty loss of FOCOPS (focops.py:326-347) and of CUP's actor-only second stage (cup.py:370-386) on the row groups of
+ * spo_wide_ppo_grad_rows: same rows (idx / cursor_dev / rows as there), same theta layout, one launch.  The loss needs
+ * F = mean_i(ind_i), ind_i = [KL_i <= kl_bound], before its cotangent; its gradient is linear in F, g_actor = g_KL + F * g_PG with
+ * both parts sums over rows, so the actor runs in TWO kinds of workgroup per row group: one backpropagates ind_i d(KL_i)/d(mean) / rows
+ * (d(log_std) term ind_i (vrat - 1) / rows), the other -(pg_coef / rows) d(ratio_i adv_i)/d(mean) with F taken as 1; the critics'
+ * workgroups (absent with actor_only) are those of the PPO launch.  Per-row arithmetic: spo_wide_kl_penalty_split's.
+ * old_mean [M, act_dim] is read through the index window like act, old_std is [act_dim]; kl_bound = +inf (CUP) gives ind_i = 1.
+ * spo_wide_kl_penalty_grad_rows_supported -- 1 when spo_wide_grad_rows_supported holds AND the launch's own LDS need (the old
+ *   distribution of the 16 rows sits behind the actor's images) fits one CU; 0 with SPO_WIDE_ROWS=0.
+ * spo_wide_kl_penalty_rows_part_floats -- floats of `parts` (actor_begin = the offset of log_std, 2 * critic parameters); the tail
+ *   behind the row groups' parts holds n_params + SPO_KLPEN_SUMS floats a caller may hand to the reduce as pg_grad / sums.
+ * spo_wide_kl_penalty_reduce_parts -- the groups added in group order (deterministic, no atomics):
+ *   combine == 0 (data-parallel): grad[lo, n_params) = the critics' data gradients (no L2 term) and g_KL in the actor's block,
+ *     lo = actor_begin with actor_only, else 0; pg_grad[actor_begin, n_params) (indexed like grad) = g_PG with F = 1;
+ *     sums[SPO_KLPEN_SUMS] = {0, 0, count of ind, sum ind*KL, sum ratio*adv, rows} (spo_wide_kl_penalty_split's layout);
+ *     losses_out[0..1] = the critics' data losses (not with actor_only).  Then the all-reduce and spo_wide_kl_penalty_combine.
+ *   combine != 0 (one GPU): additionally the actor's block of grad becomes g_KL + F * g_PG, F = sums[2] / sums[5], and
+ *     losses_out[2] = (sums[3] - pg_coef * F * sums[4]) / sums[5] -- bit for bit what combine == 0 followed by
+ *     spo_wide_kl_penalty_combine(grad_scale = 1) gives.  Then spo_wide_clip_adam_ex / spo_wide_clip_adam_dev_log.
+ * Both launch entry points refuse null pointers, shapes outside ..._supported and rows outside 1..256 before any launch. */
+int spo_wide_kl_penalty_grad_rows_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows);
+int64_t spo_wide_kl_penalty_rows_part_floats(int64_t n_params, int64_t actor_begin, int64_t rows);
+int spo_wide_kl_penalty_grad_rows(const float* theta, const spo_mlp_net* critic, const spo_mlp_net* actor, const float* obs,
+                                  const float* act, const float* logp_old, const float* target_r, const float* target_c,
+                                  const float* adv, const float* old_mean, const float* old_std, const int64_t* idx,
+                                  const int64_t* cursor_dev, int64_t rows, float kl_bound, float pg_coef, int actor_only,
+                                  float* parts, void* stream);
+int spo_wide_kl_penalty_reduce_parts(const float* parts, int64_t rows, int64_t n_params, int64_t actor_begin, int actor_only,
+                                     int combine, float pg_coef, float* grad, float* pg_grad, float* sums, float* losses_out,
+                                     void* stream);
 /* dsts[k][i, :] = srcs[k][idx[i], :] for k < count (<= SPO_GATHER_MAX) row-major arrays of widths[k] floats per row: the
  * minibatch gather of a step (the reference's DataLoader, ppo_lag.py:298-305) in one launch. */
 #define SPO_GATHER_MAX 8

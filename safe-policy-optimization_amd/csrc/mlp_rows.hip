@@ -20,6 +20,11 @@
 //   * every workgroup writes its row group's PARTIAL gradient (theta's layout) and loss sums to parts[group]; a second, tiny launch
 //     (spo_wide_reduce_parts) adds the groups in fixed order into the flat gradient -- deterministic, and exactly where the
 //     data-parallel all-reduce and spo_wide_clip_adam take over.
+//   * the KL-penalty loss of FOCOPS / CUP's second stage (focops.py:326-347, cup.py:370-386) is a second loss form of the same kernel
+//     (the LOSS template parameter): its gradient is g_KL + F g_PG with F the minibatch's fraction of rows inside the KL bound, both
+//     parts sums over rows, so the actor runs in two kinds of workgroup -- one cotangent each, see mlp_rows_grad_kernel -- and the
+//     group sum (spo_wide_kl_penalty_reduce_parts) combines them, or leaves them apart for a data-parallel all-reduce.  Measured
+//     (profiles/klpen_rows/): the launch 1.06 x the PPO launch's time, the FOCOPS step at [128, 128] 84 -> 36 us.
 // fp32 v_mfma_f32_16x16x4_f32 throughout (bitwise an fmaf chain); results differ from the launch-per-layer path in summation
 // order only.
 // Measured (hidden [128, 128], 60 / 8, 64 rows, one MI355X, profiles/r06/wide_step.txt, wide_rows_phase_cycles.txt): the kernel
@@ -51,19 +56,23 @@ __host__ __device__ inline int mr_ivar(int AP) { return MR_LS + AP; }
 __host__ __device__ inline int mr_dls(int AP) { return MR_LS + 2 * AP; }
 __host__ __device__ inline int mr_ract(int AP) { return MR_LS + 2 * AP + 16 * AP; }
 __host__ __device__ inline int mr_misc(int AP) { return MR_LS + 2 * AP + 32 * AP; }
+// the KL-penalty launch only (behind mr_misc): the rows' old means [16][act_dim], then 1 / old_std, the variance ratio and its log
+__host__ __device__ inline int mr_klx(int AP) { return 16 * AP + 3 * AP; }
+enum { MR_PPO = 0, MR_KLPEN = 1 };                  // loss form of a launch (template parameter of the gradient kernel)
 
 constexpr float LOG_SQRT_2PI_F = 0.91893853320467274178f;               // (as csrc/ma_net.hip)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // four consecutive floats at any dword address
 
 struct MrNet {
   int n;                                           // Linear layers
-  int kind;                                        // 0 reward critic, 1 cost critic, 2 actor
+  int kind;                                        // 0 reward critic, 1 cost critic, 2 actor (KL-penalty launch: its KL part), 3 actor again (PG part)
   int d[SPO_MLP_MAX_LAYERS + 1];                   // widths: d[0] = obs_dim, d[n] = 1 or act_dim
   int64_t w[SPO_MLP_MAX_LAYERS], b[SPO_MLP_MAX_LAYERS];   // offsets of W_l [d[l+1]][d[l]] and b_l in theta
   // the LDS map (mr_level / mr_pz / mr_images_end), tabulated by the host: the kernel reads an entry with one scalar load where the
   // loops of mr_level cost it a chain of dependent ones at every stage (~1 us per stage, measured)
   int pr[SPO_MLP_MAX_LAYERS + 1], hr[SPO_MLP_MAX_LAYERS + 1], ht[SPO_MLP_MAX_LAYERS + 1];
   int pz, zbase;
+  int64_t poff;                                    // KL-penalty launch: where this network's partial gradient sits in a group's part, minus w[0]'s block
 };
 struct MrArgs {
   const float* theta; const float* obs; const float* act; const float* logp_old; const float* tgt_r; const float* tgt_c; const float* adv;
@@ -71,7 +80,9 @@ struct MrArgs {
   float* parts; int64_t stride; int64_t P; int64_t ls_off;
   int rows, R, n_nets, A;
   float clip;
-  MrNet net[3];
+  const float* old_mean; const float* old_std;     // KL-penalty launch: old_mean[M][act_dim] (read through the index window), old_std[act_dim]
+  float kl_bound, pg_coef;
+  MrNet net[4];
 };
 
 __host__ __device__ inline int mr_up16(int v) { return (v + 15) & ~15; }
@@ -186,7 +197,12 @@ __device__ unsigned long long g_mr_prof[2][32];
 #define MR_STAMP(k) do { } while (0)
 #endif
 
-template <bool VEC>
+// LOSS == MR_KLPEN (FOCOPS focops.py:326-347, CUP's second stage cup.py:370-386): the actor runs in TWO kinds of workgroup, both
+// with its forward on their 16 rows -- kind 2 backpropagates ind_i d(KL_i)/d(mean) / rows, kind 3 -(pg_coef / rows) d(ratio_i adv_i)/d(mean)
+// (the fraction F of rows inside the bound taken as 1: the loss's gradient is g_KL + F g_PG, and F is known once every row's
+// indicator is, i.e. in the group sum behind this launch).  One cotangent per workgroup: the backward stages are those of the
+// clipped surrogate.  Per-row arithmetic: wide_klpen_split_kernel's (csrc/ma_net.hip).
+template <bool VEC, int LOSS = MR_PPO>
 __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, q = lane >> 4;
@@ -204,7 +220,10 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
   const int AP = mr_ap(a.A), MR_IVAR = mr_ivar(AP);
   float* const dls = misc + mr_dls(AP);                                 // [act_dim][16] d(log_std) terms
   float* const ract = misc + mr_ract(AP);                               // [16][act_dim] the rows' actions
-  float* const part = a.parts + (int64_t)rg * a.stride;
+  float* const gpart = a.parts + (int64_t)rg * a.stride;                // this group's part (the row sums sit at gpart[P ..])
+  float* const part = LOSS == MR_KLPEN ? gpart + nn.poff : gpart;
+  float* const klx = misc + mr_misc(AP);                                // KL-penalty launch: [16][act_dim] old means, 1 / old_std, vrat, log vrat
+  const bool isact = LOSS == MR_KLPEN ? kind >= 2 : kind == 2;
   const int OUT = nn.d[n];
   int stamp = 0;
   MR_STAMP(stamp++);
@@ -215,10 +234,16 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
     const int64_t at = base + row0 + imin_(tid, nrows - 1);
     ridx[tid] = a.idx ? a.idx[at] : at;
   }
-  if (kind == 2 && tid >= 64 && tid < 64 + OUT) {
+  if (isact && tid >= 64 && tid < 64 + OUT) {
     const float ls = a.theta[a.ls_off + tid - 64], sd = __expf(ls);
     misc[MR_LS + tid - 64] = ls;
     misc[MR_IVAR + tid - 64] = 1.f / (sd * sd);
+    if constexpr (LOSS == MR_KLPEN) {
+      const float iso = 1.f / a.old_std[tid - 64];
+      const float sr = sd * iso;                     // kl_normal_normal: var_ratio = (p.scale / q.scale)^2
+      const float vrat = sr * sr;
+      klx[16 * AP + tid - 64] = iso; klx[17 * AP + tid - 64] = vrat; klx[18 * AP + tid - 64] = logf(vrat);
+    }
   }
   // the weights of a wave's FIRST output tile of a layer (its first eight input tiles) and that tile's biases, requested one stage
   // ahead of their use -- before the barrier that publishes their B operand
@@ -247,15 +272,19 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
         lds[L0.hr + r * S0 + c] = v;
         lds[L0.ht + c * MR_TS + r] = v;
       }
-      if (kind == 2) {
+      if (isact) {
         const float* __restrict__ sa = a.act + ridx[r] * (int64_t)OUT;
         for (int c = lane; c < OUT; c += 64) ract[r * OUT + c] = sa[c];
+        if constexpr (LOSS == MR_KLPEN) {
+          const float* __restrict__ so = a.old_mean + ridx[r] * (int64_t)OUT;
+          for (int c = lane; c < OUT; c += 64) klx[r * OUT + c] = so[c];
+        }
       }
     }
     if (tid >= 448 && tid < 464) {
       const int64_t gi = ridx[tid - 448];
       misc[MR_RTGT + tid - 448] = kind == 0 ? a.tgt_r[gi] : (kind == 1 ? a.tgt_c[gi] : 0.f);
-      if (kind == 2) { misc[MR_RADV + tid - 448] = a.adv[gi]; misc[MR_RLOGP + tid - 448] = a.logp_old[gi]; }
+      if (isact) { misc[MR_RADV + tid - 448] = a.adv[gi]; misc[MR_RLOGP + tid - 448] = a.logp_old[gi]; }
     }
   }
   __syncthreads();
@@ -330,11 +359,33 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
   if (tid < 16) {
     const int r = tid;
     float da = 0.f, lt = 0.f;
+    [[maybe_unused]] float cnt = 0.f;
     if (r < nrows) {
       if (kind < 2) {                                    // MSE of a critic (ppo_lag.py:306-309)
         const float diff = lds[Ln.hr + r * SN] - misc[MR_RTGT + r];
         lt = diff * diff;
         da = 2.f * diff * inv_n;
+      } else if (LOSS == MR_KLPEN && kind == 2) {        // ind_i KL_i and its indicator (focops.py:326-333)
+        float kl = 0.f;
+        for (int k = 0; k < OUT; ++k) {
+          const float dm = (lds[Ln.hr + r * SN + k] - klx[r * OUT + k]) * klx[16 * AP + k];       // (loc_p - loc_q) / scale_q
+          kl += 0.5f * (klx[17 * AP + k] + dm * dm - 1.f - klx[18 * AP + k]);
+        }
+        const float ind = (kl <= a.kl_bound) ? 1.f : 0.f;
+        da = ind * inv_n;
+        lt = ind * kl;
+        cnt = ind;
+      } else if (LOSS == MR_KLPEN) {                     // ratio_i adv_i with F taken as 1 (focops.py:334-341)
+        float lp = 0.f;
+        for (int k = 0; k < OUT; ++k) {
+          const float ls = misc[MR_LS + k], ivar = misc[MR_IVAR + k];
+          const float dif = ract[r * OUT + k] - lds[Ln.hr + r * SN + k];
+          lp += -(dif * dif) * (0.5f * ivar) - ls - LOG_SQRT_2PI_F;
+        }
+        const float ad = misc[MR_RADV + r];
+        const float ratio = __expf(lp - misc[MR_RLOGP + r]);
+        da = -(a.pg_coef * ad * ratio) * inv_n;
+        lt = ratio * ad;
       } else {                                           // clipped surrogate (ppo_lag.py:316-319): wide_ppo_loss_kernel's arithmetic
         const float clip_lo = 1.f - a.clip, clip_hi = 1.f + a.clip;
         float lp = 0.f;
@@ -357,6 +408,7 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
       }
     }
     rowa[r] = da; rowl[r] = lt;
+    if constexpr (LOSS == MR_KLPEN) misc[MR_RTGT + r] = cnt;     // (the targets' slot: an actor's workgroup has none)
   }
   __syncthreads();
   for (int e = tid; e < 16 * Ln.pr; e += 512) {
@@ -364,14 +416,19 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
     float dz = 0.f;
     if (u < OUT && r < nrows) {
       if (kind < 2) dz = rowa[r];
-      else {
+      else if (LOSS == MR_KLPEN && kind == 2) {
+        const float iso = klx[16 * AP + u];
+        const float dm = (lds[Ln.hr + r * SN + u] - klx[r * OUT + u]) * iso;
+        dz = rowa[r] * dm * iso;
+        dls[u * 16 + r] = rowa[r] * (klx[17 * AP + u] - 1.f);
+      } else {
         const float ivar = misc[MR_IVAR + u];
         const float dif = ract[r * OUT + u] - lds[Ln.hr + r * SN + u];
         const float z = dif * ivar;
         dz = rowa[r] * z;
         dls[u * 16 + r] = rowa[r] * (dif * z - 1.f);
       }
-    } else if (kind == 2 && u < OUT) dls[u * 16 + r] = 0.f;
+    } else if (isact && u < OUT) dls[u * 16 + r] = 0.f;
     ZR[r * ZS + u] = dz;
     ZT[u * MR_TS + r] = dz;
   }
@@ -379,9 +436,16 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
   if (tid == 0) {
     double s = 0.0;
     for (int r = 0; r < 16; ++r) s += (double)rowl[r];
-    part[a.P + kind] = (float)s;
+    if constexpr (LOSS == MR_KLPEN) {
+      // a group's row sums: [P + 0 / 1] the critics' squared errors, [P + 2] count of ind, [P + 3] sum ind*KL, [P + 4] sum ratio*adv
+      if (kind == 2) {
+        double c = 0.0;
+        for (int r = 0; r < 16; ++r) c += (double)misc[MR_RTGT + r];
+        gpart[a.P + 2] = (float)c; gpart[a.P + 3] = (float)s;
+      } else gpart[a.P + (kind == 3 ? 4 : kind)] = (float)s;
+    } else part[a.P + kind] = (float)s;
   }
-  if (kind == 2 && tid >= 64 && tid < 64 + OUT) {
+  if (isact && tid >= 64 && tid < 64 + OUT) {
     const int u = tid - 64;
     double s = 0.0;
     for (int r = 0; r < 16; ++r) s += (double)dls[u * 16 + r];
@@ -499,6 +563,47 @@ __global__ __launch_bounds__(256) void mlp_rows_reduce_kernel(const float* __res
   }
 }
 
+// The group sum behind the KL-penalty launch (spo_wide_kl_penalty_reduce_parts).  A group's part: [0, P) the critics' gradients and
+// the actor's g_KL, [P, P + 5) its row sums, [pgoff, pgoff + P - ab) the actor's g_PG (F taken as 1).  Groups are added in group
+// order; every thread forms the minibatch's row sums itself (<= 16 groups, the same order: the same F in every thread), so the
+// combine g_KL + F g_PG needs no second pass.  combine's expressions are wide_klpen_combine_kernel's (csrc/ma_net.hip) at scale 1.
+struct MrKlReduceArgs {
+  const float* parts; int R; int64_t stride, P, ab, lo, pgoff, rows;
+  int n_loss, combine; float pg_coef;
+  float* grad; float* pg_grad; float* sums; float* losses;
+};
+__global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(MrKlReduceArgs a) {
+  double c = 0.0, k = 0.0, ra = 0.0;
+  for (int g = 0; g < a.R; ++g) {
+    const float* __restrict__ sp = a.parts + (int64_t)g * a.stride + a.P;
+    c += (double)sp[2]; k += (double)sp[3]; ra += (double)sp[4];
+  }
+  const float cnt = (float)c, skl = (float)k, sra = (float)ra, nrow = (float)a.rows;
+  const float frac = cnt / nrow;
+  for (int64_t i = a.lo + (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.P; i += (int64_t)gridDim.x * 256) {
+    float s = a.parts[i];
+    for (int g = 1; g < a.R; ++g) s += a.parts[(int64_t)g * a.stride + i];
+    if (i >= a.ab) {
+      const float* __restrict__ pp = a.parts + a.pgoff + (i - a.ab);
+      float p = pp[0];
+      for (int g = 1; g < a.R; ++g) p += pp[(int64_t)g * a.stride];
+      a.pg_grad[i] = p;
+      if (a.combine) s = s + frac * p;
+    }
+    a.grad[i] = s;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.sums[0] = 0.f; a.sums[1] = 0.f; a.sums[2] = cnt; a.sums[3] = skl; a.sums[4] = sra; a.sums[5] = nrow; a.sums[6] = 0.f; a.sums[7] = 0.f;
+    if (a.combine && a.losses) a.losses[2] = (skl - a.pg_coef * frac * sra) / nrow;
+  }
+  if (blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 64 + a.n_loss && a.losses) {
+    const int q = threadIdx.x - 64;
+    double s = 0.0;
+    for (int g = 0; g < a.R; ++g) s += (double)a.parts[(int64_t)g * a.stride + a.P + q];
+    a.losses[q] = (float)(s / (double)a.rows);
+  }
+}
+
 // ---- the optimiser behind the row groups in TWO launches (world size 1, device-resident clocks: the replayed step).
 // The launch-per-network step ended in wide_prep_kernel -> wide_coef_kernel -> wide_adam_dev_kernel (csrc/ma_net.hip): with the
 // group sum in front, four launches of ~4.5 us that each do < 1 us of work.  Here (1) the group sum, the critics' L2 gradient, the
@@ -592,7 +697,7 @@ bool mr_enabled() {
   return on;
 }
 int mr_fill_net(const spo_mlp_net* net, int64_t off, int kind, MrNet* o) {
-  o->n = net->n_layers; o->kind = kind;
+  o->n = net->n_layers; o->kind = kind; o->poff = 0;
   for (int k = 0; k <= o->n; ++k) o->d[k] = net->dims[k];
   for (int l = 0; l < o->n; ++l) {
     o->w[l] = off; off += (int64_t)o->d[l + 1] * o->d[l];
@@ -614,6 +719,14 @@ bool mr_net_ok(const spo_mlp_net* net, int A) {
   return (size_t)mr_lds_floats(t, A) * sizeof(float) <= MR_MAX_LDS;
 }
 int64_t mr_stride(int64_t P) { return (P + 4 + 3) & ~(int64_t)3; }
+// the KL-penalty launch's part of one row group: the gradient and eight row-sum slots, then the actor's policy-gradient part
+int64_t mr_kl_pgoff(int64_t P) { return (P + 8 + 3) & ~(int64_t)3; }
+int64_t mr_kl_stride(int64_t P, int64_t ab) { return mr_kl_pgoff(P) + ((P - ab + 3) & ~(int64_t)3); }
+// LDS of the KL-penalty launch: the images of the wider of the two networks, and the old distribution behind the actor's
+size_t mr_kl_lds_floats(const MrNet& critic, const MrNet& actor, int A) {
+  const size_t lc = (size_t)mr_lds_floats(critic, A), la = (size_t)mr_lds_floats(actor, A) + (size_t)mr_klx(mr_ap(A));
+  return la > lc ? la : lc;
+}
 }  // namespace
 
 #ifdef SPO_MR_PROF
@@ -727,5 +840,91 @@ extern "C" int spo_wide_rows_clip_adam_dev_log(float* parts, int64_t rows, float
   hipLaunchKernelGGL(mlp_rows_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
   hipLaunchKernelGGL(mlp_rows_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
   SPO_LAUNCH_CHECK("spo_wide_rows_clip_adam_dev_log");
+  return 0;
+}
+
+// ---- the KL-penalty loss of FOCOPS (focops.py:326-347) and CUP's second stage (cup.py:370-386) on the row groups
+extern "C" int spo_wide_kl_penalty_grad_rows_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows) {
+  if (!actor || !spo_wide_grad_rows_supported(critic, actor, rows)) return 0;
+  const int A = actor->dims[actor->n_layers];
+  MrNet c, t;
+  mr_fill_net(critic, 0, 0, &c);
+  mr_fill_net(actor, 0, 2, &t);
+  return mr_kl_lds_floats(c, t, A) * sizeof(float) <= MR_MAX_LDS ? 1 : 0;
+}
+
+extern "C" int64_t spo_wide_kl_penalty_rows_part_floats(int64_t n_params, int64_t actor_begin, int64_t rows) {
+  if (n_params < 1 || rows < 1 || actor_begin < 0 || actor_begin > n_params) return -1;
+  // (behind the groups: room for a pg_grad indexed like grad and the sums, for callers that only want the combined gradient)
+  return ((rows + 15) / 16) * mr_kl_stride(n_params, actor_begin) + ((n_params + 3) & ~(int64_t)3) + SPO_KLPEN_SUMS + 4;
+}
+
+extern "C" int spo_wide_kl_penalty_grad_rows(const float* theta, const spo_mlp_net* critic, const spo_mlp_net* actor, const float* obs,
+                                             const float* act, const float* logp_old, const float* target_r, const float* target_c,
+                                             const float* adv, const float* old_mean, const float* old_std, const int64_t* idx,
+                                             const int64_t* cursor_dev, int64_t rows, float kl_bound, float pg_coef, int actor_only,
+                                             float* parts, void* stream) {
+  SPO_REQUIRE(theta && critic && actor && obs && act && logp_old && adv && old_mean && old_std && parts,
+              "wide_kl_penalty_grad_rows: null pointer");
+  SPO_REQUIRE(actor_only || (target_r && target_c), "wide_kl_penalty_grad_rows: critic targets are NULL");
+  SPO_REQUIRE(rows >= 1 && rows <= 16 * MR_MAX_GROUPS, "wide_kl_penalty_grad_rows: rows %lld outside [1,%d]", (long long)rows,
+              16 * MR_MAX_GROUPS);
+  SPO_REQUIRE(spo_wide_kl_penalty_grad_rows_supported(critic, actor, rows),
+              "wide_kl_penalty_grad_rows: shape outside the row-group kernel (rows %lld)", (long long)rows);
+  MrArgs a{};
+  a.theta = theta; a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
+  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef;
+  a.idx = idx; a.cursor = cursor_dev; a.rows = (int)rows; a.R = (int)((rows + 15) / 16);
+  const int64_t Pc = spo_mlp_param_count(critic);
+  a.A = actor->dims[actor->n_layers];
+  a.ls_off = 2 * Pc;
+  a.P = 2 * Pc + a.A + spo_mlp_param_count(actor);
+  a.parts = parts; a.stride = mr_kl_stride(a.P, a.ls_off);
+  int k = 0;
+  if (!actor_only) {
+    mr_fill_net(critic, 0, 0, &a.net[k++]);
+    mr_fill_net(critic, Pc, 1, &a.net[k++]);
+  }
+  mr_fill_net(actor, 2 * Pc + a.A, 2, &a.net[k++]);
+  mr_fill_net(actor, 2 * Pc + a.A, 3, &a.net[k]);
+  a.net[k].poff = mr_kl_pgoff(a.P) - a.ls_off;         // g_PG[i - actor_begin] behind the group's gradient and row sums
+  a.n_nets = k + 1;
+  MrNet c0;
+  mr_fill_net(critic, 0, 0, &c0);
+  const size_t sh = mr_kl_lds_floats(c0, a.net[k], a.A) * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  bool vec = true;
+  for (int i = 0; i < a.n_nets; ++i)
+    for (int l = 0; l < a.net[i].n; ++l) vec = vec && (a.net[i].d[l] & 3) == 0;
+  static bool done_dev[SPO_MAX_DEVICES] = {};
+  bool& done = done_dev[spo::current_device_slot()];
+  if (!done) {
+    for (const void* f : {reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true, MR_KLPEN>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false, MR_KLPEN>)})
+      if (int rc = spo::hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MR_MAX_LDS),
+                                  "hipFuncSetAttribute(mlp_rows, KL penalty)"))
+        return rc;
+    done = true;
+  }
+  if (vec) hipLaunchKernelGGL((mlp_rows_grad_kernel<true, MR_KLPEN>), dim3(a.n_nets * a.R), dim3(512), sh, st, a);
+  else hipLaunchKernelGGL((mlp_rows_grad_kernel<false, MR_KLPEN>), dim3(a.n_nets * a.R), dim3(512), sh, st, a);
+  SPO_LAUNCH_CHECK("spo_wide_kl_penalty_grad_rows");
+  return 0;
+}
+
+extern "C" int spo_wide_kl_penalty_reduce_parts(const float* parts, int64_t rows, int64_t n_params, int64_t actor_begin, int actor_only,
+                                                int combine, float pg_coef, float* grad, float* pg_grad, float* sums, float* losses_out,
+                                                void* stream) {
+  SPO_REQUIRE(parts && grad && pg_grad && sums, "wide_kl_penalty_reduce_parts: null pointer");
+  SPO_REQUIRE(rows >= 1 && rows <= 16 * MR_MAX_GROUPS && n_params >= 1 && actor_begin >= 0 && actor_begin <= n_params,
+              "wide_kl_penalty_reduce_parts: bad args (rows %lld, n_params %lld, actor_begin %lld)", (long long)rows, (long long)n_params,
+              (long long)actor_begin);
+  const int64_t lo = actor_only ? actor_begin : 0;
+  MrKlReduceArgs a{parts, (int)((rows + 15) / 16), mr_kl_stride(n_params, actor_begin), n_params, actor_begin, lo, mr_kl_pgoff(n_params),
+                   rows, actor_only ? 0 : 2, combine, pg_coef, grad, pg_grad, sums, losses_out};
+  int64_t blocks = (n_params - lo + 255) / 256;
+  blocks = blocks > 512 ? 512 : (blocks < 1 ? 1 : blocks);
+  hipLaunchKernelGGL(mlp_rows_klpen_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  SPO_LAUNCH_CHECK("spo_wide_kl_penalty_reduce_parts");
   return 0;
 }

@@ -93,6 +93,10 @@ PROTOTYPES = {
     "spo_wide_reduce_parts": (c_int, [P, c_int64, c_int64, c_int, P, P, P]),
     "spo_wide_rows_clip_adam_dev_log": (c_int, [P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, POINTER(PpoCfg), P, P, P, P,
                                                 c_int, P, P, c_int64, P]),
+    "spo_wide_kl_penalty_grad_rows_supported": (c_int, [POINTER(MlpNet), POINTER(MlpNet), c_int64]),
+    "spo_wide_kl_penalty_rows_part_floats": (c_int64, [c_int64, c_int64, c_int64]),
+    "spo_wide_kl_penalty_grad_rows": (c_int, [P, POINTER(MlpNet), POINTER(MlpNet)] + [P] * 10 + [c_int64, c_float, c_float, c_int, P, P]),
+    "spo_wide_kl_penalty_reduce_parts": (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int, c_float, P, P, P, P, P]),
     "spo_gather_rows": (c_int, [c_int, P, P, P, P, c_int64, P]),
     "spo_gather_rows_at": (c_int, [c_int, P, P, P, P, P, c_int64, P]),
     "spo_values_boundary_step_fold": (c_int, [P] * 4 + [c_int, c_int] + [P] * 16 + [c_int, c_int64, c_int64, c_int64, c_int, P, P,

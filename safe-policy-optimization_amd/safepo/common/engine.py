@@ -857,7 +857,10 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
     model.py:131; the isaac_gym_specific_cfg regime of ppo_lag.py:54-65), obs_dim > 128 or act_dim > 16 (HumanoidVelocity:
     376 / 17): collect, boundary logic, GAE, statistics and the KL early stop are shared with PPOLagEngine; the policy step, the
     bootstrap values, the full-batch actor evaluation and the minibatch step (clipped surrogate, and the KL-penalty loss of
-    FOCOPS / CUP) run on the wide-network kernels (safepo.common.wide).  Data-parallel: env shards as PPOLagEngine, the flat
+    FOCOPS / CUP) run on the wide-network kernels (safepo.common.wide).  A minibatch of <= 256 rows whose images fit one CU's LDS
+    takes the row-group gradient kernel (csrc/mlp_rows.hip: one launch for gather, forwards, losses and backward passes) for
+    all three losses -- minibatch_step, and minibatch_step_ex / _minibatch_step_ex_split where _row_group_step_ok holds --, else
+    the launch-per-network step.  Data-parallel: env shards as PPOLagEngine, the flat
     gradient all-reduced (RCCL) per minibatch step before the joint clip."""
 
     def __init__(self, policy: ActorVCritic, num_envs: int, steps: int, config: dict, device,
@@ -991,13 +994,54 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
 
     def minibatch_step_ex(self, idx, adv_all, losses_out, actor_loss, kl_bound, pg_coef, actor_only, dev_clock: bool = False,
                           cfg=None) -> None:
-        """One FOCOPS minibatch step (focops.py:312-347) or one step of CUP's actor-only second stage (cup.py:370-386) on the
-        wide kernels: spo_update_iter_ex's semantics (include/safepo_hip.h), one minibatch."""
+        """One FOCOPS minibatch step (focops.py:312-347), one step of CUP's first stage (cup.py:300-351: the clipped surrogate on
+        adv_all) or of its actor-only second stage (cup.py:370-386) on the wide kernels: spo_update_iter_ex's semantics
+        (include/safepo_hip.h), one minibatch.  The gradient comes from the row-group kernel where _row_group_step_ok holds; the
+        optimiser launches are the same either way."""
         w, lib, st = self.wide, self.lib, _abi.stream_ptr
         cfg = self._cfg_struct() if cfg is None else cfg
         klpen = actor_loss == _abi.ACTOR_LOSS_KL_PENALTY
         if klpen and self.comm.world_size > 1:
             return self._minibatch_step_ex_split(idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, cfg)
+        g, off_ls, A = self.flat_grad, w.off_ls, self.A
+        part, cap = self.loss_partials, self.loss_partials.numel()
+        if self._row_group_step_ok(idx.numel(), actor_loss, actor_only):
+            # gather + forward + loss + backward in ONE launch split over the rows (csrc/mlp_rows.hip), then the group sum
+            d, M = self.buffer.data, self.M
+            arrays = (d["obs"].view(M, self.D), d["act"].view(M, A), d["log_prob"].view(M), d["target_value_r"].view(M),
+                      d["target_value_c"].view(M), (self.buffer.adv_mix if adv_all is None else adv_all).view(M))
+            if klpen:                              # the KL-penalty form: g_KL + F g_PG combined in the group sum
+                w.klpen_grad_rows(idx, *arrays, self.mean_old, self.std_old, kl_bound, pg_coef, actor_only, g, losses_out)
+            else:                                  # CUP's first stage (cup.py:300-351): the clipped surrogate on adv_all
+                w.grad_rows(idx, *arrays, float(cfg.clip), g, losses_out)
+                self._reduce_flat_grad()
+        else:
+            self._launch_per_network_grad_ex(idx, adv_all, losses_out, klpen, kl_bound, pg_coef, actor_only, cfg)
+        step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
+        lo, norm0 = (off_ls, off_ls) if actor_only else (0, 0)
+        if dev_clock:
+            self._clip_adam_dev(cfg, lo, w.P, norm0, 0, None if actor_only else losses_out, losses_out,
+                                idx if isinstance(idx, PermWindow) else None)
+            return
+        _abi.check(lib.spo_wide_clip_adam_ex(_abi.ptr(self.policy.theta), _abi.ptr(g), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v), w.P,
+                                             w.off_c, w.off_ls, w.off_ls, cfg, step_c, step_a, lo, w.P, norm0, 0,
+                                             None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
+                                             st()), "spo_wide_clip_adam_ex")
+
+    def _row_group_step_ok(self, rows: int, actor_loss: int, actor_only: bool) -> bool:
+        """Whether a step of learning_iter_ex's minibatch loop (i.e. outside _feature_split_kernel_ok) at `rows` rows takes the
+        row-group gradient launch of csrc/mlp_rows.hip: the KL-penalty loss (FOCOPS, CUP's second stage; one GPU or data-parallel)
+        where spo_wide_kl_penalty_grad_rows_supported holds, the clipped surrogate with the critics (CUP's first stage) where
+        spo_wide_grad_rows_supported does.  Otherwise -- more than 256 rows, [1024, 1024, 512], [256, 256] at 376 inputs,
+        SPO_WIDE_ROWS=0 -- the launch-per-network step."""
+        if actor_loss == _abi.ACTOR_LOSS_KL_PENALTY:
+            return self.wide.klpen_rows_ok(rows)
+        return not actor_only and self.wide.rows_grad_ok(rows)
+
+    def _launch_per_network_grad_ex(self, idx, adv_all, losses_out, klpen, kl_bound, pg_coef, actor_only, cfg) -> None:
+        """minibatch_step_ex's gradient as rounds 4-5 formed it: gather, one-workgroup-per-network forward, the loss kernels,
+        one-workgroup-per-network backward (world size 1 for the KL-penalty loss)."""
+        w, lib, st = self.wide, self.lib, _abi.stream_ptr
         got = self._gather(idx, adv_all, extra=(self.mean_old,) if klpen else ())
         obs, act, logp_old, tgt_r, tgt_c, adv = got[:6]
         n = obs.shape[0]
@@ -1026,20 +1070,12 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
                    "spo_wide_actor_loss")
         w.backward_multi(nets, obs, wss, d_outs + [d_mu], g)
         self._reduce_flat_grad(off_ls if actor_only else 0)
-        step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
-        lo, norm0 = (off_ls, off_ls) if actor_only else (0, 0)
-        if dev_clock:
-            self._clip_adam_dev(cfg, lo, w.P, norm0, 0, None if actor_only else losses_out, losses_out,
-                                idx if isinstance(idx, PermWindow) else None)
-            return
-        _abi.check(lib.spo_wide_clip_adam_ex(_abi.ptr(self.policy.theta), _abi.ptr(g), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v), w.P,
-                                             w.off_c, w.off_ls, w.off_ls, cfg, step_c, step_a, lo, w.P, norm0, 0,
-                                             None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
-                                             st()), "spo_wide_clip_adam_ex")
 
     def _minibatch_step_ex_split(self, idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, cfg) -> None:
         """The KL-penalty step (FOCOPS, CUP's second stage) under data parallelism on the wide kernels: the split form of
-        PPOLagEngine._learning_iter_ex_split.  spo_wide_kl_penalty_split gives the KL and the policy-gradient cotangents (F taken
+        PPOLagEngine._learning_iter_ex_split.  On the row-group kernel (_row_group_step_ok) ONE launch + the group sum with
+        combine = 0 leave g_KL, g_PG (F taken as 1) and the row sums in [flat_grad | g_PG | sums]; otherwise
+        spo_wide_kl_penalty_split gives the KL and the policy-gradient cotangents (F taken
         as 1), both parts of d(log_std) and the row sums; the actor is backpropagated twice (the PG part into a buffer of its
         own); one all-reduce of [flat_grad P | g_PG P | sums]; spo_wide_kl_penalty_combine forms g_KL + F g_PG with the global F
         and the global actor loss; spo_wide_clip_adam_ex (critics' L2 term, joint or actor-only clip, two clocks)."""
@@ -1051,6 +1087,32 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
             buf = self._split_buf = torch.zeros(2 * P + _abi.KLPEN_SUMS, dtype=torch.float32, device=self.dev)
             self._split_part = torch.zeros(256 * (3 + 2 * _abi.WIDE_MAX_ACT), dtype=torch.float64, device=self.dev)
         g, pgb, sums, part2 = buf[:P], buf[P:2 * P], buf[2 * P:], self._split_part
+        part, cap = self.loss_partials, self.loss_partials.numel()
+        lo = off_ls if actor_only else 0
+        if self._row_group_step_ok(idx.numel(), _abi.ACTOR_LOSS_KL_PENALTY, actor_only):
+            # one launch for gather, forwards, losses and BOTH actor backward passes (csrc/mlp_rows.hip), the group sum straight
+            # into [g | pgb | sums]
+            d, M = self.buffer.data, self.M
+            w.klpen_grad_rows(idx, d["obs"].view(M, self.D), d["act"].view(M, A), d["log_prob"].view(M), d["target_value_r"].view(M),
+                              d["target_value_c"].view(M), (self.buffer.adv_mix if adv_all is None else adv_all).view(M),
+                              self.mean_old, self.std_old, kl_bound, pg_coef, actor_only, g, losses_out, pg_grad=pgb, sums=sums)
+        else:
+            self._launch_per_network_grad_split(idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, g, pgb, sums, part2)
+        self.comm.all_reduce_sum_(buf[lo:])
+        _abi.check(lib.spo_wide_kl_penalty_combine(_abi.ptr(g), _abi.ptr(pgb), _abi.ptr(sums), P, lo, off_ls,
+                                                   1.0 / self.comm.world_size, float(pg_coef), _abi.ptr(losses_out[2:]), st()),
+                   "spo_wide_kl_penalty_combine")
+        step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
+        _abi.check(lib.spo_wide_clip_adam_ex(_abi.ptr(self.policy.theta), _abi.ptr(g), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v), P,
+                                             w.off_c, off_ls, off_ls, cfg, step_c, step_a, lo, P, lo, 0,
+                                             None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
+                                             st()), "spo_wide_clip_adam_ex")
+
+    def _launch_per_network_grad_split(self, idx, adv_all, losses_out, kl_bound, pg_coef, actor_only, g, pgb, sums, part2) -> None:
+        """_minibatch_step_ex_split's local gradients outside the row-group kernel: gather, forwards, spo_wide_kl_penalty_split,
+        the actor backpropagated twice."""
+        w, lib, st = self.wide, self.lib, _abi.stream_ptr
+        A, off_ls = self.A, w.off_ls
         obs, act, logp_old, tgt_r, tgt_c, adv, old_mean = self._gather(idx, adv_all, extra=(self.mean_old,))
         n = obs.shape[0]
         nets = "a" if actor_only else "rca"
@@ -1073,16 +1135,6 @@ class WidePPOLagEngine(_WideOps, PPOLagEngine):
             _abi.ptr(pgb[off_ls:]), _abi.ptr(sums), _abi.ptr(part2), part2.numel(), st()), "spo_wide_kl_penalty_split")
         w.backward_multi(nets, obs, wss, d_outs + [d_kl], g)
         w.backward_multi("a", obs, [ws_a], [d_pg], pgb)
-        lo = off_ls if actor_only else 0
-        self.comm.all_reduce_sum_(buf[lo:])
-        _abi.check(lib.spo_wide_kl_penalty_combine(_abi.ptr(g), _abi.ptr(pgb), _abi.ptr(sums), P, lo, off_ls,
-                                                   1.0 / self.comm.world_size, float(pg_coef), _abi.ptr(losses_out[2:]), st()),
-                   "spo_wide_kl_penalty_combine")
-        step_c, step_a = self.adam_step, self.adam_step + self.adam_step_actor_extra
-        _abi.check(lib.spo_wide_clip_adam_ex(_abi.ptr(self.policy.theta), _abi.ptr(g), _abi.ptr(self.adam_m), _abi.ptr(self.adam_v), P,
-                                             w.off_c, off_ls, off_ls, cfg, step_c, step_a, lo, P, lo, 0,
-                                             None if actor_only else _abi.ptr(losses_out), _abi.ptr(self.scal4), _abi.ptr(part), cap,
-                                             st()), "spo_wide_clip_adam_ex")
 
     def learning_iter_ex(self, perm: torch.Tensor, adv: torch.Tensor, actor_loss: int = 0,
                          kl_bound: float = float("inf"), pg_coef: float = 0.0, actor_only: bool = False) -> torch.Tensor:

@@ -169,6 +169,41 @@ class WideNets:
                                                       _abi.ptr(losses_out), _abi.stream_ptr()), "spo_wide_reduce_parts")
         return parts
 
+    def klpen_rows_ok(self, rows) -> bool:
+        """csrc/mlp_rows.hip holds the KL-penalty loss of FOCOPS / CUP at this shape: rows_grad_ok and room in LDS for the rows'
+        old distribution (SPO_WIDE_ROWS=0: never)."""
+        return bool(self.lib.spo_wide_kl_penalty_grad_rows_supported(self.net_c, self.net_a, int(rows)))
+
+    def klpen_grad_rows(self, idx, obs, act, logp_old, tgt_r, tgt_c, adv, old_mean, old_std, kl_bound, pg_coef, actor_only, grad_flat,
+                        losses_out, pg_grad=None, sums=None):
+        """focops.py:326-347 / cup.py:370-386 on the rows `idx` (as grad_rows: device indices or a PermWindow) of the full
+        [M, .] arrays: spo_wide_kl_penalty_grad_rows (the critics' workgroups and two kinds of actor workgroup per 16 rows, one
+        launch) + spo_wide_kl_penalty_reduce_parts.  pg_grad / sums None (one GPU): grad_flat's actor block = g_KL + F g_PG with the
+        minibatch's own F and losses_out[2] its actor loss.  Given (data-parallel; pg_grad indexed like grad_flat): g_KL, g_PG and
+        the row sums apart, for the all-reduce and spo_wide_kl_penalty_combine.  losses_out[0..1]: the critics' data losses (not
+        with actor_only)."""
+        win = idx if isinstance(idx, PermWindow) else None
+        n = idx.numel()
+        key = ("klpen_parts", n, bool(actor_only))
+        parts = self._scratch.get(key)
+        if parts is None:
+            parts = torch.zeros(int(self.lib.spo_wide_kl_penalty_rows_part_floats(self.P, self.off_ls, n)), dtype=torch.float32,
+                                device=self.policy.theta.device)
+            self._scratch[key] = parts
+        _abi.check(self.lib.spo_wide_kl_penalty_grad_rows(
+            _abi.ptr(self.policy.theta), self.net_c, self.net_a, _abi.ptr(obs), _abi.ptr(act), _abi.ptr(logp_old),
+            None if actor_only else _abi.ptr(tgt_r), None if actor_only else _abi.ptr(tgt_c), _abi.ptr(adv), _abi.ptr(old_mean),
+            _abi.ptr(old_std), _abi.ptr(win.perm if win else idx), _abi.ptr(win.cursor) if win else None, n, float(kl_bound),
+            float(pg_coef), int(actor_only), _abi.ptr(parts), _abi.stream_ptr()), "spo_wide_kl_penalty_grad_rows")
+        combine = pg_grad is None
+        if combine:                                  # (scratch behind the row groups' parts)
+            tail = parts[parts.numel() - (self.P + 3) // 4 * 4 - _abi.KLPEN_SUMS - 4:]
+            pg_grad, sums = tail, tail[(self.P + 3) // 4 * 4:]
+        _abi.check(self.lib.spo_wide_kl_penalty_reduce_parts(
+            _abi.ptr(parts), n, self.P, self.off_ls, int(actor_only), int(combine), float(pg_coef), _abi.ptr(grad_flat), _abi.ptr(pg_grad),
+            _abi.ptr(sums), _abi.ptr(losses_out), _abi.stream_ptr()), "spo_wide_kl_penalty_reduce_parts")
+        return parts
+
     def gather_rows(self, idx, srcs):
         """[src[idx] for src in srcs] (row-major float32 arrays, int64 device indices) in one launch (spo_gather_rows).  `idx` may
         be a PermWindow: the rows perm[cursor : cursor + n] with the cursor on the device (a replayed minibatch step)."""

@@ -4,7 +4,9 @@
 kernel (spo_update_iter_ex); the multiplier is bounded by CUP_NU.  Data-parallel (torchrun): stage one as a clipped-surrogate
 gradient (spo_ppo_lag_grad) + all-reduce + spo_clip_adam_ex with the two optimiser clocks, stage two as the split KL-penalty
 gradient (spo_kl_penalty_grad, F = 1) + all-reduce + spo_clip_adam_ex over the actor alone (PPOLagEngine._learning_iter_ex_split;
-the wide-network kernels' form: WidePPOLagEngine._minibatch_step_ex_split).
+the wide-network kernels' form: WidePPOLagEngine._minibatch_step_ex_split).  hidden_sizes other than [64, 64]: both stages on the
+row-group gradient kernel (csrc/mlp_rows.hip) -- stage one spo_wide_ppo_grad_rows with adv_r, stage two the actor-only form of
+spo_wide_kl_penalty_grad_rows (F = 1) --, one GPU and data-parallel (WidePPOLagEngine._row_group_step_ok).
 """
 from __future__ import annotations
 
