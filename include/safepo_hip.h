@@ -273,6 +273,27 @@ int spo_cpo_linesearch_eval(const float* theta, const float* obs, const float* a
                             const float* adv_r, const float* adv_c, const float* mean_old, const float* log_std_old,
                             int64_t rows, int obs_dim, int act_dim, double* partial_ws, int partial_capacity,
                             double* sums3_out, void* stream);
+
+/* ---- CPO full-batch primitives for obs_dim 65..128 (the Car / Racecar / Doggo / Ant tasks of
+ * single_agent/benchmark.py:5-44), hidden [64, 64], act_dim <= 16.  Same argument meaning, layouts and workspaces as
+ * their namesakes above; obs_dim / act_dim outside that range fail with -2.
+ *   spo_cpo128_supported        1 exactly for 65 <= obs_dim <= 128 and 1 <= act_dim <= 16 (host code, no GPU needed)
+ *   spo_cpo128_num_partials     workgroups = partial vectors for `rows` rows (sizes partial_ws / loss_ws)
+ *   spo_cpo128_surrogate_grad   cpo.py:356-365, :372-381
+ *   spo_cpo128_fvp              cpo.py:132-157 (one launch + the fixed-order reduction, like spo_cpo_fvp)
+ *   spo_cpo128_linesearch_eval  cpo.py:473-491 */
+int spo_cpo128_supported(int obs_dim, int act_dim);
+int spo_cpo128_num_partials(int64_t rows);
+int spo_cpo128_surrogate_grad(const float* theta, const float* obs, const float* act, const float* logp_old,
+                              const float* adv, float sign, int64_t rows, int obs_dim, int act_dim,
+                              float* partial_ws, double* loss_ws, float* grad_out, double* loss_sum_out, void* stream);
+int spo_cpo128_fvp(const float* theta, const float* obs, const float* vec, int64_t rows, int obs_dim, int act_dim,
+                   float* partial_ws, double* loss_ws, float* out, void* stream);
+int spo_cpo128_linesearch_eval(const float* theta, const float* obs, const float* act, const float* logp_old,
+                               const float* adv_r, const float* adv_c, const float* mean_old, const float* log_std_old,
+                               int64_t rows, int obs_dim, int act_dim, double* partial_ws, int partial_capacity,
+                               double* sums3_out, void* stream);
+
 int spo_critic_fit_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                         const float* obs, const float* target_r, const float* target_c, const int32_t* perm,
                         int64_t M, const spo_ppo_cfg* cfg_host, float* stale_sq_io, float* losses_out,

@@ -17,6 +17,18 @@
 //              For a diagonal Gaussian with state-independent log_std the Hessian of the mean KL at
 //              cur == old is block diagonal: J^T diag(1/sigma^2) J / (M*A) on the mean network and
 //              2/A on log_std (added on the host together with the 0.1 damping).
+//
+// obs_dim 65..128 (KIN = 128; the spo_cpo128_* entry points): the surrogate form and the line search are instantiations of
+// the same kernels (147 776 B and 56 128 B of LDS).  MODE_FVP's second network image does not fit beside the five
+// transposed buffers (203 904 B of 163 840), so the product has a layout of its own:
+//   MODE_FVP_REUSE: both images + THREE buffers P (64 x 68), Q (64 x 68), R (16 x 68) = 151 680 B, reused by four sub-phases
+//              1  P = H1^T, Q = dZ2^T, R = dO^T          -> dW2, db2
+//              2  P = H2^T, Q = dZ1^T                    -> dW3, db3; this wave's dZ1^T rows go to registers, db1
+//              3  P = X^T features 0..63                 -> dW1 columns 0..63
+//              4  P = X^T features 64..127               -> dW1 columns 64..127
+//   with x kept in registers until sub-phases 3 / 4.  Eight barriers per chunk instead of four, one forward pass, no global
+//   round trip; every accumulator receives the same products in the same order as in MODE_FVP (bit-identical to the two-launch
+//   form that was measured against it: DESIGN_NOTES.md).
 #include "common.h"
 #include "mlp_mfma.h"
 #include "../../include/safepo_hip.h"
@@ -25,16 +37,17 @@ namespace {
 using namespace spo;
 
 constexpr int LDB = 64 + 4;
-enum { MODE_SURR = 0, MODE_FVP = 1 };
+enum { MODE_SURR = 0, MODE_FVP = 1, MODE_FVP_REUSE = 2 };
 
 template <int KIN, int MODE>
 struct CpoLds {
   using L = NetLds<KIN>;
   static constexpr int W = 0;
   static constexpr int V = L::SIZE;                               // FVP only
-  static constexpr int XT = (MODE == MODE_FVP ? 2 : 1) * L::SIZE;
-  static constexpr int H1T = XT + KIN * LDB;
-  static constexpr int H2T = H1T + HID * LDB;
+  static constexpr bool REUSE = MODE == MODE_FVP_REUSE;           // P = XT = H1T = H2T, Q = DZT, R = DOT
+  static constexpr int XT = (MODE == MODE_SURR ? 1 : 2) * L::SIZE;
+  static constexpr int H1T = REUSE ? XT : XT + KIN * LDB;
+  static constexpr int H2T = REUSE ? XT : H1T + HID * LDB;
   static constexpr int DZT = H2T + HID * LDB;                     // dZ2^T, then dZ1^T (two sub-phases)
   static constexpr int DOT = DZT + HID * LDB;
   static constexpr int RED = DOT + OUTP * LDB;
@@ -62,7 +75,7 @@ __global__ __launch_bounds__(256, 1) void cpo_actor_kernel(CpoArgs a) {
   const int ls_off = g.off - A;
   const int Pa = actor_size(D, A);
   stage_net<KIN>(a.theta, g, lds + U::W, tid, 256);
-  if (MODE == MODE_FVP) {
+  if (MODE != MODE_SURR) {
     // the direction vector uses the actor's own flat layout: shift it so that net_geom offsets apply
     NetGeom gv = g;
     gv.off = A;                                   // W1 of the direction sits after its log_std block
@@ -104,10 +117,12 @@ __global__ __launch_bounds__(256, 1) void cpo_actor_kernel(CpoArgs a) {
     const int64_t smp = cv ? row : a.M - 1;
     f4 x[NT1];
     load_obs_tiles<KIN>(a.obs + smp * D, D, q, x);
+    if (MODE != MODE_FVP_REUSE) {
 #pragma unroll
-    for (int nt = 0; nt < NT1; ++nt)
+      for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) lds[U::XT + (16 * nt + 4 * q + e) * LDB + mycol] = x[nt][e];
+        for (int e = 0; e < 4; ++e) lds[U::XT + (16 * nt + 4 * q + e) * LDB + mycol] = x[nt][e];
+    }
     f4 h1[4], h2[4];
     const f4 o = net_forward<KIN>(Wl, x, h1, h2, j, q);
     f4 dO = {0.f, 0.f, 0.f, 0.f};
@@ -134,8 +149,13 @@ __global__ __launch_bounds__(256, 1) void cpo_actor_kernel(CpoArgs a) {
       }
     } else {
       // tangent (forward-mode) pass: t1 = V1 x + vb1 ; h1' = (1-h1^2) t1 ; t2 = W2 h1' + V2 h1 + vb2 ; ...
+      // KIN = 128: scheduling fences between the layers keep each layer's operand reads out of the previous layer's register
+      // budget (119 instead of 155 AGPRs used as spill space); the narrower forms are scheduled as before
+      constexpr bool FENCE = KIN > 64;
       f4 t1[4], t2[4];
+      if (FENCE) __builtin_amdgcn_sched_barrier(0);
       layer_hidden<NT1, false>(Vl + L::W1, L::LD1, Vl + L::B1, x, t1, j, q);
+      if (FENCE) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -143,7 +163,9 @@ __global__ __launch_bounds__(256, 1) void cpo_actor_kernel(CpoArgs a) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) t2[mt] = *reinterpret_cast<const f4*>(Vl + L::B2 + 16 * mt + 4 * q);
       layer_accum<4>(Wl + L::W2, LDH, t1, t2, j, q);
+      if (FENCE) __builtin_amdgcn_sched_barrier(0);
       layer_accum<4>(Vl + L::W2, LDH, h1, t2, j, q);
+      if (FENCE) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -186,6 +208,96 @@ __global__ __launch_bounds__(256, 1) void cpo_actor_kernel(CpoArgs a) {
         for (int r = 0; r < 4; ++r) dz1[mt][r] = acc[mt][r] * fmaf(-h1[mt][r], h1[mt][r], 1.f);
     }
 
+    if (MODE == MODE_FVP_REUSE) {
+      constexpr int P = U::XT, Q = U::DZT, R = U::DOT;
+      // 1: P = H1^T, Q = dZ2^T, R = dO^T  ->  dW2
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int f = (16 * mt + 4 * q + r) * LDB + mycol;
+          lds[P + f] = h1[mt][r];
+          lds[Q + f] = dz2[mt][r];
+        }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lds[R + (4 * q + r) * LDB + mycol] = dO[r];
+      __syncthreads();
+      {
+        f4 az[4];
+        float rs = 0.f;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          az[r4] = *reinterpret_cast<const f4*>(lds + Q + (16 * wave + j) * LDB + 16 * r4 + 4 * q);
+          rs += (az[r4][0] + az[r4][1]) + (az[r4][2] + az[r4][3]);
+        }
+        db2 += rs;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          f4 bh[4];
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt)
+            bh[nt] = *reinterpret_cast<const f4*>(lds + P + (16 * nt + j) * LDB + 16 * r4 + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) aW2[nt] = mfma4(az[r4][e], bh[nt][e], aW2[nt]);
+        }
+      }
+      __syncthreads();
+      // 2: P = H2^T, Q = dZ1^T  ->  dW3; dZ1^T rows of this wave go to registers
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int f = (16 * mt + 4 * q + r) * LDB + mycol;
+          lds[P + f] = h2[mt][r];
+          lds[Q + f] = dz1[mt][r];
+        }
+      __syncthreads();
+      f4 az1[4];
+      {
+        float rs = 0.f;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const f4 az = *reinterpret_cast<const f4*>(lds + R + j * LDB + 16 * r4 + 4 * q);
+          rs += (az[0] + az[1]) + (az[2] + az[3]);
+          const f4 bh = *reinterpret_cast<const f4*>(lds + P + (16 * wave + j) * LDB + 16 * r4 + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) aW3 = mfma4(az[e], bh[e], aW3);
+        }
+        db3 += rs;
+        rs = 0.f;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          az1[r4] = *reinterpret_cast<const f4*>(lds + Q + (16 * wave + j) * LDB + 16 * r4 + 4 * q);
+          rs += (az1[r4][0] + az1[r4][1]) + (az1[r4][2] + az1[r4][3]);
+        }
+        db1 += rs;
+      }
+      // 3, 4: P = X^T features 0..63, then 64..127  ->  dW1 halves
+#pragma unroll
+      for (int half = 0; half < NT1 / 4; ++half) {
+        __syncthreads();
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) lds[P + (16 * nt + 4 * q + e) * LDB + mycol] = x[4 * half + nt][e];
+        __syncthreads();
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          f4 bh[4];
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt)
+            bh[nt] = *reinterpret_cast<const f4*>(lds + P + (16 * nt + j) * LDB + 16 * r4 + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) aW1[4 * half + nt] = mfma4(az1[r4][e], bh[nt][e], aW1[4 * half + nt]);
+        }
+      }
+      __syncthreads();
+      continue;
+    }
     // ---- sub-phase A: dW3 (dO^T, H2^T) and dW2 (dZ2^T, H1^T)
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -416,13 +528,26 @@ int launch_cpo(const CpoArgs& a, int blocks, hipStream_t st) {
     hipLaunchKernelGGL((cpo_actor_kernel<K, MODE>), dim3(blocks), dim3(256), sh, st, a);               \
   }
   if (kin == 16) SPO_LAUNCH(16) else if (kin == 32) SPO_LAUNCH(32) else SPO_LAUNCH(64)
-#undef SPO_LAUNCH
   return 0;
 }
+
+template <int MODE>
+int launch_cpo128(const CpoArgs& a, int blocks, hipStream_t st) {
+  static_assert(CpoLds<128, MODE>::SIZE * sizeof(float) <= 160 * 1024, "cpo128: LDS form does not fit one workgroup");
+  SPO_LAUNCH(128)
+  return 0;
+}
+#undef SPO_LAUNCH
 
 int check(int D, int A) {
   if (D < 1 || D > 64) return spo::fail(-2, "cpo: obs_dim %d outside [1,64]", D);
   if (A < 1 || A > SPO_MAX_ACT) return spo::fail(-2, "cpo: act_dim %d outside [1,16]", A);
+  return 0;
+}
+
+int check128(int D, int A) {
+  if (D < 65 || D > 128) return spo::fail(-2, "cpo128: obs_dim %d outside [65,128]", D);
+  if (A < 1 || A > SPO_MAX_ACT) return spo::fail(-2, "cpo128: act_dim %d outside [1,16]", A);
   return 0;
 }
 
@@ -486,5 +611,63 @@ extern "C" int spo_cpo_linesearch_eval(const float* theta, const float* obs, con
   }
   hipLaunchKernelGGL(sum3_kernel, dim3(1), dim3(64), 0, st, partial_ws, (int)blocks, sums3_out);
   SPO_LAUNCH_CHECK("spo_cpo_linesearch_eval");
+  return 0;
+}
+
+// ---- obs_dim 65..128: the same three primitives on the KIN = 128 forms (see the head of this file)
+extern "C" int spo_cpo128_supported(int obs_dim, int act_dim) {
+  return (obs_dim >= 65 && obs_dim <= 128 && act_dim >= 1 && act_dim <= SPO_MAX_ACT) ? 1 : 0;
+}
+
+extern "C" int spo_cpo128_num_partials(int64_t rows) { return spo_cpo_num_partials(rows); }
+
+extern "C" int spo_cpo128_surrogate_grad(const float* theta, const float* obs, const float* act, const float* logp_old,
+                                         const float* adv, float sign, int64_t rows, int obs_dim, int act_dim,
+                                         float* partial_ws, double* loss_ws, float* grad_out, double* loss_sum_out,
+                                         void* stream) {
+  if (int rc = check128(obs_dim, act_dim)) return rc;
+  SPO_REQUIRE(theta && obs && act && logp_old && adv && partial_ws && loss_ws && grad_out && loss_sum_out && rows > 0,
+              "cpo128_surrogate_grad: bad args");
+  const int blocks = spo_cpo128_num_partials(rows);
+  CpoArgs a{theta, nullptr, obs, act, logp_old, adv, rows, obs_dim, act_dim, sign, partial_ws, loss_ws};
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch_cpo128<MODE_SURR>(a, blocks, st)) return rc;
+  const int Pa = spo::actor_size(obs_dim, act_dim);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((Pa + 63) / 64), dim3(64), 0, st, partial_ws, blocks, Pa, grad_out,
+                     loss_ws, loss_sum_out);
+  SPO_LAUNCH_CHECK("spo_cpo128_surrogate_grad");
+  return 0;
+}
+
+extern "C" int spo_cpo128_fvp(const float* theta, const float* obs, const float* vec, int64_t rows, int obs_dim,
+                              int act_dim, float* partial_ws, double* loss_ws, float* out, void* stream) {
+  if (int rc = check128(obs_dim, act_dim)) return rc;
+  SPO_REQUIRE(theta && obs && vec && partial_ws && loss_ws && out && rows > 0, "cpo128_fvp: bad args");
+  const int blocks = spo_cpo128_num_partials(rows);
+  CpoArgs a{theta, vec, obs, nullptr, nullptr, nullptr, rows, obs_dim, act_dim, 1.f, partial_ws, loss_ws};
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = launch_cpo128<MODE_FVP_REUSE>(a, blocks, st)) return rc;
+  const int Pa = spo::actor_size(obs_dim, act_dim);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((Pa + 63) / 64), dim3(64), 0, st, partial_ws, blocks, Pa, out,
+                     loss_ws, (double*)nullptr);
+  SPO_LAUNCH_CHECK("spo_cpo128_fvp");
+  return 0;
+}
+extern "C" int spo_cpo128_linesearch_eval(const float* theta, const float* obs, const float* act, const float* logp_old,
+                                          const float* adv_r, const float* adv_c, const float* mean_old,
+                                          const float* log_std_old, int64_t rows, int obs_dim, int act_dim,
+                                          double* partial_ws, int partial_capacity, double* sums3_out, void* stream) {
+  if (int rc = check128(obs_dim, act_dim)) return rc;
+  SPO_REQUIRE(theta && obs && act && logp_old && adv_r && adv_c && mean_old && log_std_old && partial_ws && sums3_out &&
+                  rows > 0, "cpo128_linesearch_eval: bad args");
+  int64_t blocks = (rows + 63) / 64;
+  if (blocks > 1024) blocks = 1024;
+  if (blocks * 3 > partial_capacity) blocks = partial_capacity / 3;
+  SPO_REQUIRE(blocks >= 1, "cpo128_linesearch_eval: partial capacity too small");
+  LsArgs a{theta, obs, act, logp_old, adv_r, adv_c, mean_old, log_std_old, partial_ws, rows, obs_dim, act_dim};
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((cpo_linesearch_kernel<128>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(sum3_kernel, dim3(1), dim3(64), 0, st, partial_ws, (int)blocks, sums3_out);
+  SPO_LAUNCH_CHECK("spo_cpo128_linesearch_eval");
   return 0;
 }
