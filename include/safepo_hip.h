@@ -210,9 +210,23 @@ int spo_update_scratch_release(void* stream_or_null, int all);
  * (the main + helper form) or 0 (the four-wave form) is set in the environment.  Same arguments, same results to rounding. */
 int spo_update_rs_supported(int obs_dim, int act_dim, int batch, int n_nets);
 
+/* The row-split form for observations of 65 .. 128 values (a KIN = 128 instantiation of the same kernel: the Car / Racecar / Doggo /
+ * Ant navigation tasks).  Layer 1's optimiser state does not fit a 256-register wave the way it is held up to 64 inputs, so the
+ * x^T operands of its weight gradient pass through the registers in two halves, its parameters stay in LDS until they are used, and
+ * its Adam step runs behind the joint norm with the clip coefficient in hand (no speculation, no backups, no redo).  Returns 1
+ * exactly for 65 <= obs_dim <= 128, 1 <= act_dim <= 16, 1 <= batch <= 64 and n_nets == 3: spo_ppo_lag_update_iter then runs on it
+ * unless SPO_RS_OBS128=0 (read at every launch: the four-wave kernel, as before) or SPO_UPDATE_FORM < 3 is set.  n_nets == 2 (the
+ * critic fit, four row groups) returns 0: that instantiation was measured slower than the forms it would replace and is not built.
+ * A separate question from spo_update_rs_supported, which stays 0 above 64: it also keys the data-parallel routing, and the
+ * data-parallel row-split form has no KIN = 128 instantiation.  In spo_debug_update_counters the form's steps count as row-split
+ * steps; nothing is redone in it, the second counter counts its steps whose joint clip was active. */
+int spo_update_rs128_supported(int obs_dim, int act_dim, int batch, int n_nets);
+
 /* Measurement aid: counters of the main + helper update kernel summed over the launches of this process since the last reset
  * (out4_host, host array): {minibatch steps run, steps whose speculative update turned out clipped and was redone, steps
- * clipped under the conservative protocol, steps run under the conservative protocol}.  Synchronises the device. */
+ * clipped under the conservative protocol, steps run under the conservative protocol}.  The row-split kernel adds its steps to
+ * the first two; its KIN = 128 form (spo_update_rs128_supported) does not speculate, so nothing is redone there and it adds its
+ * steps whose joint clip was active to the second -- the steps a speculating form would have redone.  Synchronises the device. */
 int spo_debug_update_counters(unsigned long long* out4_host, int reset);
 
 /* Debug self-test of the cross-lane helpers (DPP row sums, gfx950 permlane swaps): in[64] -> out[192]. */

@@ -3031,10 +3031,20 @@ namespace {
 using namespace spo;
 // SPO_UPDATE_FORM: 0 = four-wave kernel everywhere, 2 = main + helper waves where that form applies (persistent PPO step,
 // clipped-surrogate loss, no in-kernel cross-rank exchange, batch <= 64, obs <= 64), 3 (default, round 6) = the row-split kernel
-// (update_rs.hip) for the one-GPU PPO-Lagrangian step and the critic fit where spo_update_rs_supported, form 2 elsewhere.
+// (update_rs.hip) for the one-GPU PPO-Lagrangian step and the critic fit where spo_update_rs_supported or
+// spo_update_rs128_supported (rs_takes below), form 2 elsewhere up to 64 observations, the four-wave kernel above.
 inline int update_form() {
   static const int v = [] { const char* e = getenv("SPO_UPDATE_FORM"); return e ? atoi(e) : 3; }();
   return v;
+}
+// Does the row-split kernel take this one-GPU launch?  Where spo_update_rs128_supported (observations of 65 .. 128 values, the
+// PPO-Lagrangian step) it runs on the KIN = 128 form unless SPO_RS_OBS128=0 (read at every launch) restores the four-wave kernel.
+inline bool rs_takes(const spo_ppo_cfg* c, int n_nets) {
+  if (update_form() < 3) return false;
+  if (spo_update_rs_supported(c->obs_dim, c->act_dim, c->batch, n_nets)) return true;
+  if (!spo_update_rs128_supported(c->obs_dim, c->act_dim, c->batch, n_nets)) return false;
+  const char* e = getenv("SPO_RS_OBS128");
+  return !(e && *e == '0');
 }
 
 // SPO_P2P_HELPER=1 (opt-in): the data-parallel step with its exchange on the HELPER waves of the main + helper kernel (packed words)
@@ -3124,7 +3134,7 @@ extern "C" int spo_ppo_lag_update_iter(float* theta, float* adam_m, float* adam_
   SPO_REQUIRE(M > 0 && adam_step_host >= 0, "update_iter: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  if (update_form() >= 3 && spo_update_rs_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, 3)) {
+  if (rs_takes(cfg_host, 3)) {
     if (int rc = spo::rs_update_launch(theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
                                        cfg_host, 3, nullptr, losses_out, sync_ws, g_prof_buf, stream)) return rc;
     SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter (row-split)");
@@ -3156,7 +3166,7 @@ extern "C" int spo_critic_fit_iter(float* theta, float* adam_m, float* adam_v, i
   SPO_REQUIRE(M > 0 && adam_step_host >= 0, "critic_fit_iter: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  if (update_form() >= 3 && spo_update_rs_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, 2)) {
+  if (rs_takes(cfg_host, 2)) {
     if (int rc = spo::rs_update_launch(theta, adam_m, adam_v, adam_step_host, obs, nullptr, nullptr, target_r, target_c, nullptr,
                                        perm, M, cfg_host, 2, stale_sq_io, losses_out, sync_ws, nullptr, stream)) return rc;
     SPO_LAUNCH_CHECK("spo_critic_fit_iter (row-split)");

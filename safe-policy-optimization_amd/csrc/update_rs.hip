@@ -45,7 +45,7 @@ using namespace spo;
 #ifndef SPO_RS_XR_TWO_PHASE_MIN
 #define SPO_RS_XR_TWO_PHASE_MIN 4     // data-parallel form: all-to-all of every word below this world size, reduce-scatter + all-gather from it on (A/B knob)
 #endif
-constexpr int RS_NS = 16;                        // exchange slots (16-byte groups per lane) per (destination, source): NT1 + 8 <= 12 used
+constexpr int RS_NS = 16;                        // exchange slots (16-byte groups per lane) per (destination, source): NT1 + 8 used (12 at KIN = 64, all 16 at KIN = 128)
 constexpr int RS_MAX_R = 4;
 constexpr unsigned RS_SPIN_LIMIT = 1u << 22;
 constexpr int RS_NPHASE = 12;
@@ -98,7 +98,8 @@ constexpr size_t rs_z_bytes(int R) { return (size_t)2 * 3 * R * R * RS_NS * 4096
 constexpr int RS_GRAN_WORDS = 2 * RS_MAX_R * 3 * 4;
 constexpr int RS_CENSUS_WORDS = 3 * RS_MAX_R;
 
-// minibatch steps run / steps whose speculative layer-1 update turned out clipped and was redone, summed over the launches of the
+// minibatch steps run / steps whose speculative layer-1 update turned out clipped and was redone (KIN = 128, where layer 1's Adam
+// waits for the joint norm and nothing is redone: steps whose clip was active -- the same steps), summed over the launches of the
 // process (first optimiser lane of workgroup 0); read through spo_debug_update_counters
 __device__ unsigned long long g_rs_counters[2];
 
@@ -202,7 +203,15 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
   using S = RsLds<KIN, NCT>;
   constexpr int LDC = S::LDC;
   constexpr int NT1 = KIN / 16;
+  // KIN = 128: layer 1's optimiser state does not fit a 256-register wave the way it is held up to 64 (6 x NT1 f4 of moments,
+  // parameters and their backups, 2 x NT1 of x^T operands) -- the x^T operands of dW1 pass through the registers in two halves,
+  // the parameters stay in LDS until they are used, and layer 1's Adam runs BEHIND the joint norm with the clip coefficient in
+  // hand: no speculation, so no backups, no redo and no repeated L1 (the norm poll is back on the critical path: +0.2 - 0.4 us measured)
+  constexpr bool WIDE = KIN > 64;
+  constexpr int NTX = WIDE ? NT1 / 2 : NT1;       // x^T tiles of dW1 in registers at a time
+  constexpr bool SPEC1 = !WIDE;                   // layer 1's Adam runs ahead of the joint norm
   constexpr int NOWN = NCT, NPART = 4 / NCT;      // output tiles per column wave, waves per column tile
+  static_assert(NT1 + 8 <= RS_NS, "layer 1's NT1 + 1 groups and layers 2 / 3's 7 share the RS_NS slots of a (destination, source) pair");
   unsigned long long pacc[RS_NPHASE] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tprev = 0;
 #define RS_STAMP(i)                                            \
@@ -888,7 +897,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     }
     // ---- the optimiser waits for the last image here anyway (the column waves' last backward product is longer than dW2 / dW3):
     // the x^T operands of dW1 (complete since b1), this lane's W1 / b1 parameters (L2 term, backup), the optimiser scalars of the step
-    f4 bx[NCT][NT1], pW1[NT1];
+    f4 bx[NCT][NTX], pW1[WIDE ? 1 : NT1];
     float pb1;
     {
       RS_REIDX
@@ -896,12 +905,14 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
 #pragma unroll
       for (int r4 = 0; r4 < NCT; ++r4)
 #pragma unroll
-        for (int nt = 0; nt < NT1; ++nt)
+        for (int nt = 0; nt < NTX; ++nt)
           bx[r4][nt] = *reinterpret_cast<const f4*>(xt + (16 * nt + j) * LDC + 16 * r4 + 4 * q);
+      if constexpr (!WIDE) {
 #pragma unroll
-      for (int nt = 0; nt < NT1; ++nt)
+        for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pW1[nt][r] = lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j];
+          for (int r = 0; r < 4; ++r) pW1[nt][r] = lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j];
+      }
       pb1 = lds[L::B1 + 16 * ow + j];
     }
     pw1 *= (double)b1c; pw2 *= (double)b2c;
@@ -912,7 +923,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     RS_STAMP(3)
     // the first peer's layer-2 / 3 partials (sent at b4: long there): their round trip runs under the dW1 products
     u4 zwA[1][7];
-    if constexpr (R == 2) RS_LOADS(zwA, 7, NT1 + 1, par, 1, 2)            // (R = 4: 28 more live registers across dW1 spill the wave)
+    if constexpr (R == 2 && !WIDE) RS_LOADS(zwA, 7, NT1 + 1, par, 1, 2)   // (R = 4 and KIN = 128: 28 more live registers across dW1 spill the wave)
     {
       // ---- dW1, db1
       RS_REIDX
@@ -927,7 +938,21 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int nt = 0; nt < NT1; ++nt) gB[nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[nt]);
+          for (int nt = 0; nt < NTX; ++nt) gB[nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[nt]);
+      if constexpr (WIDE) {                                                 // the second half of the tiles through the same registers
+        const float* const xt = lds + S::XT + par * KIN * LDC;
+#pragma unroll
+        for (int r4 = 0; r4 < NCT; ++r4)
+#pragma unroll
+          for (int nt = 0; nt < NTX; ++nt)
+            bx[r4][nt] = *reinterpret_cast<const f4*>(xt + (16 * (NTX + nt) + j) * LDC + 16 * r4 + 4 * q);
+#pragma unroll
+        for (int r4 = 0; r4 < NCT; ++r4)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nt = 0; nt < NTX; ++nt) gB[NTX + nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[NTX + nt]);
+      }
       float rs1 = 0.f;
 #pragma unroll
       for (int r4 = 0; r4 < NCT; ++r4) rs1 += (az1[r4][0] + az1[r4][1]) + (az1[r4][2] + az1[r4][3]);
@@ -937,7 +962,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     RS_STAMP(4)                                                            // dW1, stores
     // ---- while layer 1's partials travel: the peers' layer-2 / 3 partials (sent at b4: long there), their L2 terms and norm share
     // (before b5 this work would come straight out of the column waves' last backward product: the two waves of a SIMD add)
-    RS_POLL_SUM(gA, zwA, 7, NT1 + 1, par, 10, (R == 2))
+    RS_POLL_SUM(gA, zwA, 7, NT1 + 1, par, 10, (R == 2 && !WIDE))
     const unsigned gtag = gtag0 + (unsigned)s;                             // (data-parallel form: the global step's tag)
     constexpr int NFA = 26, NFB = 4 * NT1 + 1;                             // floats that cross ranks: layers 2 / 3 (+ db2, db3, d log_std), layer 1 (+ db1)
     float fA[NFA];
@@ -1042,9 +1067,10 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
       gB[NT1][0] = fB[4 * NT1];
     }
     // ---- layer 1: L2 term, norm share out, then Adam at once with clip coefficient 1 -- max_grad_norm almost never binds, and the
-    // next forward waits for nothing else.  Backups in registers; the joint norm is checked behind b1 (below).
-    f4 bmW1[NT1], bvW1[NT1];
-    float bmb1, bvb1;
+    // next forward waits for nothing else.  Backups in registers; the joint norm is checked behind b1 (below).  (KIN = 128: the
+    // norm share goes out here, Adam follows behind the coefficient.)
+    f4 bmW1[WIDE ? 1 : NT1], bvW1[WIDE ? 1 : NT1];                          // (KIN = 128: placeholders, like pW1 -- never touched)
+    float bmb1 = 0.f, bvb1 = 0.f;
     unsigned long long gv0 = 0;
     {
       RS_REIDX
@@ -1053,7 +1079,9 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
         for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {                                     // pad columns hold p == 0, g == 0
-            const float p_ = pW1[nt][r];
+            float p_;
+            if constexpr (WIDE) p_ = lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j];
+            else p_ = pW1[nt][r];
             const float g_ = vcoef * fmaf(l2x2, p_, gB[nt][r]);
             gB[nt][r] = g_; gsq = fmaf(g_, g_, gsq); psq = fmaf(p_, p_, psq);
           }
@@ -1079,21 +1107,23 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
         const unsigned own_bits = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(wg_sq), 63);
         if (lane == 4 * netl + ow) gv0 = ((unsigned long long)tag << 32) | own_bits;
       }
+      if constexpr (SPEC1) {
 #pragma unroll
-      for (int nt = 0; nt < NT1; ++nt) {
-        bmW1[nt] = mW1[nt]; bvW1[nt] = vW1[nt];
+        for (int nt = 0; nt < NT1; ++nt) {
+          bmW1[nt] = mW1[nt]; bvW1[nt] = vW1[nt];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const AdamOut o_ = adam1(pW1[nt][r], gB[nt][r], mW1[nt][r], vW1[nt][r], b1c, b2c, eps, step_size, inv_bc2s);
-          mW1[nt][r] = o_.m; vW1[nt][r] = o_.v; lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j] = o_.p;
+          for (int r = 0; r < 4; ++r) {
+            const AdamOut o_ = adam1(pW1[nt][r], gB[nt][r], mW1[nt][r], vW1[nt][r], b1c, b2c, eps, step_size, inv_bc2s);
+            mW1[nt][r] = o_.m; vW1[nt][r] = o_.v; lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j] = o_.p;
+          }
         }
+        bmb1 = mb1; bvb1 = vb1;
+        const AdamOut o_ = adam1(pb1, gb1, mb1, vb1, b1c, b2c, eps, step_size, inv_bc2s);
+        mb1 = o_.m; vb1 = o_.v; lds[L::B1 + 16 * ow + j] = o_.p;
       }
-      bmb1 = mb1; bvb1 = vb1;
-      const AdamOut o_ = adam1(pb1, gb1, mb1, vb1, b1c, b2c, eps, step_size, inv_bc2s);
-      mb1 = o_.m; vb1 = o_.v; lds[L::B1 + 16 * ow + j] = o_.p;
     }
     RS_STAMP(6)                                                            // L2 term, norm share out, Adam W1 (coefficient 1)
-    if (s + 1 < nsteps) __syncthreads();                                  // b1 of step s + 1
+    if constexpr (SPEC1) { if (s + 1 < nsteps) __syncthreads(); }         // b1 of step s + 1
     // ---- joint clip_grad_norm_ over all networks (ppo_lag.py:325): the granules of the workgroups with my row-group index
     float coef;
     {
@@ -1129,24 +1159,42 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
       stale_sq *= coef * coef;
     }
     RS_STAMP(7)                                                            // wait b1, poll norms, coefficient
-    if (coef != 1.f) {
-      // ---- clipped after all (rare): layer 1 restored and redone exactly.  The column waves are inside L1 of the next step on the
-      // speculative weights; the flag makes them repeat it behind b2 -- by then this redo is complete, no extra barrier.
+    if constexpr (!SPEC1) {
+      // ---- KIN = 128: layer 1's Adam with the coefficient in hand, then b1 (the counter of redone steps counts the clipped ones)
       RS_REIDX
-      ++n_redo;
+      if (coef != 1.f) ++n_redo;
 #pragma unroll
-      for (int nt = 0; nt < NT1; ++nt) {
-        mW1[nt] = bmW1[nt]; vW1[nt] = bvW1[nt];
+      for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const AdamOut o_ = adam1(pW1[nt][r], gB[nt][r] * coef, mW1[nt][r], vW1[nt][r], b1c, b2c, eps, step_size, inv_bc2s);
+          const AdamOut o_ = adam1(lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j], gB[nt][r] * coef, mW1[nt][r], vW1[nt][r], b1c, b2c,
+                                   eps, step_size, inv_bc2s);
           mW1[nt][r] = o_.m; vW1[nt][r] = o_.v; lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j] = o_.p;
         }
-      }
-      mb1 = bmb1; vb1 = bvb1;
       const AdamOut o_ = adam1(pb1, gb1 * coef, mb1, vb1, b1c, b2c, eps, step_size, inv_bc2s);
       mb1 = o_.m; vb1 = o_.v; lds[L::B1 + 16 * ow + j] = o_.p;
-      if (ol == 0) reinterpret_cast<volatile int*>(red)[98] = (int)((s + 1) & 0x3fffffff);
+      if (s + 1 < nsteps) __syncthreads();                                 // b1 of step s + 1
+    }
+    if constexpr (SPEC1) {
+      if (coef != 1.f) {
+        // ---- clipped after all (rare): layer 1 restored and redone exactly.  The column waves are inside L1 of the next step on
+        // the speculative weights; the flag makes them repeat it behind b2 -- by then this redo is complete, no extra barrier.
+        RS_REIDX
+        ++n_redo;
+#pragma unroll
+        for (int nt = 0; nt < NT1; ++nt) {
+          mW1[nt] = bmW1[nt]; vW1[nt] = bvW1[nt];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const AdamOut o_ = adam1(pW1[nt][r], gB[nt][r] * coef, mW1[nt][r], vW1[nt][r], b1c, b2c, eps, step_size, inv_bc2s);
+            mW1[nt][r] = o_.m; vW1[nt][r] = o_.v; lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j] = o_.p;
+          }
+        }
+        mb1 = bmb1; vb1 = bvb1;
+        const AdamOut o_ = adam1(pb1, gb1 * coef, mb1, vb1, b1c, b2c, eps, step_size, inv_bc2s);
+        mb1 = o_.m; vb1 = o_.v; lds[L::B1 + 16 * ow + j] = o_.p;
+        if (ol == 0) reinterpret_cast<volatile int*>(red)[98] = (int)((s + 1) & 0x3fffffff);
+      }
     }
     {
       RS_REIDX
@@ -1159,7 +1207,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     }
     RS_STAMP(8)                                                            // (redo,) Adam W2
     if (s + 1 < nsteps) __syncthreads();                                  // b2 of step s + 1
-    if (coef != 1.f && s + 1 < nsteps) __syncthreads();                   // (the column waves repeat L1: their halves meet at one more barrier)
+    if (SPEC1 && coef != 1.f && s + 1 < nsteps) __syncthreads();          // (the column waves repeat L1: their halves meet at one more barrier)
     {
       RS_REIDX
 #pragma unroll
@@ -1379,6 +1427,15 @@ extern "C" int spo_update_rs_supported(int obs_dim, int act_dim, int batch, int 
   return 0;
 }
 
+// ... and its KIN = 128 form (observations of 65 .. 128 values: the Car / Racecar / Doggo / Ant navigation tasks)?  A separate
+// question on purpose: spo_update_rs_supported also keys the data-parallel routing, which has no such form.  The PPO-Lagrangian
+// step only: the critic fit (n_nets 2, four row groups) was built and measured SLOWER than the split form it would replace
+// (16.6 - 17.9 against 15.7 - 16.0 us per 128-row step at 72 / 2, 104 / 12, 128 / 16: DESIGN_NOTES.md) and is not instantiated.
+extern "C" int spo_update_rs128_supported(int obs_dim, int act_dim, int batch, int n_nets) {
+  if (obs_dim < 65 || obs_dim > 128 || act_dim < 1 || act_dim > SPO_MAX_ACT || batch < 1) return 0;
+  return (n_nets == 3 && batch <= 64) ? 1 : 0;
+}
+
 // Called by spo_ppo_lag_update_iter / spo_critic_fit_iter (update.hip) when the shape is supported and SPO_UPDATE_FORM selects it.
 int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host, const float* obs, const float* act,
                           const float* logp_old, const float* target_r, const float* target_c, const float* adv,
@@ -1402,12 +1459,20 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   // measured SLOWER, 9.46 against 7.9 us per step: the matrix work per SIMD halves again, but three peers' partials to poll, add
   // and reset put 10.9 k cycles between b5 and b1 where the two-row-group form has 5.4 k; profiles/r06/update_ab_rs.txt)
   static const int rows_env = [] { const char* e = getenv("SPO_RS_ROWS"); return e ? atoi(e) : 32; }();
-  const bool rows16 = cfg_host->batch <= 64 && rows_env == 16;
+  const bool rows16 = cfg_host->batch <= 64 && rows_env == 16 && cfg_host->obs_dim <= 64;
   const int R = (cfg_host->batch <= 64 && !rows16) ? 2 : 4;
   { const char* e = getenv("SPO_RS_PROF_WG"); a.prof_wg = (e && *e) ? atoi(e) : n_nets * R - 1; }
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
   if (int rc = spo::hip_check(hipMemsetAsync(a.zbuf, 0xFF, R == 2 ? rs_z_bytes(2) : rs_z_bytes(4), st), "hipMemsetAsync(rs slots)")) return rc;
-  const int kin = cfg_host->obs_dim <= 16 ? 16 : cfg_host->obs_dim <= 32 ? 32 : 64;
+  const int kin = cfg_host->obs_dim <= 16 ? 16 : cfg_host->obs_dim <= 32 ? 32 : cfg_host->obs_dim <= 64 ? 64 : 128;
+  if (kin == 128) {
+    // one instantiation: 32 rows per workgroup (SPO_RS_ROWS=16 is not read above 64 observations) and no instrumented build --
+    // a profile buffer set through spo_debug_set_update_profile is left untouched by these launches (tools/phase_profile_rs.py
+    // measures KIN <= 64 only)
+    SPO_REQUIRE(spo_update_rs128_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, n_nets),
+                "update_rs: no KIN = 128 form for obs_dim %d, batch %d, %d networks", cfg_host->obs_dim, cfg_host->batch, n_nets);
+    return rs_launch_k<128, 2, false>(a, st);
+  }
 #define RS_GO(K)                                                                                  \
   {                                                                                               \
     if (rows16) { if (prof && K == 64) return rs_launch_k<K, 4, (K == 64), 0, 1>(a, st); return rs_launch_k<K, 4, false, 0, 1>(a, st); } \
