@@ -611,6 +611,38 @@ int spo_ma_clip_adam(float* theta, const float* grad, float* adam_m, float* adam
                      float lr, float adam_eps, float weight_decay, float max_grad_norm, int use_max_grad_norm,
                      float* grad_norm_out, double* partial_ws, void* stream);
 
+/* MACPO's trust-region step without host round trips (csrc/multi_agent.hip), the form the data-parallel trainer runs
+ * (safepo/multi_agent/macpo.py, MACPO_Trainer with world_size > 1 or macpo_sharded_form).
+ *
+ * spo_ma_trpo_linesearch_sums replaces reference safepo/multi_agent/macpo.py:329-366 up to the accept test (evaluate_actions'
+ * log-probabilities, ratio = prod_d exp(logp_d - old_logp_d), the two surrogate means and the mean of kl_divergence,
+ * macpo.py:153-166): one row pass over mean / act / old_logp / mu_old [rows, act_dim], adv / cost_adv / factor [rows],
+ * log_std / std_old [act_dim] with std = std_y_coef * sigmoid(log_std / std_x_coef) and the per-dimension log-probability of
+ * spo_ma_log_probs.  sums4_out (device, fp64) = {sum ratio*factor*adv, sum ratio*factor*cost_adv, sum KL_row, sum ratio}:
+ * ROW SUMS of this rank, so a data-parallel caller all-reduces the four doubles and divides by the global row count;
+ * ratio_out_or_null: float[rows], the per-row ratio.  Reduced in a fixed order (per-block fp64 partials in partial_ws, then one
+ * workgroup per sum; no atomics): the same rows give the same bits on every call and every rank.
+ * partial_ws: double[SPO_MA_LS_WS_DOUBLES].  1 <= act_dim <= SPO_MAX_ACT, rows >= 1.
+ *
+ * spo_ma_cg_init / spo_ma_cg_update replace the body of conjugate_gradient (macpo.py:168-185) around the Fisher-vector product:
+ * x, r, p: float[n] and state4 = {rdotr, done, last alpha, last beta} stay on the device.
+ *   init:    x = 0, r = p = b, rdotr = b.b, done = 0
+ *   update:  alpha = rdotr / (p.avp + 1e-8); x += alpha p; r -= alpha avp; new = r.r; p = r + (new / rdotr) p; rdotr = new;
+ *            done = new < residual_tol.  With done set an update changes nothing, so nsteps enqueued updates give what the
+ *            reference's `break` gives and no host read is needed inside a solve.
+ * Dot products accumulate in fp64 and round once to fp32; the scalar recurrences are fp32 in the reference's order.  One launch
+ * per update up to 16384 elements, two beyond (any n); fixed-order reductions.  ws: double[SPO_MA_CG_WS_DOUBLES], owned by the
+ * solve between init and its last update. */
+#define SPO_MA_LS_WS_DOUBLES 4096
+#define SPO_MA_CG_WS_DOUBLES 520
+int spo_ma_trpo_linesearch_sums(const float* mean, const float* log_std, float std_x_coef, float std_y_coef, const float* act,
+                                const float* old_logp, const float* adv, const float* cost_adv, const float* factor,
+                                const float* mu_old, const float* std_old, int64_t rows, int act_dim, double* sums4_out,
+                                float* ratio_out_or_null, double* partial_ws, void* stream);
+int spo_ma_cg_init(const float* b, float* x, float* r, float* p, float* state4, double* ws, int64_t n, void* stream);
+int spo_ma_cg_update(const float* avp, float* x, float* r, float* p, float* state4, double* ws, int64_t n, float residual_tol,
+                     void* stream);
+
 /* Test comparator for the multi-agent networks' plain products: y[B,N] = x[B,K] w[N,K]^T (mode 0) or y[B,K] = x[B,N] w[N,K]
  * (mode 1) through the hand-written fp32 MFMA kernel (use_rocblas = 0, what spo_ma_forward / backward / jvp run) or through
  * rocBLAS (use_rocblas = 1; dlopen'ed on demand, not used by any product path). */

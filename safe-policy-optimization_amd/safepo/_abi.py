@@ -66,6 +66,7 @@ MAX_OBS, MAX_ACT, CPO_MAX_OBS, WIDE_MAX_ACT = 128, 16, 64, 64   # SPO_MAX_OBS, S
 WIDE_ACTOR_CLIP, WIDE_ACTOR_SURR, WIDE_ACTOR_KLPEN = 0, 1, 2     # spo_wide_actor_loss modes
 KLPEN_SUMS = 8                                     # include/safepo_hip.h SPO_KLPEN_SUMS (floats of spo_kl_penalty_grad's sums)
 GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GAE_PARTIAL_STRIDE (doubles per workgroup)
+MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
 
@@ -177,6 +178,9 @@ PROTOTYPES = {
     "spo_ma_jvp": (c_int, [P, POINTER(MaNet), P, c_int64, P, P, P, P]),
     "spo_ma_value_loss": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P, P, P]),
     "spo_ma_clip_adam": (c_int, [P, P, P, P, c_int64, c_int64, c_float, c_float, c_float, c_float, c_int, P, P, P]),
+    "spo_ma_trpo_linesearch_sums": (c_int, [P, P, c_float, c_float] + [P] * 7 + [c_int64, c_int, P, P, P, P]),
+    "spo_ma_cg_init": (c_int, [P] * 6 + [c_int64, P]),
+    "spo_ma_cg_update": (c_int, [P] * 6 + [c_int64, c_float, P]),
     "spo_ma_gae": (c_int, [P] * 7 + [c_int64, c_int64, c_double, c_double, c_float, c_float, c_float, c_float, P]),
     "spo_mlp_param_count": (c_int64, [POINTER(MlpNet)]),
     "spo_mlp_workspace_floats": (c_int64, [POINTER(MlpNet), c_int64]),
