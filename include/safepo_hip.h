@@ -509,12 +509,12 @@ int spo_synth_env_step_rel(float* next_obs, float* final_obs, float* reward, flo
                            uint64_t step_rel, const uint64_t* step_base_dev, float p_term, float p_cost, int trunc_len,
                            int affine, float obs_scale, float obs_shift, void* stream);
 
-/* ---- f3: multi-agent MAPPO-L networks and update (csrc/ma_net.hip).
+/* ---- f3: multi-agent MAPPO-L networks and update (csrc/ma_net.hip; plain products: csrc/gemm_f32.hip).
  * Networks: safepo/common/model.py:172-363 + safepo/utils/{mlp,act,distributions}.py -- LayerNorm(obs), then n_blocks x
  * [Linear -> ELU -> LayerNorm], then a Linear head (actor: action mean, with a state-independent
  * std = sigmoid(log_std / std_x_coef) * std_y_coef; critics: one value).  One flat fp32 parameter vector per network in the
  * reference's state_dict order (spo_ma_param_offset: which = 0 feature_norm.weight, 1 feature_norm.bias, 2 W_k, 3 b_k,
- * 4 ln_k.weight, 5 ln_k.bias, 6 log_std, 7 head W, 8 head b).  GEMMs run on the in-tree fp32 MFMA kernels (rocBLAS is only the comparator of spo_debug_ma_gemm).
+ * 4 ln_k.weight, 5 ln_k.bias, 6 log_std, 7 head W, 8 head b).  GEMMs run on the in-tree fp32 MFMA kernels.
  * spo_ma_forward keeps the activations of `rows` rows in ws (spo_ma_workspace_floats) for spo_ma_backward, which turns
  * d(loss)/d(head output) into the flat gradient (log_std's entry is owned by spo_ma_actor_loss).
  * Trainer pieces (safepo/multi_agent/mappolag.py:126-199): spo_ma_actor_loss = clipped surrogate on
@@ -643,12 +643,12 @@ int spo_ma_cg_init(const float* b, float* x, float* r, float* p, float* state4, 
 int spo_ma_cg_update(const float* avp, float* x, float* r, float* p, float* state4, double* ws, int64_t n, float residual_tol,
                      void* stream);
 
-/* Test comparator for the multi-agent networks' plain products: y[B,N] = x[B,K] w[N,K]^T (mode 0) or y[B,K] = x[B,N] w[N,K]
- * (mode 1) through the hand-written fp32 MFMA kernel (use_rocblas = 0, what spo_ma_forward / backward / jvp run) or through
- * rocBLAS (use_rocblas = 1; dlopen'ed on demand, not used by any product path). */
+/* Test hook for the plain products of csrc/gemm_f32.hip: y[B,N] = x[B,K] w[N,K]^T (mode 0) or y[B,K] = x[B,N] w[N,K]
+ * (mode 1) through the hand-written fp32 MFMA kernel, what spo_ma_forward / backward / jvp and the wide path run.
+ * use_rocblas must be 0: the rocBLAS comparator it once selected was removed (nonzero: -1, spo_last_error names the removal). */
 int spo_debug_ma_gemm(int use_rocblas, int mode, const float* x, const float* w, float* y, int64_t B, int K, int N, void* stream);
 
-/* ---- wide single-agent networks: ActorVCritic(obs_dim, act_dim, hidden_sizes) for any hidden_sizes (reference
+/* ---- wide single-agent networks (csrc/wide.hip): ActorVCritic(obs_dim, act_dim, hidden_sizes) for any hidden_sizes (reference
  * safepo/common/model.py:30-48,131; isaac_gym_specific_cfg = [1024, 1024, 512], safepo/single_agent/ppo_lag.py:54-65).
  * A network is n_layers Linear layers with tanh between them; dims[0] = input width, dims[n_layers] = output width.
  * Flat layout of one network: for each layer W [out, in] row-major, then b [out] (nn.Sequential.parameters() order).
@@ -769,7 +769,7 @@ int spo_wide_clip_adam(float* theta, float* grad, float* adam_m, float* adam_v, 
                        float* losses3_inout, float* scalars4_out, double* partial_ws, int partial_capacity, void* stream);
 
 
-/* ---- round 4: the wide path as the fallback for any (obs_dim, act_dim, hidden_sizes) and every single-agent script.  The
+/* ---- round 4 (csrc/wide.hip): the wide path as the fallback for any (obs_dim, act_dim, hidden_sizes) and every single-agent script.  The
  * reference's ActorVCritic takes any dims (safepo/common/model.py:131) and its default sweep (safepo/single_agent/benchmark.py:5-44)
  * pairs cpo / pcpo / rcpo / trpo_lag / focops / cup / ppo_lag / cppo_pid with tasks of 72-88 observations (Car, Doggo, Racecar)
  * and with HumanoidVelocity (376 observations, 17 actions).  act_dim <= SPO_WIDE_MAX_ACT.

@@ -1,4 +1,4 @@
-// Adam arithmetic shared by the persistent update kernels (update.hip) and the wide-network path (ma_net.hip).
+// Adam arithmetic shared by the persistent update kernels (update.hip) and the wide-network path (wide.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

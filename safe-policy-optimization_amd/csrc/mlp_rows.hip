@@ -16,7 +16,7 @@
 //     no weight is staged and no barrier sits inside a layer -- one barrier per layer each way; a wave's first tile of the NEXT
 //     layer (eight input tiles: all of a 128-wide layer) is requested a whole stage ahead into a second register set;
 //   * the loss of the network (MSE of a critic, the clipped surrogate and d(log_std) of the actor: the arithmetic of
-//     wide_ppo_loss_kernel, csrc/ma_net.hip) is evaluated between forward and backward on the 16 rows, with the GLOBAL 1 / rows;
+//     wide_ppo_loss_kernel, csrc/wide.hip) is evaluated between forward and backward on the 16 rows, with the GLOBAL 1 / rows;
 //   * every workgroup writes its row group's PARTIAL gradient (theta's layout) and loss sums to parts[group]; a second, tiny launch
 //     (spo_wide_reduce_parts) adds the groups in fixed order into the flat gradient -- deterministic, and exactly where the
 //     data-parallel all-reduce and spo_wide_clip_adam take over.
@@ -60,7 +60,7 @@ __host__ __device__ inline int mr_misc(int AP) { return MR_LS + 2 * AP + 32 * AP
 __host__ __device__ inline int mr_klx(int AP) { return 16 * AP + 3 * AP; }
 enum { MR_PPO = 0, MR_KLPEN = 1 };                  // loss form of a launch (template parameter of the gradient kernel)
 
-constexpr float LOG_SQRT_2PI_F = 0.91893853320467274178f;               // (as csrc/ma_net.hip)
+constexpr float LOG_SQRT_2PI_F = 0.91893853320467274178f;               // (mlp_mfma.h's LOG_SQRT_2PI)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // four consecutive floats at any dword address
 
 struct MrNet {
@@ -201,7 +201,7 @@ __device__ unsigned long long g_mr_prof[2][32];
 // with its forward on their 16 rows -- kind 2 backpropagates ind_i d(KL_i)/d(mean) / rows, kind 3 -(pg_coef / rows) d(ratio_i adv_i)/d(mean)
 // (the fraction F of rows inside the bound taken as 1: the loss's gradient is g_KL + F g_PG, and F is known once every row's
 // indicator is, i.e. in the group sum behind this launch).  One cotangent per workgroup: the backward stages are those of the
-// clipped surrogate.  Per-row arithmetic: wide_klpen_split_kernel's (csrc/ma_net.hip).
+// clipped surrogate.  Per-row arithmetic: wide_klpen_split_kernel's (csrc/wide.hip).
 template <bool VEC, int LOSS = MR_PPO>
 __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void mlp_rows_reduce_kernel(const float* __res
 // The group sum behind the KL-penalty launch (spo_wide_kl_penalty_reduce_parts).  A group's part: [0, P) the critics' gradients and
 // the actor's g_KL, [P, P + 5) its row sums, [pgoff, pgoff + P - ab) the actor's g_PG (F taken as 1).  Groups are added in group
 // order; every thread forms the minibatch's row sums itself (<= 16 groups, the same order: the same F in every thread), so the
-// combine g_KL + F g_PG needs no second pass.  combine's expressions are wide_klpen_combine_kernel's (csrc/ma_net.hip) at scale 1.
+// combine g_KL + F g_PG needs no second pass.  combine's expressions are wide_klpen_combine_kernel's (csrc/wide.hip) at scale 1.
 struct MrKlReduceArgs {
   const float* parts; int R; int64_t stride, P, ab, lo, pgoff, rows;
   int n_loss, combine; float pg_coef;
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(MrKlReduceAr
 }
 
 // ---- the optimiser behind the row groups in TWO launches (world size 1, device-resident clocks: the replayed step).
-// The launch-per-network step ended in wide_prep_kernel -> wide_coef_kernel -> wide_adam_dev_kernel (csrc/ma_net.hip): with the
+// The launch-per-network step ended in wide_prep_kernel -> wide_coef_kernel -> wide_adam_kernel<true> (csrc/wide.hip): with the
 // group sum in front, four launches of ~4.5 us that each do < 1 us of work.  Here (1) the group sum, the critics' L2 gradient, the
 // value coefficient and the norm partials are one pass over the parameters, whose first workgroup also advances the optimiser
 // clocks and the cursor (nobody in that launch reads them), and (2) every workgroup of the Adam pass forms the clip coefficient

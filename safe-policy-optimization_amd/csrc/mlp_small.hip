@@ -1,6 +1,6 @@
 // Small-batch forward / backward of a wide-path network in ONE launch each (round 4).  gfx950 only.
 //
-// The wide-network path (csrc/ma_net.hip spo_mlp_forward / spo_mlp_backward; reference safepo/common/model.py:30-48 build_mlp_network,
+// The wide-network path (csrc/wide.hip spo_mlp_forward / spo_mlp_backward; reference safepo/common/model.py:30-48 build_mlp_network,
 // any hidden_sizes) runs a layer as a GEMM launch plus small kernels: right for the 8 192-row minibatches of
 // isaac_gym_specific_cfg (ppo_lag.py:54-65), but at the reference's default batch of 64 a network's forward is 5 launches and
 // its backward 18 -- a minibatch step of three networks ~70 launches of ~5 us, none of which has 5 us of work (0.37 ms per step,

@@ -5,7 +5,7 @@ The reference builds its MLPs for any `hidden_sizes` (safepo/common/model.py:30-
 `[1024, 1024, 512]` with minibatches of steps_per_epoch // 4 rows for Isaac Gym tasks
 (isaac_gym_specific_cfg, safepo/single_agent/ppo_lag.py:54-65).  The persistent kernels of csrc/update.hip are built
 around a 64-wide network living in one CU's LDS; every other shape runs here, as a sequence of launches on the in-tree
-fp32 MFMA GEMM kernels (csrc/ma_net.hip: spo_mlp_forward / spo_mlp_backward / spo_wide_ppo_loss / spo_wide_clip_adam).
+fp32 MFMA GEMM kernels (csrc/wide.hip on csrc/gemm_f32.hip: spo_mlp_forward / spo_mlp_backward / spo_wide_ppo_loss / spo_wide_clip_adam).
 Same flat parameter vector, same state_dict keys, same optimiser semantics (critic L2 terms, joint clip_grad_norm_,
 three Adam optimisers with the actor's own learning rate, ppo_lag.py:306-329).
 """

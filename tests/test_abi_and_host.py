@@ -1,6 +1,7 @@
 """CPU tests (no GPU): the C-ABI library loads and exports every symbol include/safepo_hip.h declares;
 host-side logic (CLI surface, logger formats, Lagrange, env sharding) matches the reference's contract."""
 import csv
+import ctypes
 import json
 import os
 import re
@@ -49,6 +50,8 @@ def test_argument_errors_without_gpu(built_lib):
     assert b"null" in lib.spo_last_error()
     assert lib.spo_policy_step(None, None, None, None, None, None, None, None, None, None, None, None, 4, 1, 0, 500, 8, None) < 0
     assert b"obs_dim" in lib.spo_last_error()
+    buf = (ctypes.c_float * 4)()                       # non-null, never dereferenced: the call is refused before any launch
+    assert lib.spo_debug_ma_gemm(1, 0, buf, buf, buf, 1, 1, 1, None) < 0 and b"rocBLAS comparator was removed" in lib.spo_last_error()
 
 
 def test_feature_split_entry_points_shape_envelope_and_argument_errors(built_lib):

@@ -939,3 +939,64 @@ def test_mlp_forward_backward_at_small_row_counts_vs_fp64(dev, dims, rows):
             sl = slice(o, o + cnt)
             assert bool((err[sl] <= 3 * yard[sl] + 2e-6 * g64[sl].abs().max()).all()), (l, cnt, float(err[sl].max()), float(yard[sl].max()))
             o += cnt
+
+
+def test_wide_clip_adam_forms_agree_bitwise(dev):
+    """The four entry points of the wide path's joint clip + Adam share one host sequence and one Adam kernel: with equal
+    clocks, the full range and no rescaling spo_wide_clip_adam_ex is spo_wide_clip_adam; with the clocks beta^t placed on the
+    device spo_wide_clip_adam_dev is spo_wide_clip_adam_ex, at the full range and on the two sub-ranges the engines use (the
+    critic fit: Adam below the actor, the actor's stale gradient rescaled; CUP's second stage: norm and Adam over the actor
+    only).  Bit for bit, clipping or not.  700 parameters: three workgroups with a ragged tail, all three parameter ranges;
+    262 221: past the 1 024-workgroup cap, so the grid-stride loops and the coefficient kernel's 64-lane sum take several
+    trips."""
+    import ctypes
+    from safepo import _abi
+    lib = _abi.load()
+    t = 7
+    cfg = _abi.PpoCfg(obs_dim=60, act_dim=8, batch=64, use_critic_norm=1, use_value_coefficient=0, clip=0.2, max_grad_norm=40.0,
+                      lr_actor=2e-4, lr_critic=3e-4, beta1=0.9, beta2=0.999, adam_eps=1e-8, l2_coef=0.001)
+    b1, b2 = float(cfg.beta1), float(cfg.beta2)                    # the betas as the library sees them: rounded to fp32
+    for P, r_end, c_end in ((700, 200, 400), (262144 + 77, 100003, 200006)):
+        ab = c_end
+        g = torch.Generator(device=dev).manual_seed(11)
+        th = torch.randn(P, device=dev, generator=g)
+        m = 0.01 * torch.randn(P, device=dev, generator=g)
+        v = 1e-4 * torch.rand(P, device=dev, generator=g)
+        grad0 = torch.randn(P, device=dev, generator=g)
+
+        def run(form, grad, lo=0, hi=P, norm0=0, rest=0):
+            t_, g_, m_, v_ = th.clone(), grad.clone(), m.clone(), v.clone()
+            l3 = torch.tensor([0.5, 0.25, 0.125], device=dev)
+            s4 = torch.full((4,), float("nan"), device=dev)
+            part = torch.zeros(3 * 1024, dtype=torch.float64, device=dev)
+            pow4 = torch.tensor([b1 ** t, b2 ** t, b1 ** t, b2 ** t, -1.0, -1.0], dtype=torch.float64, device=dev)
+            head = (_abi.ptr(t_), _abi.ptr(g_), _abi.ptr(m_), _abi.ptr(v_), P, r_end, c_end, ab, ctypes.byref(cfg))
+            tail = (_abi.ptr(l3), _abi.ptr(s4), _abi.ptr(part), part.numel(), _abi.stream_ptr())
+            if form == "plain":
+                rc = lib.spo_wide_clip_adam(*head, t, *tail)
+            elif form == "ex":
+                rc = lib.spo_wide_clip_adam_ex(*head, t, t, lo, hi, norm0, rest, *tail)
+            else:
+                rc = lib.spo_wide_clip_adam_dev(*head, _abi.ptr(pow4), lo, hi, norm0, rest, *tail)
+            _abi.check(rc, form)
+            torch.cuda.synchronize()
+            return {"theta": t_, "m": m_, "v": v_, "grad": g_, "scalars4": s4, "losses3": l3}
+
+        def same(a, b, what):
+            for k in a:
+                assert torch.equal(a[k], b[k]), (what, k, float((a[k] - b[k]).abs().max()))
+
+        for scale, clips in ((10.0, True), (1e-3, False)):
+            grad = grad0 * scale
+            plain, ex, devf = run("plain", grad), run("ex", grad), run("dev", grad)
+            assert (float(ex["scalars4"][0]) < 1.0) == clips and bool(torch.isfinite(ex["theta"]).all())
+            assert not torch.equal(ex["theta"], th)
+            same(plain, ex, ("plain/ex", clips))
+            same(ex, devf, ("ex/dev", clips))
+            for lo, hi, norm0, rest in ((0, ab, 0, 1), (ab, P, ab, 0)):          # the critic fit; CUP's second stage
+                a, b = run("ex", grad, lo, hi, norm0, rest), run("dev", grad, lo, hi, norm0, rest)
+                same(a, b, ("ex/dev", clips, lo, hi))
+                assert torch.equal(a["theta"][:lo], th[:lo]) and torch.equal(a["theta"][hi:], th[hi:])
+                assert not torch.equal(a["theta"][lo:hi], th[lo:hi])
+                if rest:
+                    assert torch.equal(a["grad"][hi:], grad[hi:] * a["scalars4"][0])

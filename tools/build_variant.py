@@ -26,7 +26,7 @@ for src in G.HIP_SOURCES:
     else:
         objs.append(os.path.join(G.OBJDIR, src.replace(".hip", ".o")))
 out = os.path.join(vdir, f"libsafepo_hip_{name}.so")
-r = subprocess.run([G._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", out], capture_output=True, text=True)
+r = subprocess.run([G._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out], capture_output=True, text=True)
 if r.returncode:
     sys.exit(r.stderr)
 print(out)

@@ -63,7 +63,7 @@ def _one(WidePPOLagEngine, hidden, batch, steps, D, A, **cfg_kw):
             "params": int(pol.theta.numel()),
             "kernel": (f"ppo_update_ks_kernel: ONE persistent launch for the {steps} steps, 3 networks x {(D + 63) // 64} feature slices = "
                        f"{3 * ((D + 63) // 64)} workgroups (csrc/update_ks.hip)") if ks else rows_label if rows else
-                      "launch-per-layer wide step (csrc/ma_net.hip kernels), full minibatches replayed from one HIP graph"}
+                      "launch-per-layer wide step (csrc/wide.hip kernels), full minibatches replayed from one HIP graph"}
 
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "--isaac":
