@@ -222,6 +222,53 @@ int spo_update_rs_supported(int obs_dim, int act_dim, int batch, int n_nets);
  * steps; nothing is redone in it, the second counter counts its steps whose joint clip was active. */
 int spo_update_rs128_supported(int obs_dim, int act_dim, int batch, int n_nets);
 
+/* Seed-batched PPO-Lagrangian: S INDEPENDENT runs (own parameters, optimiser state, buffers, shuffle, cfg scalars) take the
+ * minibatch steps of one learning iteration in ONE persistent launch of the row-split kernel, every run on its own six workgroups
+ * (3 networks x 2 row groups) of one XCD; run r sits on XCD r mod 8, so up to eight runs have an XCD each and runs r, r + 8, ...
+ * share one.  Per run the arithmetic is that of spo_ppo_lag_update_iter on the row-split form, bit for bit.  Every run has its own
+ * exchange slots, norm granules, placement census and error word (the int at byte 64 of ITS sync_ws: a run whose exchange timed
+ * out leaves its theta and optimiser state as they were and sets it; the others are unaffected).  A run with active == 0 is
+ * skipped: nothing of it is read or written.  The launch keeps one ~49 MB scratch block per (device, stream), allocated at the
+ * first call together with a pinned host ring of argument tables (not under stream capture; the call itself is not capturable:
+ * it copies its argument table from host memory), both freed by spo_update_scratch_release. */
+#define SPO_RS_MAX_REPLICAS 32
+typedef struct {
+  float *theta, *adam_m, *adam_v;
+  int64_t adam_step;            /* optimiser steps this run has taken (adam_step_host of spo_ppo_lag_update_iter) */
+  const float *obs, *act, *logp_old, *target_r, *target_c, *adv;
+  const int32_t* perm;          /* (perm and losses_out may be NULL in a run with active == 0) */
+  float* losses_out;            /* [num_minibatches][3] */
+  void* sync_ws;                /* >= 72 bytes; only the error word at byte 64 is used */
+  spo_ppo_cfg cfg;              /* obs_dim, act_dim, batch equal over the runs; the scalars are the run's own */
+  int active;
+} spo_update_replica;
+
+/* One learning iteration (ceil(M / batch) steps) for every active run of reps_host[n_replicas] (a HOST array).  Checked on the
+ * host before anything is enqueued: 1 <= n_replicas <= SPO_RS_MAX_REPLICAS, equal obs_dim / act_dim / batch, a supported shape
+ * (spo_update_rs_multi_supported), no two runs sharing theta or sync_ws.  Does not read SPO_UPDATE_FORM / SPO_RS_OBS128: the
+ * caller decides whether to batch.  SPO_RS_SAFE=1 forces write-through exchange stores as in the single launch. */
+int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host, int n_replicas, int64_t M, void* stream);
+
+/* 1 exactly where (spo_update_rs_supported(D, A, batch, 3) || spo_update_rs128_supported(D, A, batch, 3)) and
+ * 1 <= n_replicas <= SPO_RS_MAX_REPLICAS. */
+int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas);
+
+/* 1 where spo_ppo_lag_update_iter would itself run this shape on the kernel form the seed-batched launch runs (the row-split
+ * kernel with two row groups) under this process's routing: SPO_UPDATE_FORM >= 3 and no SPO_RS_ROWS=16 (both read once per
+ * process), SPO_RS_OBS128 not 0 above 64 observations.  Batching is bit-for-bit neutral exactly there, so a caller that must
+ * reproduce the stand-alone run batches only where this says 1. */
+int spo_update_rs_multi_matches_single(int obs_dim, int act_dim, int batch);
+
+/* The launch's block -> (run, workgroup 0..5) mapping, the function the kernel itself uses (testable without a GPU): the grid has
+ * 48 * ceil(n_replicas / 8) blocks; block b has XCD label b & 7 and serves run 8 * ((b >> 3) / 6) + (b & 7) as workgroup
+ * (b >> 3) % 6.  Returns 1 and fills replica / wg, or 0 for a block without work (run >= n_replicas, or block outside the grid). */
+int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg);
+
+/* Measurement aid: {runs that took part in a seed-batched launch, of those: runs whose placement census chose write-through
+ * stores (its workgroups not on one XCD, or SPO_RS_SAFE=1)} since the last reset (out2_host, host array).  Their minibatch steps
+ * and clipped / redone steps are summed over the runs into spo_debug_update_counters.  Synchronises the device. */
+int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset);
+
 /* Measurement aid: counters of the main + helper update kernel summed over the launches of this process since the last reset
  * (out4_host, host array): {minibatch steps run, steps whose speculative update turned out clipped and was redone, steps
  * clipped under the conservative protocol, steps run under the conservative protocol}.  The row-split kernel adds its steps to

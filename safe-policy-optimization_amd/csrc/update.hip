@@ -3025,6 +3025,7 @@ extern "C" int spo_update_scratch_release(void* stream_or_null, int all) {
   freed += split_local_release(dev, stream_or_null, all);
   freed += spo::ks_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_scratch_release(dev, stream_or_null, all);
+  freed += spo::rs_multi_scratch_release(dev, stream_or_null, all);
   return freed;
 }
 namespace {
@@ -3122,6 +3123,12 @@ int check_cfg(const spo_ppo_cfg* c) {
 }
 
 }  // namespace
+
+extern "C" int spo_update_rs_multi_matches_single(int obs_dim, int act_dim, int batch) {
+  spo_ppo_cfg c{};
+  c.obs_dim = obs_dim; c.act_dim = act_dim; c.batch = batch;
+  return (rs_takes(&c, 3) && spo::rs_row_groups(obs_dim, batch) == 2) ? 1 : 0;
+}
 
 extern "C" int spo_ppo_lag_update_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                                        const float* obs, const float* act, const float* logp_old,

@@ -20,4 +20,8 @@ int rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t adam
                         void* const* regions, uint32_t step0, size_t rsx_off, void* stream);
 // {minibatch steps run, steps redone after a late clip verdict} of the row-split kernel since the last reset
 int rs_counters(unsigned long long* out2_host, int reset);
+// row groups (2 or 4) the one-GPU launch above runs for this shape (SPO_RS_ROWS, read once per process)
+int rs_row_groups(int obs_dim, int batch);
+// scratch blocks of the replica-batched launch (spo_ppo_lag_update_iter_multi), freed by spo_update_scratch_release
+int rs_multi_scratch_release(int dev, void* stream_or_null, int all);
 }  // namespace spo

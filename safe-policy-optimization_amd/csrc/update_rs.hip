@@ -49,6 +49,7 @@ constexpr int RS_NS = 16;                        // exchange slots (16-byte grou
 constexpr int RS_MAX_R = 4;
 constexpr unsigned RS_SPIN_LIMIT = 1u << 22;
 constexpr int RS_NPHASE = 12;
+constexpr int RS_MULTI_WG = 6;                    // replica-batched launch: workgroups per replica (3 networks x 2 row groups)
 
 template <int KIN, int NCT>
 struct RsLds {                                   // floats; NCT = 16-column tiles per workgroup (2: 32 rows of a minibatch, 1: 16)
@@ -184,8 +185,10 @@ __device__ __forceinline__ void layer_part(const float* Wl, int ld, const float*
 // NCT: 16-column tiles per workgroup -- 2: 32 rows of every minibatch, the four column waves are 2 column tiles x 2 feature halves;
 // 1: 16 rows, the four column waves are the four feature quarters of the one tile (the PPO-Lagrangian step at R = 4: half the
 // matrix work per SIMD again).
-template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2>
-__device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
+// MULTI: the replica-batched launch (ppo_update_rs_multi_kernel) -- the workgroup's index inside its replica arrives in wg_multi
+// (rs_multi_map) instead of following from the block index, and the step counters are added with agent-scope atomics.
+template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2, bool MULTI = false>
+__device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const int wg_multi = 0) {
   // The launch's pointers as INDIVIDUAL scalar-register pairs.  Read straight from the argument struct they arrive as one
   // s_load_dwordx16 -- a 16-register tuple that the allocator can only spill and restore WHOLE: 16 v_readlane at each of 41 places
   // in the step loop, 656 of the loop's ~4 000 instructions, to get at one 64-bit pointer each time (round 6, ISA census).  A plain
@@ -219,7 +222,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     const unsigned long long _t = __builtin_readcyclecounter(); \
     pacc[i] += _t - tprev; tprev = _t;                         \
   }
-  const int wg = (int)(blockIdx.x >> 3);
+  const int wg = MULTI ? wg_multi : (int)(blockIdx.x >> 3);
   const int netl = wg / R, hf = wg - netl * R, net = a.first_net + netl;
   const int tid = threadIdx.x, lane = tid & 63, j_ = lane & 15, q_ = lane >> 4;
   const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1242,7 +1245,12 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds) {
     for (int i = 0; i < RS_NPHASE; ++i) a.prof[RS_NPHASE + i] = pacc[i];
   __syncthreads();                                                        // after the loop: orders the final image before the write-back
   if (ol == 0 && wg == 0) {
-    atomicAdd(&g_rs_counters[0], (unsigned long long)nsteps); atomicAdd(&g_rs_counters[1], (unsigned long long)n_redo);
+    if constexpr (MULTI) {                                                // several replicas in flight: workgroup 0 of each adds
+      __hip_atomic_fetch_add(&g_rs_counters[0], (unsigned long long)nsteps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&g_rs_counters[1], (unsigned long long)n_redo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      atomicAdd(&g_rs_counters[0], (unsigned long long)nsteps); atomicAdd(&g_rs_counters[1], (unsigned long long)n_redo);
+    }
   }
   if (ow == 0 && lane == 0 && hf == 0 && nsteps > 0) {
     const float pp = (red[88] + red[89]) + (red[90] + red[91]);
@@ -1342,6 +1350,68 @@ __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
   else rs_body<KIN, R, false, PROF, XW, NCT>(a, lds);
 }
 
+// ---- replica-batched launch: S independent PPO-Lagrangian runs (own parameters, buffers, optimiser state) take their minibatch
+// steps in ONE persistent launch, each on its own six workgroups (3 networks x 2 row groups) of one XCD.  Workgroups are dealt to
+// the XCDs round-robin by block index (the placement hint above), so block b carries XCD label b & 7; of the blocks with one
+// label, six consecutive ones serve one replica: replica r sits on label r & 7, replicas r, r + 8, ... share an XCD and its L2
+// (at most SPO_RS_MAX_REPLICAS / 8 = 4 of them: 24 workgroups of one CU each on the XCD's 32 CUs).  Host and device share this
+// function (spo_rs_multi_block_map).  False: the block has no work.
+__host__ __device__ inline bool rs_multi_map(int block, int n_replicas, int* replica, int* wg) {
+  const int x = block & 7, k = block >> 3;
+  *replica = 8 * (k / RS_MULTI_WG) + x;
+  *wg = k % RS_MULTI_WG;
+  return *replica < n_replicas;
+}
+inline int rs_multi_grid(int n_replicas) { return 8 * RS_MULTI_WG * ((n_replicas + 7) / 8); }
+
+// One replica's arguments as the kernel reads them from the device table (32 of them do not fit the kernel-argument segment):
+// its own exchange slots, granules + census words, tag base and err word -- the step itself is rs_body's, unchanged.
+struct RsMultiEntry { RsArgs a; int active; };
+
+// {replicas that ran a launch, of those: on the write-through path (the census found them on more than one XCD, or SPO_RS_SAFE=1)}
+__device__ unsigned long long g_rs_multi_counters[2];
+
+template <int KIN>
+__global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiEntry* __restrict__ table, int n_replicas) {
+  int rep, wg;
+  if (!rs_multi_map((int)blockIdx.x, n_replicas, &rep, &wg)) return;
+  if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the replica)
+  const RsArgs a = table[rep].a;                 // uniform address: scalar loads, once
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* const red = lds + RsLds<KIN, 2>::RED;
+  const int tid = threadIdx.x;
+  // ---- placement census, as in ppo_update_rs_kernel but PER REPLICA: over the replica's six workgroups, in its own census words
+  bool fast;
+  {
+    unsigned long long* const xid = a.gran + RS_GRAN_WORDS;
+    const unsigned myx = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;      // HW_REG_XCC_ID
+    if (tid == 0) {
+      red[96] = 0.f;
+      __hip_atomic_store(xid + wg, ((unsigned long long)a.tag_base << 32) | myx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (tid < RS_MULTI_WG) {
+      unsigned long long v = __hip_atomic_load(xid + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned spins = 0;
+      while ((unsigned)(v >> 32) != a.tag_base) {
+        if (++spins > RS_SPIN_LIMIT) { *a.err = 1; break; }
+        __builtin_amdgcn_s_sleep(1);
+        v = __hip_atomic_load(xid + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if ((unsigned)v != myx) red[96] = 1.f;
+    }
+    __syncthreads();
+    fast = (red[96] == 0.f) && !a.force_safe;
+    __syncthreads();
+  }
+  if (wg == 0 && tid == 0) {
+    __hip_atomic_fetch_add(&g_rs_multi_counters[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!fast) __hip_atomic_fetch_add(&g_rs_multi_counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (fast) rs_body<KIN, 2, true, false, 0, 2, true>(a, lds, wg);
+  else rs_body<KIN, 2, false, false, 0, 2, true>(a, lds, wg);
+}
+
 // Exchange scratch: the partial-gradient slots and the norm granules, ordinary device memory.  One block per (device, stream),
 // allocated on first use (update_ks.hip's scheme): launches on one stream are ordered and share it.
 struct RsEntry { int dev; void* stream; char* base; unsigned tag; };
@@ -1436,6 +1506,14 @@ extern "C" int spo_update_rs128_supported(int obs_dim, int act_dim, int batch, i
   return (n_nets == 3 && batch <= 64) ? 1 : 0;
 }
 
+// Row groups of the one-GPU launch below: 2 up to 64 rows, 4 above -- and 4 up to 64 rows too under SPO_RS_ROWS=16 (read once
+// per process; not read above 64 observations).
+int spo::rs_row_groups(int obs_dim, int batch) {
+  static const int rows_env = [] { const char* e = getenv("SPO_RS_ROWS"); return e ? atoi(e) : 32; }();
+  const bool rows16 = batch <= 64 && rows_env == 16 && obs_dim <= 64;
+  return (batch <= 64 && !rows16) ? 2 : 4;
+}
+
 // Called by spo_ppo_lag_update_iter / spo_critic_fit_iter (update.hip) when the shape is supported and SPO_UPDATE_FORM selects it.
 int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host, const float* obs, const float* act,
                           const float* logp_old, const float* target_r, const float* target_c, const float* adv,
@@ -1458,9 +1536,8 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   // opt-in, 16 (SPO_RS_ROWS=16: four row groups up to 64 rows, the column waves as four feature quarters of one column tile --
   // measured SLOWER, 9.46 against 7.9 us per step: the matrix work per SIMD halves again, but three peers' partials to poll, add
   // and reset put 10.9 k cycles between b5 and b1 where the two-row-group form has 5.4 k; profiles/r06/update_ab_rs.txt)
-  static const int rows_env = [] { const char* e = getenv("SPO_RS_ROWS"); return e ? atoi(e) : 32; }();
-  const bool rows16 = cfg_host->batch <= 64 && rows_env == 16 && cfg_host->obs_dim <= 64;
-  const int R = (cfg_host->batch <= 64 && !rows16) ? 2 : 4;
+  const int R = spo::rs_row_groups(cfg_host->obs_dim, cfg_host->batch);
+  const bool rows16 = cfg_host->batch <= 64 && R == 4;
   { const char* e = getenv("SPO_RS_PROF_WG"); a.prof_wg = (e && *e) ? atoi(e) : n_nets * R - 1; }
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
   if (int rc = spo::hip_check(hipMemsetAsync(a.zbuf, 0xFF, R == 2 ? rs_z_bytes(2) : rs_z_bytes(4), st), "hipMemsetAsync(rs slots)")) return rc;
@@ -1513,4 +1590,194 @@ int spo::rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t
                                                                                      : rs_launch_k<K, 2, false, 8>(a, st))
   return kin == 16 ? RS_GO_DP(16) : kin == 32 ? RS_GO_DP(32) : RS_GO_DP(64);
 #undef RS_GO_DP
+}
+
+// ---------------------------------------------------------------------------------------------------- replica-batched launch
+namespace {
+// Exchange scratch of the replica-batched launch, one block per (device, stream), allocated on first use for the full
+// SPO_RS_MAX_REPLICAS (never under capture, like rs_scratch): [replica] exchange slots of two row groups -- contiguous, so ONE
+// hipMemsetAsync re-arms the first n_replicas of them per launch -- then [replica] granules + census words, then the argument table.
+constexpr size_t RSM_Z_BYTES = rs_z_bytes(2);
+constexpr size_t RSM_G_STRIDE = (RS_G_BYTES + 255) / 256 * 256;
+constexpr size_t RSM_G_OFF = (size_t)SPO_RS_MAX_REPLICAS * RSM_Z_BYTES;
+constexpr size_t RSM_T_OFF = RSM_G_OFF + (size_t)SPO_RS_MAX_REPLICAS * RSM_G_STRIDE;
+constexpr size_t RSM_BYTES = RSM_T_OFF + (size_t)SPO_RS_MAX_REPLICAS * sizeof(RsMultiEntry);
+// The argument table leaves the host from pinned memory: RSM_TAB_RING tables per entry, used in turn, each with an event recorded
+// behind its copy -- a table is rewritten only once the copy that read it last has completed, so a launch makes the host wait
+// only when RSM_TAB_RING launches are already queued behind one another.
+constexpr int RSM_TAB_RING = 4;
+struct RsmEntry { int dev; void* stream; char* base; unsigned tag; RsMultiEntry* tab_host; hipEvent_t ev[RSM_TAB_RING]; unsigned calls; };
+RsmEntry g_rsm[RS_SCRATCH_MAX] = {};
+int g_rsm_n = 0;
+
+void rsm_free(RsmEntry& e) {
+  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(replica-batched rs scratch)");
+  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(replica table)");
+  for (int i = 0; i < RSM_TAB_RING; ++i)
+    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(replica table)");
+  e = RsmEntry{};
+}
+
+// The caller holds g_rs_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot).
+int rsm_scratch(hipStream_t st, char** base, unsigned* tag_base, unsigned nsteps, RsMultiEntry** tab_host, hipEvent_t* ev) {
+  const int dev = current_device_slot();
+  RsmEntry* e = nullptr;
+  for (int i = 0; i < g_rsm_n; ++i)
+    if (g_rsm[i].dev == dev && g_rsm[i].stream == (void*)st) e = &g_rsm[i];
+  if (!e) {
+    if (g_rsm_n == RS_SCRATCH_MAX)
+      return spo::fail(-1, "replica-batched update: more than %d (device, stream) pairs hold exchange scratch in this process; "
+                           "call spo_update_scratch_release(stream) for streams that are gone", RS_SCRATCH_MAX);
+    RsmEntry n{};
+    n.dev = dev; n.stream = (void*)st; n.tag = 16u;
+    void* p = nullptr;
+    if (int rc = spo::hip_check(hipMalloc(&p, RSM_BYTES), "hipMalloc(replica-batched rs scratch)")) return rc;
+    n.base = static_cast<char*>(p);
+    if (int rc = spo::hip_check(hipMemset(p, 0, RSM_BYTES), "hipMemset(replica-batched rs scratch)")) { rsm_free(n); return rc; }
+    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(replica-batched rs scratch)")) { rsm_free(n); return rc; }
+    void* h = nullptr;
+    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)RSM_TAB_RING * SPO_RS_MAX_REPLICAS * sizeof(RsMultiEntry), hipHostMallocDefault),
+                                "hipHostMalloc(replica table)")) { rsm_free(n); return rc; }
+    n.tab_host = static_cast<RsMultiEntry*>(h);
+    for (int i = 0; i < RSM_TAB_RING; ++i)
+      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(replica table)")) {
+        rsm_free(n); return rc;
+      }
+    g_rsm[g_rsm_n] = n;
+    e = &g_rsm[g_rsm_n++];
+  }
+  *base = e->base;
+  *tag_base = e->tag;
+  e->tag += nsteps + 2u;
+  const unsigned slot = e->calls++ % RSM_TAB_RING;
+  *tab_host = e->tab_host + (size_t)slot * SPO_RS_MAX_REPLICAS;
+  *ev = e->ev[slot];
+  // (an event that was never recorded is complete)
+  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
+}
+
+template <int KIN>
+int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
+  const size_t sh = RsLds<KIN, 2>::SIZE * sizeof(float);
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  const int dslot = current_device_slot();
+  if (!attr_done[dslot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_multi_kernel<KIN>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs_multi)");
+    attr_done[dslot] = true;
+  }
+  hipLaunchKernelGGL((ppo_update_rs_multi_kernel<KIN>), dim3(rs_multi_grid(n_replicas)), dim3(512), sh, st, table_dev, n_replicas);
+  return 0;
+}
+}  // namespace
+
+int spo::rs_multi_scratch_release(int dev, void* stream_or_null, int all) {
+  std::lock_guard<std::mutex> lk(g_rs_mu);
+  int freed = 0;
+  for (int i = 0; i < g_rsm_n;) {
+    if (g_rsm[i].dev == dev && (all || g_rsm[i].stream == stream_or_null)) {
+      rsm_free(g_rsm[i]);
+      g_rsm[i] = g_rsm[--g_rsm_n];
+      g_rsm[g_rsm_n] = RsmEntry{};
+      ++freed;
+    } else ++i;
+  }
+  return freed;
+}
+
+extern "C" int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas) {
+  if (n_replicas < 1 || n_replicas > SPO_RS_MAX_REPLICAS) return 0;
+  return (spo_update_rs_supported(obs_dim, act_dim, batch, 3) || spo_update_rs128_supported(obs_dim, act_dim, batch, 3)) ? 1 : 0;
+}
+
+extern "C" int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
+  if (n_replicas < 1 || n_replicas > SPO_RS_MAX_REPLICAS || block < 0 || block >= rs_multi_grid(n_replicas)) return 0;
+  int r = 0, w = 0;
+  const bool work = rs_multi_map(block, n_replicas, &r, &w);
+  if (work && replica) *replica = r;
+  if (work && wg) *wg = w;
+  return work ? 1 : 0;
+}
+
+extern "C" int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset) {
+  SPO_REQUIRE(out2_host, "rs_multi_counters: null pointer");
+  if (int rc = spo::hip_check(hipMemcpyFromSymbol(out2_host, HIP_SYMBOL(g_rs_multi_counters), 16), "hipMemcpyFromSymbol")) return rc;
+  if (reset) {
+    unsigned long long z[2] = {0, 0};
+    return spo::hip_check(hipMemcpyToSymbol(HIP_SYMBOL(g_rs_multi_counters), z, 16), "hipMemcpyToSymbol");
+  }
+  return 0;
+}
+
+extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host, int n_replicas, int64_t M, void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "update_iter_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_RS_MAX_REPLICAS, "update_iter_multi: %d replicas outside [1, %d]", n_replicas,
+              SPO_RS_MAX_REPLICAS);
+  SPO_REQUIRE(M > 0, "update_iter_multi: bad sizes");
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  SPO_REQUIRE(spo_update_rs_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, n_replicas),
+              "update_iter_multi: no replica-batched form for obs_dim %d, act_dim %d, batch %d (spo_update_rs_multi_supported)",
+              c0.obs_dim, c0.act_dim, c0.batch);
+  const int64_t nsteps = (M + c0.batch - 1) / c0.batch;
+  SPO_REQUIRE(nsteps < (1ll << 30), "update_iter_multi: too many minibatch steps in one launch");
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_replica& p = reps_host[r];
+    SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.act && p.logp_old && p.target_r && p.target_c && p.adv && p.sync_ws &&
+                    ((p.perm && p.losses_out) || !p.active), "update_iter_multi: null pointer in replica %d", r);
+    SPO_REQUIRE(p.adam_step >= 0, "update_iter_multi: replica %d: negative adam_step", r);
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "update_iter_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r, p.cfg.obs_dim,
+                p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+    for (int q = 0; q < r; ++q)
+      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
+                  "update_iter_multi: replicas %d and %d share theta or sync_ws", q, r);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return spo::fail(-1, "update_iter_multi: the stream is under capture (the argument table is copied from host memory at "
+                           "every call: not a graph node)");
+  }
+  int force_safe;
+  { const char* e = getenv("SPO_RS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  std::lock_guard<std::mutex> lk(g_rs_mu);                                 // (until the table's copy and its event are enqueued)
+  char* base = nullptr;
+  unsigned tag_base = 0;
+  RsMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  if (int rc = rsm_scratch(st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_replica& p = reps_host[r];
+    RsArgs a{};
+    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
+    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
+    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
+    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_Z_BYTES);
+    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_G_OFF + (size_t)r * RSM_G_STRIDE);
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
+    a.tag_base = tag_base;
+    a.n_nets = 3; a.first_net = 0; a.stale_io = nullptr; a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
+    tab[r].a = a;
+    tab[r].active = p.active ? 1 : 0;
+    n_active += tab[r].active;
+  }
+  if (n_active == 0) return 0;
+  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_T_OFF);
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(RsMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
+  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_Z_BYTES, st), "hipMemsetAsync(rs slots)")) return rc;
+  const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : c0.obs_dim <= 64 ? 64 : 128;
+  int rc = kin == 16 ? rs_multi_launch_k<16>(table_dev, n_replicas, st) : kin == 32 ? rs_multi_launch_k<32>(table_dev, n_replicas, st)
+         : kin == 64 ? rs_multi_launch_k<64>(table_dev, n_replicas, st) : rs_multi_launch_k<128>(table_dev, n_replicas, st);
+  if (rc) return rc;
+  SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_multi");
+  return 0;
 }

@@ -25,6 +25,13 @@ class PpoCfg(Structure):
                 ("adam_eps", c_float), ("l2_coef", c_float)]
 
 
+class UpdateReplica(Structure):
+    """spo_update_replica (include/safepo_hip.h): one run of a seed-batched launch."""
+    _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step", c_int64), ("obs", c_void_p),
+                ("act", c_void_p), ("logp_old", c_void_p), ("target_r", c_void_p), ("target_c", c_void_p), ("adv", c_void_p),
+                ("perm", c_void_p), ("losses_out", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg), ("active", c_int)]
+
+
 class MaNet(Structure):
     """spo_ma_net (include/safepo_hip.h)."""
     _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_blocks", c_int32), ("out_dim", c_int32),
@@ -66,6 +73,7 @@ MAX_OBS, MAX_ACT, CPO_MAX_OBS, WIDE_MAX_ACT = 128, 16, 64, 64   # SPO_MAX_OBS, S
 WIDE_ACTOR_CLIP, WIDE_ACTOR_SURR, WIDE_ACTOR_KLPEN = 0, 1, 2     # spo_wide_actor_loss modes
 KLPEN_SUMS = 8                                     # include/safepo_hip.h SPO_KLPEN_SUMS (floats of spo_kl_penalty_grad's sums)
 GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GAE_PARTIAL_STRIDE (doubles per workgroup)
+RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -106,6 +114,11 @@ PROTOTYPES = {
     "spo_ks_supported": (c_int, [c_int, c_int, c_int]),
     "spo_update_rs_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "spo_update_rs128_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_ppo_lag_update_iter_multi": (c_int, [POINTER(UpdateReplica), c_int, c_int64, P]),
+    "spo_update_rs_multi_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_update_rs_multi_matches_single": (c_int, [c_int, c_int, c_int]),
+    "spo_rs_multi_block_map": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_rs_multi_counters": (c_int, [P, c_int]),
     "spo_ppo_lag_update_iter_ks": (c_int, [P, P, P, c_int64] + [P] * 7 + [c_int64, POINTER(PpoCfg), P, P, P]),
     "spo_ppo_lag_grad_ks": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex_ks": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,

@@ -1,0 +1,223 @@
+"""Seed-batched PPO-Lagrangian: S independent runs (own seed, policy, buffer, optimiser state) on one GPU whose minibatch
+steps share ONE persistent launch (spo_ppo_lag_update_iter_multi, csrc/update_rs.hip): run r on its own six co-XCD workgroups.
+Per run nothing changes -- the arithmetic of a step is the single launch's, bit for bit, and every run draws its random numbers
+from its own generator state (ReplicaRNG), so run r of a group is the stand-alone run with its seed.
+
+The stand-alone step uses 6 of the card's 256 CUs; collect, GAE and the KL of the early-stop test stay one launch per run on
+the one stream.
+"""
+from __future__ import annotations
+
+import contextlib
+import os
+import random
+
+import numpy as np
+import torch
+
+from safepo import _abi
+
+
+class ReplicaRNG:
+    """The random-number state of one run of a group: Python's `random`, numpy's global generator, torch's CPU generator and --
+    with `device` -- that device's default generator, seeded the way a stand-alone run seeds itself (random.seed, np.random.seed,
+    torch.manual_seed: single_agent/_first_order.run).  `with rng:` switches the state in and saves it back on the way out;
+    whatever is drawn for the run (policy init, env creation and reset, the rollout's noise, the shuffle) is drawn inside."""
+
+    def __init__(self, seed: int, device=None):
+        self.seed = int(seed)
+        self.device = None if device is None else torch.device(device)
+        # the states a stand-alone run has right after seeding.  Python, numpy and torch's CPU generator: built on generators of
+        # our own.  The device: its default generator is seeded and put back -- no other device's generator is touched (as
+        # torch.manual_seed would), and nothing process-wide is left changed.
+        dev_state = None
+        if self.device is not None:
+            outer = torch.cuda.get_rng_state(self.device)             # (initialises the device's generator if need be)
+            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+            torch.cuda.default_generators[idx].manual_seed(self.seed)
+            dev_state = torch.cuda.get_rng_state(self.device)
+            torch.cuda.set_rng_state(outer, self.device)
+        self._state = (random.Random(self.seed).getstate(), np.random.RandomState(self.seed).get_state(),
+                       torch.Generator().manual_seed(self.seed).get_state(), dev_state)
+        self._outer = None
+
+    def _capture(self):
+        dev = None if self.device is None else torch.cuda.get_rng_state(self.device)
+        return random.getstate(), np.random.get_state(), torch.get_rng_state(), dev
+
+    def _restore(self, st) -> None:
+        random.setstate(st[0])
+        np.random.set_state(st[1])
+        torch.set_rng_state(st[2])
+        if self.device is not None:
+            torch.cuda.set_rng_state(st[3], self.device)
+
+    def __enter__(self):
+        assert self._outer is None, "ReplicaRNG is not re-entrant"
+        self._outer = self._capture()
+        self._restore(self._state)
+        return self
+
+    def __exit__(self, *exc):
+        self._state = self._capture()
+        self._restore(self._outer)
+        self._outer = None
+        return False
+
+
+class PPOLagEngineGroup:
+    """S ordinary one-GPU PPOLagEngines of one shape (observations, actions, rows, minibatch size) on one device.
+    `rngs`: one ReplicaRNG per engine -- the default shuffle of run i is then drawn under rngs[i]."""
+
+    def __init__(self, engines, rngs=None):
+        from safepo.common.engine import PPOLagEngine
+        engines = list(engines)
+        if not engines:
+            raise ValueError("PPOLagEngineGroup: no engines")
+        e0 = engines[0]
+        for i, e in enumerate(engines):
+            if isinstance(e, PPOLagEngine):
+                if type(e) is not PPOLagEngine:
+                    raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
+                                        "PPOLagEngine (hidden [64, 64], obs_dim <= 128, act_dim <= 16) can be grouped")
+                if e.comm.world_size != 1:
+                    raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
+            if (e.D, e.A, e.M) != (e0.D, e0.A, e0.M) or e.dev != e0.dev:
+                raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} has obs / act / rows / device {e.D} / {e.A} / {e.M} / {e.dev}, "
+                                    f"engine 0 has {e0.D} / {e0.A} / {e0.M} / {e0.dev}")
+        if rngs is not None and len(rngs) != len(engines):
+            raise ValueError("PPOLagEngineGroup: one ReplicaRNG per engine")
+        self.engines, self.rngs = engines, rngs
+        # (anything else that has PPOLagEngine's methods -- a recording stand-in in a test -- is stepped one by one)
+        self._native = all(isinstance(e, PPOLagEngine) for e in engines)
+        self.lib = _abi.load() if self._native else None
+
+    def __len__(self):
+        return len(self.engines)
+
+    def rng(self, i: int):
+        """Context of run i's random-number state (a no-op context without rngs)."""
+        return self.rngs[i] if self.rngs is not None else contextlib.nullcontext()
+
+    # ------------------------------------------------------------------ one learning iteration of every active run
+    def batched(self, cfgs=None) -> bool:
+        """Does learning_iter_all run as one launch?  Where the two-row-group row-split kernel is the stand-alone form too
+        (spo_update_rs_multi_matches_single: the library's own routing answers, nothing of it is repeated here) and all runs
+        share the minibatch size.  SPO_FORCE_DP=1 is PPOLagEngine.learning_iter's own switch to the data-parallel entry point."""
+        if not self._native:
+            return False
+        cfgs = cfgs or [e._cfg_struct() for e in self.engines]
+        c0 = cfgs[0]
+        if any(c.batch != c0.batch for c in cfgs):
+            return False
+        if os.environ.get("SPO_FORCE_DP", "0") == "1":
+            return False
+        return bool(self.lib.spo_update_rs_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))
+                    and self.lib.spo_update_rs_multi_matches_single(c0.obs_dim, c0.act_dim, c0.batch))
+
+    def learning_iter_all(self, perms, active=None):
+        """PPOLagEngine.learning_iter(perms[i]) for every run i with active[i] (default: all): one
+        spo_ppo_lag_update_iter_multi launch where batched(), else one launch per run -- the same results.  Returns the
+        per-minibatch losses [n_mb, 3] per run (None for a run that did not take part)."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        if len(perms) != S or len(active) != S:
+            raise ValueError("learning_iter_all: one perm and one active flag per engine")
+        cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
+        if not self.batched(cfgs):
+            return [e.learning_iter(perms[i]) if active[i] else None for i, e in enumerate(self.engines)]
+        e0 = self.engines[0]
+        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
+        reps = (_abi.UpdateReplica * S)()
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            d, b = e.buffer.data, e.buffer
+            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
+            perm = perms[i] if active[i] else None
+            if perm is not None:
+                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            r = reps[i]
+            r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
+            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(b.adv_mix)
+            r.perm, r.losses_out = _abi.ptr(perm), _abi.ptr(losses[i])
+            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
+        _abi.check(self.lib.spo_ppo_lag_update_iter_multi(reps, S, e0.M, _abi.stream_ptr()), "spo_ppo_lag_update_iter_multi")
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                e.adam_step += n_mb
+        return losses
+
+    # ------------------------------------------------------------------ the epoch's update of every run
+    def _read_kls(self, idx) -> list:
+        """kl_read() of the runs idx after their kl_launch(): ONE host synchronisation for all of them."""
+        es = [self.engines[i] for i in idx]
+        if all(torch.is_tensor(getattr(e, "kl_sum", None)) for e in es):
+            sums = torch.cat([e.kl_sum.reshape(1) for e in es]).cpu().tolist()
+            return [float(s) / float(e.M * e.comm.world_size) for s, e in zip(sums, es)]
+        return [e.kl_read() for e in es]
+
+    def update(self, lams, perm_fns=None):
+        """PPOLagEngine.update for every run: GAE, the old-distribution snapshot, then learning iterations with KL early
+        stopping under the run's own target_kl and learning_iters.  A run that stops sits out the remaining launches; the loop
+        ends when none is active.  Per run the order of shuffle draws and KL reads is the stand-alone loop's (the next pass's
+        shuffle is drawn before the KL is read, also on the pass that stops).  Returns the list of update()'s dicts."""
+        es, S = self.engines, len(self.engines)
+        if len(lams) != S:
+            raise ValueError("update: one multiplier per engine")
+        for e, lam in zip(es, lams):
+            e.buffer.compute_gae(lam, e.comm)
+            e.snapshot_old_distribution()
+
+        def default_perm_fn(i):
+            def fn(it):
+                with self.rng(i):
+                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
+            return fn
+
+        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
+        perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+        n_its = [e.cfg["learning_iters"] for e in es]
+        active = [n > 0 for n in n_its]
+        perms = [perm_fns[i](0) if active[i] else None for i in range(S)]
+        all_losses = [[] for _ in range(S)]
+        stop_iter, kl = [0] * S, [1.0] * S
+        it = 0
+        while any(active):
+            idx = [i for i in range(S) if active[i]]
+            losses = self.learning_iter_all(perms, active)
+            for i in idx:
+                all_losses[i].append(losses[i])
+                es[i].kl_launch()
+            for i in idx:
+                perms[i] = perm_fns[i](it + 1) if it + 1 < n_its[i] else None
+            for i, v in zip(idx, self._read_kls(idx)):
+                kl[i] = v
+                stop_iter[i] += 1
+                if v > es[i].cfg["target_kl"] or it + 1 >= n_its[i]:
+                    active[i] = False
+            it += 1
+        self.check_sync_error()
+        outs = []
+        for i, e in enumerate(es):
+            e.buffer.reset()
+            means = torch.cat(all_losses[i], 0).mean(0).tolist() if all_losses[i] else [float("nan")] * 3
+            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2],
+                         "losses": all_losses[i]})
+        return outs
+
+    def check_sync_error(self) -> None:
+        """PPOLagEngine.check_sync_error per run (every run has its own error word); the message names the run."""
+        es = self.engines
+        if all(torch.is_tensor(getattr(e, "sync_ws", None)) for e in es):
+            codes = torch.stack([e.sync_ws[8] for e in es]).cpu().tolist()       # one read for all runs
+        else:
+            codes = [1] * len(es)
+        for i, e in enumerate(es):
+            if not codes[i]:
+                continue
+            try:
+                e.check_sync_error()
+            except _abi.SpoError as err:
+                raise _abi.SpoError(f"replica {i} of {len(es)}: {err}") from None

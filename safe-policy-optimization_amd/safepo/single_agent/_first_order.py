@@ -22,7 +22,7 @@ from safepo.common.lagrange import Lagrange, PIDLagrangian
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import isaac_gym_map
+from safepo.utils.config import isaac_gym_map, refuse_seed_batch, seed_list
 
 NO_CLIP = 1e30      # clamp(ratio, 1-1e30, 1+1e30) is the identity: pg's unclipped surrogate on the same kernel
 
@@ -35,9 +35,80 @@ FOCOPS_LAM, FOCOPS_NU = 1.50, 2.00     # focops.py:44-45
 CUP_LAMBDA, CUP_NU = 0.95, 0.20        # cup.py:44-45
 
 
+def _eval_episodes(policy, eval_env, n_episodes: int, device):
+    """Deterministic-policy episodes on the single eval env (ppo_lag.py:237-269) -> (returns, costs, lengths)."""
+    eval_rews, eval_costs, eval_lens = [], [], []
+    for _ in range(n_episodes):
+        eval_obs, _ = eval_env.reset()
+        eval_obs = _to_dev(eval_obs, device).reshape(1, -1)
+        eval_rew, eval_cost, eval_len, eval_done = 0.0, 0.0, 0.0, False
+        while not eval_done:
+            act, _, _, _ = policy.step(eval_obs, deterministic=True)
+            a_in = act if getattr(eval_env, "is_device_env", False) else act.detach().cpu().numpy()
+            nobs, rew, cst, term, trunc, _ = eval_env.step(a_in)
+            eval_rew += float(np.asarray(rew.cpu() if torch.is_tensor(rew) else rew).reshape(-1)[0])
+            eval_cost += float(np.asarray(cst.cpu() if torch.is_tensor(cst) else cst).reshape(-1)[0])
+            eval_len += 1
+            t0 = np.asarray(term.cpu() if torch.is_tensor(term) else term).reshape(-1)[0]
+            t1 = np.asarray(trunc.cpu() if torch.is_tensor(trunc) else trunc).reshape(-1)[0]
+            eval_done = bool(t0) or bool(t1)
+            eval_obs = _to_dev(nobs, device).reshape(1, -1)
+        eval_rews.append(eval_rew); eval_costs.append(eval_cost); eval_lens.append(eval_len)
+    return eval_rews, eval_costs, eval_lens
+
+
+def _log_epoch(logger, args, out, variant, lagrange, epoch, next_lr, engine, env, is_root, *, t_rollout, t_eval, t_update, t_total):
+    """The epoch's row of progress.csv (ppo_lag.py:351-386)."""
+    if not logger.logged:
+        logger.log_tabular("Metrics/EpRet")
+        logger.log_tabular("Metrics/EpCost")
+        logger.log_tabular("Metrics/EpLen")
+        if args.use_eval:
+            logger.log_tabular("Metrics/EvalEpRet")
+            logger.log_tabular("Metrics/EvalEpCost")
+            logger.log_tabular("Metrics/EvalEpLen")
+        logger.log_tabular("Train/Epoch", epoch + 1)
+        logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
+        logger.log_tabular("Train/StopIter", out["stop_iter"])
+        if variant == "cup":
+            logger.log_tabular("Train/SeconStageStopIter", out["second_stage_stop_iter"])   # (sic) cup.py:419
+        logger.log_tabular("Train/KL", out["kl"])
+        if lagrange is not None:
+            logger.log_tabular("Train/LagragianMultiplier", lagrange.lagrangian_multiplier)
+        logger.log_tabular("Train/LR", next_lr)
+        logger.log_tabular("Loss/Loss_reward_critic")
+        logger.log_tabular("Loss/Loss_cost_critic")
+        logger.log_tabular("Loss/Loss_actor")
+        logger.log_tabular("Time/Rollout", t_rollout)
+        if args.use_eval:
+            logger.log_tabular("Time/Eval", t_eval)
+        logger.log_tabular("Time/Update", t_update)
+        logger.log_tabular("Time/Total", t_total)
+        stats = engine.buffer.stats.cpu()
+        d = engine.buffer.data
+        logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
+        logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
+        logger.dump_tabular()
+        if is_root and ((epoch + 1) % 100 == 0 or epoch == 0):
+            logger.torch_save(itr=epoch)
+            logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
+    else:
+        logger.epoch_dict["Loss/Loss_reward_critic"] = []
+        logger.epoch_dict["Loss/Loss_cost_critic"] = []
+        logger.epoch_dict["Loss/Loss_actor"] = []
+        for k in ("Metrics/EvalEpRet", "Metrics/EvalEpCost", "Metrics/EvalEpLen"):
+            if k in logger.epoch_dict:
+                logger.epoch_dict[k] = []
+
+
 def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip: float | None = 0.2,
         variant: str = "ppo"):
     """variant: "ppo" (clipped surrogate family), "focops" (focops.py:279-367) or "cup" (cup.py:279-405)."""
+    if len(seed_list(args)) > 1:
+        if variant != "ppo":
+            refuse_seed_batch(args, "focops and cup")
+        return run_seed_batch(args, cfg_env, default_cfg, multiplier, clip)
+    args.seed = seed_list(args)[0]      # (`--seeds s` alone is `--seed s`)
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -124,23 +195,7 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
         # (The reference steps `env` instead of `eval_env` inside this loop, which only works for
         #  --num-envs 1; the eval env is stepped here.)
         if args.use_eval:
-            eval_rews, eval_costs, eval_lens = [], [], []
-            for _ in range(1 if epoch < epochs - 1 else 10):
-                eval_obs, _ = eval_env.reset()
-                eval_obs = _to_dev(eval_obs, device).reshape(1, -1)
-                eval_rew, eval_cost, eval_len, eval_done = 0.0, 0.0, 0.0, False
-                while not eval_done:
-                    act, _, _, _ = policy.step(eval_obs, deterministic=True)
-                    a_in = act if getattr(eval_env, "is_device_env", False) else act.detach().cpu().numpy()
-                    nobs, rew, cst, term, trunc, _ = eval_env.step(a_in)
-                    eval_rew += float(np.asarray(rew.cpu() if torch.is_tensor(rew) else rew).reshape(-1)[0])
-                    eval_cost += float(np.asarray(cst.cpu() if torch.is_tensor(cst) else cst).reshape(-1)[0])
-                    eval_len += 1
-                    t0 = np.asarray(term.cpu() if torch.is_tensor(term) else term).reshape(-1)[0]
-                    t1 = np.asarray(trunc.cpu() if torch.is_tensor(trunc) else trunc).reshape(-1)[0]
-                    eval_done = bool(t0) or bool(t1)
-                    eval_obs = _to_dev(nobs, device).reshape(1, -1)
-                eval_rews.append(eval_rew); eval_costs.append(eval_cost); eval_lens.append(eval_len)
+            eval_rews, eval_costs, eval_lens = _eval_episodes(policy, eval_env, 1 if epoch < epochs - 1 else 10, device)
             logger.store(**{"Metrics/EvalEpRet": np.mean(eval_rews), "Metrics/EvalEpCost": np.mean(eval_costs),
                             "Metrics/EvalEpLen": np.mean(eval_lens)})
         torch.cuda.synchronize(device)
@@ -167,47 +222,122 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
         logger.store(**{"Loss/Loss_reward_critic": out["loss_r"], "Loss/Loss_cost_critic": out["loss_c"],
                         "Loss/Loss_actor": out["loss_pi"]})
         timings.append((rollout_end_time - rollout_start_time, update_end_time - eval_end_time))
-        if not logger.logged:
-            logger.log_tabular("Metrics/EpRet")
-            logger.log_tabular("Metrics/EpCost")
-            logger.log_tabular("Metrics/EpLen")
-            if args.use_eval:
-                logger.log_tabular("Metrics/EvalEpRet")
-                logger.log_tabular("Metrics/EvalEpCost")
-                logger.log_tabular("Metrics/EvalEpLen")
-            logger.log_tabular("Train/Epoch", epoch + 1)
-            logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
-            logger.log_tabular("Train/StopIter", out["stop_iter"])
-            if variant == "cup":
-                logger.log_tabular("Train/SeconStageStopIter", out["second_stage_stop_iter"])   # (sic) cup.py:419
-            logger.log_tabular("Train/KL", out["kl"])
-            if lagrange is not None:
-                logger.log_tabular("Train/LagragianMultiplier", lagrange.lagrangian_multiplier)
-            logger.log_tabular("Train/LR", next_lr)
-            logger.log_tabular("Loss/Loss_reward_critic")
-            logger.log_tabular("Loss/Loss_cost_critic")
-            logger.log_tabular("Loss/Loss_actor")
-            logger.log_tabular("Time/Rollout", rollout_end_time - rollout_start_time)
-            if args.use_eval:
-                logger.log_tabular("Time/Eval", eval_end_time - rollout_end_time)
-            logger.log_tabular("Time/Update", update_end_time - eval_end_time)
-            logger.log_tabular("Time/Total", update_end_time - rollout_start_time)
-            stats = engine.buffer.stats.cpu()
-            d = engine.buffer.data
-            logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
-            logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
-            logger.dump_tabular()
-            if is_root and ((epoch + 1) % 100 == 0 or epoch == 0):
-                logger.torch_save(itr=epoch)
-                logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
-        else:
-            logger.epoch_dict["Loss/Loss_reward_critic"] = []
-            logger.epoch_dict["Loss/Loss_cost_critic"] = []
-            logger.epoch_dict["Loss/Loss_actor"] = []
-            for k in ("Metrics/EvalEpRet", "Metrics/EvalEpCost", "Metrics/EvalEpLen"):
-                if k in logger.epoch_dict:
-                    logger.epoch_dict[k] = []
+        _log_epoch(logger, args, out, variant, lagrange, epoch, next_lr, engine, env, is_root,
+                   t_rollout=rollout_end_time - rollout_start_time, t_eval=eval_end_time - rollout_end_time,
+                   t_update=update_end_time - eval_end_time, t_total=update_end_time - rollout_start_time)
     logger.close()
     return {"timings": timings, "policy": policy, "engine": engine}
 
 
+class _SeedRun:
+    """One run of a seed-batched process: what run() holds in local variables, per seed."""
+
+
+def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, clip: float | None):
+    """`--seeds s0 s1 ...`: run() for several seeds in one process on one GPU.  Every seed has its own env, policy, engine,
+    multiplier and logger (in the log directory its own `--seed` run would write) and draws every random number from its own
+    generator state (ReplicaRNG), so each is the stand-alone run of its seed; rollout, evaluation, multiplier update and logging
+    run seed by seed, the update runs through PPOLagEngineGroup -- the seeds' minibatch steps in one persistent launch.  The
+    Time/ columns hold the wall time of the phase for ALL seeds of the process."""
+    from safepo.common.engine_group import PPOLagEngineGroup, ReplicaRNG
+    seeds = seed_list(args)
+    if len(set(seeds)) != len(seeds):
+        raise SystemExit(f"--seeds {seeds}: the same seed twice")
+    if args.device == "cpu":
+        raise RuntimeError("this build runs the PPO-Lagrangian hot path on a ROCm GPU only (--device cuda); "
+                           "there is no CPU fallback")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--seeds with more than one seed does not combine with torchrun (data-parallel runs): one GPU per process")
+    device = torch.device(f"cuda:{args.device_id}")
+    torch.cuda.set_device(device)
+    if args.task in isaac_gym_map:
+        raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
+    config = dict(default_cfg)
+    config.update(getattr(args, "cfg_override", None) or {})
+    config = {k: v for k, v in config.items() if v is not None}
+    config["clip"] = NO_CLIP if clip is None else clip
+    log_dirs = getattr(args, "log_dirs", None) or [os.path.join(args.log_dir, "-".join(["seed", str(s).zfill(3)])) for s in seeds]
+    if len(log_dirs) != len(seeds):
+        raise ValueError("args.log_dirs: one directory per seed")
+    env_kwargs = getattr(args, "env_kwargs", None) or {}
+    steps_per_epoch = config.get("steps_per_epoch", args.steps_per_epoch)
+    total_steps = config.get("total_steps", args.total_steps)
+    local_steps_per_epoch = steps_per_epoch // args.num_envs
+    epochs = total_steps // steps_per_epoch
+
+    runs = []
+    for seed, log_dir in zip(seeds, log_dirs):
+        r = _SeedRun()
+        r.seed, r.rng = seed, ReplicaRNG(seed, device)
+        with r.rng:                                   # the order of run(): env, eval env, policy, ..., reset
+            r.env, obs_space, act_space = make_sa_mujoco_env(num_envs=args.num_envs, env_id=args.task, seed=seed, device=device,
+                                                             **env_kwargs)
+            r.eval_env = None
+            if args.use_eval:
+                r.eval_env, _, _ = make_sa_mujoco_env(num_envs=1, env_id=args.task, seed=None, device=device, **env_kwargs)
+            r.policy = ActorVCritic(obs_dim=obs_space.shape[0], act_dim=act_space.shape[0],
+                                    hidden_sizes=config["hidden_sizes"]).to(device)
+            if not r.policy.kernels_supported():
+                raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "
+                                 f"128, act_dim <= 16); {args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network "
+                                 "kernels: one process per seed")
+            r.engine = PPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
+            if multiplier == "adam":
+                r.lagrange = Lagrange(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init,
+                                      lagrangian_multiplier_lr=args.lagrangian_multiplier_lr, lagrangian_upper_bound=None)
+            elif multiplier == "pid":
+                r.lagrange = PIDLagrangian(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init)
+            else:
+                r.lagrange = None
+            dict_args = dict(vars(args))
+            dict_args.update(config)
+            dict_args.update(seed=seed, log_dir=log_dir)          # (what the stand-alone run of this seed records)
+            r.logger = EpochLogger(log_dir=log_dir, seed=str(seed), verbose=True)
+            r.logger.save_config(dict_args)
+            r.logger.setup_torch_saver(r.policy.actor)
+            r.logger.log("Start with training.")
+            r.rms = r.env.fuse_normalize(True) if hasattr(r.env, "fuse_normalize") else None
+            obs, _ = r.env.reset()
+            r.obs = _to_dev(obs, device)
+        runs.append(r)
+    group = PPOLagEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs])
+
+    timings = []
+    for epoch in range(epochs):
+        rollout_start_time = time.time()
+        for r in runs:
+            with r.rng:
+                r.obs = r.engine.rollout_epoch(r.env, r.obs, rms=r.rms)
+            r.engine.drain_episode_events(r.logger)
+        torch.cuda.synchronize(device)
+        rollout_end_time = time.time()
+        if args.use_eval:
+            for r in runs:
+                with r.rng:
+                    rews, costs, lens = _eval_episodes(r.policy, r.eval_env, 1 if epoch < epochs - 1 else 10, device)
+                r.logger.store(**{"Metrics/EvalEpRet": np.mean(rews), "Metrics/EvalEpCost": np.mean(costs),
+                                  "Metrics/EvalEpLen": np.mean(lens)})
+        torch.cuda.synchronize(device)
+        eval_end_time = time.time()
+        lams = []
+        for r in runs:
+            ep_costs = float(r.logger.get_stats("Metrics/EpCost"))
+            if r.lagrange is not None:
+                r.lagrange.update_lagrange_multiplier(ep_costs)
+            lams.append(r.lagrange.lagrangian_multiplier if r.lagrange is not None else 0.0)
+            r.engine.lr_factor = 1.0 - epoch / epochs if epochs > 0 else 1.0
+        outs = group.update(lams)                      # (the shuffles are drawn under the runs' generator states)
+        torch.cuda.synchronize(device)
+        update_end_time = time.time()
+        next_lr = 3e-4 * (1.0 - min(epoch + 1, epochs) / epochs)
+        timings.append((rollout_end_time - rollout_start_time, update_end_time - eval_end_time))
+        for r, out in zip(runs, outs):
+            r.logger.store(**{"Loss/Loss_reward_critic": out["loss_r"], "Loss/Loss_cost_critic": out["loss_c"],
+                              "Loss/Loss_actor": out["loss_pi"]})
+            _log_epoch(r.logger, args, out, "ppo", r.lagrange, epoch, next_lr, r.engine, r.env, True,
+                       t_rollout=rollout_end_time - rollout_start_time, t_eval=eval_end_time - rollout_end_time,
+                       t_update=update_end_time - eval_end_time, t_total=update_end_time - rollout_start_time)
+    for r in runs:
+        r.logger.close()
+    return {"timings": timings, "policies": [r.policy for r in runs], "engines": [r.engine for r in runs], "group": group,
+            "policy": runs[0].policy, "engine": runs[0].engine}

@@ -23,10 +23,11 @@ from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
 from safepo.single_agent.cpo import _to_dev, make_engine
-from safepo.utils.config import isaac_gym_map
+from safepo.utils.config import isaac_gym_map, refuse_seed_batch
 
 
 def run(args, cfg_env, default_cfg: dict, line_search: bool, use_lagrange: bool):
+    refuse_seed_batch(args, "the second-order scripts")
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)

@@ -4,6 +4,10 @@
 
 MI355X specifics: every run is a whole-GPU job (persistent kernels), so runs are dealt round-robin over the visible GPUs
 through `--device-id`, and `--workers` defaults to one per GPU.  `--workers 0` only prints the commands.
+`--seeds-per-run K` (not a reference flag; default 1 = one subprocess per seed, as the reference) puts up to K seeds of one
+(task, algorithm) into ONE subprocess through the scripts' `--seeds`: their updates share one persistent launch (ppo_lag,
+cppo_pid -- and ppo / pg -- on the persistent kernels' shapes); the other algorithms, and HumanoidVelocity, keep one subprocess
+per seed.
 """
 from __future__ import annotations
 
@@ -48,23 +52,45 @@ def parse_args(argv=None):
     p.add_argument("--total-steps", type=int, default=10000000, help="total number of steps")
     p.add_argument("--num-envs", type=int, default=10, help="number of environments to run in parallel")
     p.add_argument("--steps-per-epoch", type=int, default=20000, help="number of steps per epoch")
+    p.add_argument("--seeds-per-run", type=int, default=1,
+                   help="seeds of one (task, algorithm) per subprocess (--seeds of the scripts: ppo_lag, ppo, pg, cppo_pid; up to 32.  "
+                        "The update's step takes 7.8-7.9 us for all seeds together up to 16 and 8.2 us at 32 where one seed alone takes "
+                        "7.7 (60 / 8; profiles/seed_batch/step_times.txt): no knee up to 32, so the largest K the sweep has seeds for)")
     return p.parse_args(argv)
+
+
+SEED_BATCHED_ALGOS = ("ppo_lag", "ppo", "pg", "cppo_pid")     # the scripts with a `--seeds` form (persistent-kernel shapes only)
+
+
+def _takes_seeds(algo: str, task: str) -> bool:
+    """Can `--seeds` carry several seeds for this (algorithm, task)?  HumanoidVelocity (376 / 17) runs on the wide-network
+    kernels, which have no seed-batched form."""
+    return algo in SEED_BATCHED_ALGOS and "Humanoid" not in task
 
 
 def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
     n_gpus = n_gpus or visible_gpus()
+    per_run = max(getattr(args, "seeds_per_run", 1), 1)
+    if per_run > 32:
+        raise SystemExit("--seeds-per-run: at most 32 seeds share a launch")
+    seeds = [args.start_seed + 1000 * k for k in range(args.num_seeds)]
     commands = []
-    for seed in range(args.num_seeds):
+    for g0 in range(0, len(seeds), per_run):
+        group = seeds[g0:g0 + per_run]
         for task in args.tasks:
             total, per_epoch, envs = args.total_steps, args.steps_per_epoch, args.num_envs
             if "Doggo" in task:                     # benchmark.py:99-102: the long-horizon robot gets 10x the budget
                 total, per_epoch, envs = 100000000, 200000, 20
             for algo in args.algo:
-                commands.append(" ".join([
-                    shlex.quote(sys.executable), shlex.quote(os.path.join(script_dir, f"{algo}.py")), "--task", shlex.quote(task),
-                    "--seed", str(args.start_seed + 1000 * seed), "--write-terminal", "False", "--experiment",
-                    shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
-                    str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))
+                # one command for the whole group where the script takes --seeds, else one per seed as ever
+                batched = len(group) > 1 and _takes_seeds(algo, task)
+                for run in ([group] if batched else [[s] for s in group]):
+                    commands.append(" ".join([
+                        shlex.quote(sys.executable), shlex.quote(os.path.join(script_dir, f"{algo}.py")), "--task", shlex.quote(task),
+                        "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else []) + [
+                        "--write-terminal", "False", "--experiment",
+                        shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
+                        str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))
     return commands
 
 

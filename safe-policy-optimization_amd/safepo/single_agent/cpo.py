@@ -27,7 +27,7 @@ from safepo.common.env import make_sa_mujoco_env
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import isaac_gym_map, run_as_script
+from safepo.utils.config import isaac_gym_map, refuse_seed_batch, run_as_script
 
 STEP_FRACTION = 0.8
 CPO_SEARCHING_STEPS = 15
@@ -767,6 +767,7 @@ def _to_dev(x, dev):
 
 
 def main(args, cfg_env=None, _update="cpo"):
+    refuse_seed_batch(args, "the second-order scripts")
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
