@@ -269,6 +269,16 @@ int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg);
  * and clipped / redone steps are summed over the runs into spo_debug_update_counters.  Synchronises the device. */
 int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset);
 
+/* The row-split kernel's one-GPU forms up to 64 observations skip the joint clip's coefficient arithmetic on a step whose joint squared gradient norm is
+ * at most a per-launch threshold, computed on the host from max_grad_norm so that min(1, max_grad_norm / (sqrtf(t) + 1e-6f)) is
+ * exactly 1.0f in float32 for every 0 <= t <= threshold (the largest float not above (0.999 max_grad_norm)^2; derivation in
+ * csrc/update_rs.hip); above it the exact expression runs as before, so results do not depend on the threshold.  This writes the
+ * threshold a launch with this max_grad_norm uses to *thr_sq_out_host: -1 (never taken) below 2e-3, where 0.001 max_grad_norm
+ * no longer dominates the 1e-6 and the roundings.  Host code, no GPU.  Refused: a null pointer, a negative or NaN norm.
+ * Layer 1's hand-off of the two-row-group forms at 33 .. 64 observations goes out in two batches; SPO_RS_L1_PIPE=0 (read at
+ * every launch, by the seed-batched launch too) selects the one-batch form: the same bits, for A/B runs and tests. */
+int spo_debug_clip_threshold(float max_grad_norm, float* thr_sq_out_host);
+
 /* Measurement aid: counters of the main + helper update kernel summed over the launches of this process since the last reset
  * (out4_host, host array): {minibatch steps run, steps whose speculative update turned out clipped and was redone, steps
  * clipped under the conservative protocol, steps run under the conservative protocol}.  The row-split kernel adds its steps to

@@ -29,6 +29,8 @@
 // Arithmetic per element is that of ppo_update_kernel (same MFMA chaining, loss, Adam); the batch sum of a weight gradient is
 // formed as (rows 0..31) + (rows 32..63) instead of one chain (rounding-level difference: tests at 1e-5 on the first steps and the
 // fp64 drift envelopes at full size).  One GPU; clipped-surrogate actor loss; obs_dim <= 64, act_dim <= 16, batch <= 32 R.
+#include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -44,6 +46,9 @@ using namespace spo;
 
 #ifndef SPO_RS_XR_TWO_PHASE_MIN
 #define SPO_RS_XR_TWO_PHASE_MIN 4     // data-parallel form: all-to-all of every word below this world size, reduce-scatter + all-gather from it on (A/B knob)
+#endif
+#ifndef SPO_RS_CLIP_FAST
+#define SPO_RS_CLIP_FAST 1            // one GPU, KIN <= 64: the joint clip's unclipped fast path (rs_clip_threshold); 0 builds without it (A/B)
 #endif
 constexpr int RS_NS = 16;                        // exchange slots (16-byte groups per lane) per (destination, source): NT1 + 8 used (12 at KIN = 64, all 16 at KIN = 128)
 constexpr int RS_MAX_R = 4;
@@ -86,6 +91,7 @@ struct RsArgs {
   int n_nets, first_net;               // 3 / 0: a PPO-Lagrangian step; 2 / 0: the critic fit
   float* stale_io;                     // critic fit: ||actor.grad||^2 that the joint clip still sees and rescales (cpo.py:557), in / out
   int force_safe;                      // SPO_RS_SAFE=1: write-through exchange stores whatever the placement (tests)
+  float clip_thr_sq;                   // joint ||g||^2 up to which the clip coefficient is exactly 1 (rs_clip_threshold; -1: never taken)
   unsigned long long* prof;            // optional [3][RS_NPHASE] cycle accumulators (instrumented instantiation)
   int prof_wg;                         // ... of this workgroup (SPO_RS_PROF_WG; default: the last one = the actor's last row group)
   // data-parallel form (XW > 0 instantiations): the ranks' exchange regions (spo_p2p_alloc / spo_p2p_open: uncached, IPC-mapped),
@@ -187,7 +193,11 @@ __device__ __forceinline__ void layer_part(const float* Wl, int ld, const float*
 // matrix work per SIMD again).
 // MULTI: the replica-batched launch (ppo_update_rs_multi_kernel) -- the workgroup's index inside its replica arrives in wg_multi
 // (rs_multi_map) instead of following from the block index, and the step counters are added with agent-scope atomics.
-template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2, bool MULTI = false>
+// L1P: layer 1's hand-off in two batches (R = 2, one GPU, KIN = 64) -- the first half of the dW1 tiles leaves while the second
+// half is still being accumulated, and the consumer sums it, takes its L2 / norm terms and runs its speculative Adam while the
+// second half is in flight.  Same slots, parity, cache policy and per-element arithmetic, the norm terms in the same order: the
+// same bits as the one-batch form (SPO_RS_L1_PIPE=0).
+template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2, bool MULTI = false, bool L1P = false>
 __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const int wg_multi = 0) {
   // The launch's pointers as INDIVIDUAL scalar-register pairs.  Read straight from the argument struct they arrive as one
   // s_load_dwordx16 -- a 16-register tuple that the allocator can only spill and restore WHOLE: 16 v_readlane at each of 41 places
@@ -215,6 +225,12 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
   constexpr bool SPEC1 = !WIDE;                   // layer 1's Adam runs ahead of the joint norm
   constexpr int NOWN = NCT, NPART = 4 / NCT;      // output tiles per column wave, waves per column tile
   static_assert(NT1 + 8 <= RS_NS, "layer 1's NT1 + 1 groups and layers 2 / 3's 7 share the RS_NS slots of a (destination, source) pair");
+  constexpr int HB = L1P ? NT1 / 2 : 0;           // dW1 tiles of the first batch
+  // The joint clip's unclipped fast path: one GPU, KIN <= 64.  It pays through the second copy of the layer-2 / 3 Adam steps without
+  // "* coef" (skipping the coefficient arithmetic alone measured no gain); at KIN = 128 layer 1's 33 elements are among the steps
+  // behind the coefficient, and a copy of them costs that form registers it does not have (its scratch grew): not built there.
+  constexpr bool CLIP_FAST = XW == 0 && !WIDE && SPO_RS_CLIP_FAST;
+  static_assert(!L1P || (R == 2 && XW == 0 && NCT == 2 && KIN == 64), "the two-batch hand-off is built for R = 2, one GPU, KIN = 64");
   unsigned long long pacc[RS_NPHASE] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tprev = 0;
 #define RS_STAMP(i)                                            \
@@ -830,6 +846,8 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
       (FL)[f_] = (RSX2_OWNER((W0) + f_ / 3) == a.xr_rank) ? (FL)[f_] : __uint_as_float(x_[f_ / 3][f_ % 3]); \
   }
 
+  // the gradient an Adam step takes: times the clip coefficient, or as it is on a step the threshold test found unclipped
+#define RS_CLIPPED(CL, G) (decltype(CL)::value ? (G) * coef : (G))
 #define RS_ADAM(ADDR, G, M, V)                                                             \
   {                                                                                        \
     const AdamOut o_ = adam1(lds[ADDR], (G), (M), (V), b1c, b2c, eps, step_size, inv_bc2s); \
@@ -936,12 +954,23 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
         az1[r4] = *reinterpret_cast<const f4*>(lds + S::DZ1T + (16 * ow + j) * LDC + 16 * r4 + 4 * q);
 #pragma unroll
       for (int nt = 0; nt < NT1; ++nt) gB[nt] = f4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (L1P) {
+        // the first batch: its tiles' chains interleaved, every accumulator the same products in the same order as below
+#pragma unroll
+        for (int r4 = 0; r4 < NCT; ++r4)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int nt = 0; nt < HB; ++nt) gB[nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[nt]);
+        RS_PUSH(gB, HB, 0, par)
+        __builtin_amdgcn_sched_barrier(0);                                  // (the stores leave HERE, not behind the second batch's products)
+      }
 #pragma unroll
       for (int r4 = 0; r4 < NCT; ++r4)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int nt = 0; nt < NTX; ++nt) gB[nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[nt]);
+          for (int nt = HB; nt < NTX; ++nt) gB[nt] = mfma4(az1[r4][e], bx[r4][nt][e], gB[nt]);
       if constexpr (WIDE) {                                                 // the second half of the tiles through the same registers
         const float* const xt = lds + S::XT + par * KIN * LDC;
 #pragma unroll
@@ -960,9 +989,13 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
 #pragma unroll
       for (int r4 = 0; r4 < NCT; ++r4) rs1 += (az1[r4][0] + az1[r4][1]) + (az1[r4][2] + az1[r4][3]);
       gB[NT1] = f4{quad_row_sum(rs1), 0.f, 0.f, 0.f};
-      RS_PUSH(gB, NT1 + 1, 0, par)
+      RS_PUSH((gB + HB), NT1 + 1 - HB, HB, par)
     }
     RS_STAMP(4)                                                            // dW1, stores
+    // (two-batch hand-off) the first look at the peer's first batch flies under the layer-2 / 3 sums (issued behind those sums
+    // and their L2 terms instead: 7.56 against 7.49 us per step, profiles/rs_l1_pipe/step_times.txt)
+    u4 zwB0[1][L1P ? HB : 1];
+    if constexpr (L1P) RS_LOADS(zwB0, HB, 0, par, 1, 2)
     // ---- while layer 1's partials travel: the peers' layer-2 / 3 partials (sent at b4: long there), their L2 terms and norm share
     // (before b5 this work would come straight out of the column waves' last backward product: the two waves of a SIMD add)
     RS_POLL_SUM(gA, zwA, 7, NT1 + 1, par, 10, (R == 2 && !WIDE))
@@ -1033,7 +1066,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     if constexpr (XW == 0) l2_terms_a();
     const float loss_data = gA[5][2] * inv_n;
     RS_STAMP(5)                                                            // layers 2 / 3: poll, sums, L2 terms
-    {
+    if constexpr (!L1P) {
       u4 zwB[1][NT1 + 1];
       RS_POLL_SUM(gB, zwB, NT1 + 1, 0, par, 11, false)
     }
@@ -1075,6 +1108,71 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     f4 bmW1[WIDE ? 1 : NT1], bvW1[WIDE ? 1 : NT1];                          // (KIN = 128: placeholders, like pW1 -- never touched)
     float bmb1 = 0.f, bvb1 = 0.f;
     unsigned long long gv0 = 0;
+    if constexpr (L1P) {
+      // ---- two-batch hand-off: the first batch is summed, takes its L2 / norm terms and runs its Adam under the second batch's
+      // flight (whose first look is issued before that work); the norm terms in the order of the one-batch form below -- W1 tiles
+      // in nt, r order, then the bias -- and the share out before the second batch's Adam
+      RS_REIDX
+      auto l1_terms = [&](auto LO, auto HI) {                               // L2 term and norm contributions of W1 tiles [LO, HI)
+        if (has_l2) {
+#pragma unroll
+          for (int nt = decltype(LO)::value; nt < decltype(HI)::value; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {                                   // pad columns hold p == 0, g == 0
+              const float p_ = pW1[nt][r];
+              const float g_ = vcoef * fmaf(l2x2, p_, gB[nt][r]);
+              gB[nt][r] = g_; gsq = fmaf(g_, g_, gsq); psq = fmaf(p_, p_, psq);
+            }
+        } else {
+#pragma unroll
+          for (int nt = decltype(LO)::value; nt < decltype(HI)::value; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gsq = fmaf(gB[nt][r], gB[nt][r], gsq);
+        }
+      };
+      auto l1_adam = [&](auto LO, auto HI) {                                // their speculative Adam (backups first)
+#pragma unroll
+        for (int nt = decltype(LO)::value; nt < decltype(HI)::value; ++nt) {
+          bmW1[nt] = mW1[nt]; bvW1[nt] = vW1[nt];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const AdamOut o_ = adam1(pW1[nt][r], gB[nt][r], mW1[nt][r], vW1[nt][r], b1c, b2c, eps, step_size, inv_bc2s);
+            mW1[nt][r] = o_.m; vW1[nt][r] = o_.v; lds[L::W1 + (orow + r) * L::LD1 + 16 * nt + j] = o_.p;
+          }
+        }
+      };
+      constexpr std::integral_constant<int, 0> c_0{};
+      constexpr std::integral_constant<int, HB> c_hb{};
+      constexpr std::integral_constant<int, NT1> c_nt1{};
+      RS_POLL_SUM(gB, zwB0, HB, 0, par, 11, true)
+      u4 zwB1[1][NT1 + 1 - HB];
+      RS_LOADS(zwB1, NT1 + 1 - HB, HB, par, 1, 2)
+      l1_terms(c_0, c_hb);
+      l1_adam(c_0, c_hb);
+      RS_POLL_SUM((gB + HB), zwB1, NT1 + 1 - HB, HB, par, 11, true)
+      l1_terms(c_hb, c_nt1);
+      if (has_l2) {
+        gb1 = vcoef * fmaf(l2x2, pb1, gB[NT1][0]);
+        if (own_b) { gsq = fmaf(gb1, gb1, gsq); psq = fmaf(pb1, pb1, psq); }
+      } else {
+        gb1 = gB[NT1][0];
+        if (own_b) gsq = fmaf(gb1, gb1, gsq);
+      }
+      const float wg_sq = wave_sum_lane63(gsq), wp_sq = wave_sum_lane63(psq);
+      if (lane == 63) {
+        gstore(grow + 4 * netl + ow, ((unsigned long long)tag << 32) | __float_as_uint(wg_sq));
+        red[88 + ow] = wp_sq;
+      }
+      if (lane < 4 * a.n_nets) gv0 = __hip_atomic_load(grow + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (first look: below)
+      {
+        const unsigned own_bits = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(wg_sq), 63);
+        if (lane == 4 * netl + ow) gv0 = ((unsigned long long)tag << 32) | own_bits;
+      }
+      l1_adam(c_hb, c_nt1);
+      bmb1 = mb1; bvb1 = vb1;
+      const AdamOut o_ = adam1(pb1, gb1, mb1, vb1, b1c, b2c, eps, step_size, inv_bc2s);
+      mb1 = o_.m; vb1 = o_.v; lds[L::B1 + 16 * ow + j] = o_.p;
+    } else
     {
       RS_REIDX
       if (has_l2) {
@@ -1129,6 +1227,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     if constexpr (SPEC1) { if (s + 1 < nsteps) __syncthreads(); }         // b1 of step s + 1
     // ---- joint clip_grad_norm_ over all networks (ppo_lag.py:325): the granules of the workgroups with my row-group index
     float coef;
+    bool unclipped = false;                                                // (uniform) the joint norm is below the launch's threshold
     {
       float mine = 0.f;
       unsigned sp_n = 0;
@@ -1156,10 +1255,19 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
 #pragma unroll
       for (int kk = 0; kk < 12; ++kk)
         total_sq += __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(mine), kk));
-      const float norm = sqrtf(total_sq);
-      coef = a.cfg.max_grad_norm / (norm + 1e-6f);                        // clip_grad_norm_ (torch): eps 1e-6
-      coef = coef > 1.f ? 1.f : coef;
-      stale_sq *= coef * coef;
+      // total_sq is the same value in every lane (and workgroup): one scalar compare decides the step.  At or below the
+      // threshold the expression underneath is exactly 1.0f (rs_clip_threshold), so the square root, the division and the
+      // rescale of the stale norm (x 1) are skipped and the Adam steps below take the gradient as it is (x * 1.0f == x).
+      if constexpr (CLIP_FAST)
+        unclipped = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(total_sq))) <= a.clip_thr_sq;
+      if (unclipped) {
+        coef = 1.f;
+      } else {
+        const float norm = sqrtf(total_sq);
+        coef = a.cfg.max_grad_norm / (norm + 1e-6f);                      // clip_grad_norm_ (torch): eps 1e-6
+        coef = coef > 1.f ? 1.f : coef;
+        stale_sq *= coef * coef;
+      }
     }
     RS_STAMP(7)                                                            // wait b1, poll norms, coefficient
     if constexpr (!SPEC1) {
@@ -1201,37 +1309,43 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     }
     {
       RS_REIDX
+      auto adam_l2 = [&](auto CL) {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
+        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          RS_ADAM(L::W2 + (orow + r) * LDH + 16 * nt + j, gA[nt][r] * coef, mW2[nt][r], vW2[nt][r])
-      RS_ADAM(L::B2 + 16 * ow + j, gb2 * coef, mb2, vb2)
+          for (int r = 0; r < 4; ++r)
+            RS_ADAM(L::W2 + (orow + r) * LDH + 16 * nt + j, RS_CLIPPED(CL, gA[nt][r]), mW2[nt][r], vW2[nt][r])
+        RS_ADAM(L::B2 + 16 * ow + j, RS_CLIPPED(CL, gb2), mb2, vb2)
+      };
+      if (CLIP_FAST && unclipped) adam_l2(std::false_type{}); else adam_l2(std::true_type{});
     }
     RS_STAMP(8)                                                            // (redo,) Adam W2
     if (s + 1 < nsteps) __syncthreads();                                  // b2 of step s + 1
     if (SPEC1 && coef != 1.f && s + 1 < nsteps) __syncthreads();          // (the column waves repeat L1: their halves meet at one more barrier)
     {
       RS_REIDX
+      auto adam_l3 = [&](auto CL) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        RS_ADAM(L::W3 + (4 * q + r) * LDH + 16 * ow + j, gA[4][r] * coef, mW3[r], vW3[r])
-      if (ow == 0) {
-        RS_ADAM(L::B3 + j, gb3 * coef, mb3, vb3)
-        if (is_actor) {
+        for (int r = 0; r < 4; ++r)
+          RS_ADAM(L::W3 + (4 * q + r) * LDH + 16 * ow + j, RS_CLIPPED(CL, gA[4][r]), mW3[r], vW3[r])
+        if (ow == 0) {
+          RS_ADAM(L::B3 + j, RS_CLIPPED(CL, gb3), mb3, vb3)
+          if (is_actor) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int ai = 4 * q + r;
-            RS_ADAM(S::LS + ai, gA[6][r] * coef, mls[r], vls[r])             // (replicated over j: identical values)
-            if (ai < A) {                                                    // ... and the loss constants that follow from it
-              const float lsv = lds[S::LS + ai];
-              const float sdv = __expf(lsv);
-              lds[S::LS + 16 + ai] = __builtin_amdgcn_rcpf(sdv * sdv);
-              lds[S::LS + 32 + ai] = lsv + LOG_SQRT_2PI;
+            for (int r = 0; r < 4; ++r) {
+              const int ai = 4 * q + r;
+              RS_ADAM(S::LS + ai, RS_CLIPPED(CL, gA[6][r]), mls[r], vls[r])    // (replicated over j: identical values)
+              if (ai < A) {                                                    // ... and the loss constants that follow from it
+                const float lsv = lds[S::LS + ai];
+                const float sdv = __expf(lsv);
+                lds[S::LS + 16 + ai] = __builtin_amdgcn_rcpf(sdv * sdv);
+                lds[S::LS + 32 + ai] = lsv + LOG_SQRT_2PI;
+              }
             }
           }
         }
-      }
+      };
+      if (CLIP_FAST && unclipped) adam_l3(std::false_type{}); else adam_l3(std::true_type{});
       if (ow == 0 && lane == 0 && hf == 0 && s + 1 < nsteps) {
         const float pp = (red[88] + red[89]) + (red[90] + red[91]);        // (written before b1)
         a.losses[s * 3 + net] = is_actor ? -loss_data : loss_data + l2 * pp;
@@ -1257,6 +1371,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     a.losses[(nsteps - 1) * 3 + net] = is_actor ? -last_loss : last_loss + l2 * pp;
   }
 #undef RS_ADAM
+#undef RS_CLIPPED
 #undef RS_PUSH
 #undef RS_POLL_SUM
 #undef RS_POLL
@@ -1315,7 +1430,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
 #undef RS_STAMP
 }
 
-template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2>
+template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false>
 __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
   if (blockIdx.x & 7) return;                    // placement hint (update.hip): the working blocks land on one XCD and share its L2
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1346,8 +1461,8 @@ __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
     fast = (red[96] == 0.f) && !a.force_safe;
     __syncthreads();
   }
-  if (fast) rs_body<KIN, R, true, PROF, XW, NCT>(a, lds);
-  else rs_body<KIN, R, false, PROF, XW, NCT>(a, lds);
+  if (fast) rs_body<KIN, R, true, PROF, XW, NCT, false, L1P>(a, lds);
+  else rs_body<KIN, R, false, PROF, XW, NCT, false, L1P>(a, lds);
 }
 
 // ---- replica-batched launch: S independent PPO-Lagrangian runs (own parameters, buffers, optimiser state) take their minibatch
@@ -1371,7 +1486,7 @@ struct RsMultiEntry { RsArgs a; int active; };
 // {replicas that ran a launch, of those: on the write-through path (the census found them on more than one XCD, or SPO_RS_SAFE=1)}
 __device__ unsigned long long g_rs_multi_counters[2];
 
-template <int KIN>
+template <int KIN, bool L1P>
 __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiEntry* __restrict__ table, int n_replicas) {
   int rep, wg;
   if (!rs_multi_map((int)blockIdx.x, n_replicas, &rep, &wg)) return;
@@ -1408,8 +1523,8 @@ __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiE
     __hip_atomic_fetch_add(&g_rs_multi_counters[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!fast) __hip_atomic_fetch_add(&g_rs_multi_counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (fast) rs_body<KIN, 2, true, false, 0, 2, true>(a, lds, wg);
-  else rs_body<KIN, 2, false, false, 0, 2, true>(a, lds, wg);
+  if (fast) rs_body<KIN, 2, true, false, 0, 2, true, L1P>(a, lds, wg);
+  else rs_body<KIN, 2, false, false, 0, 2, true, L1P>(a, lds, wg);
 }
 
 // Exchange scratch: the partial-gradient slots and the norm granules, ordinary device memory.  One block per (device, stream),
@@ -1450,18 +1565,42 @@ int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* t
   return 0;
 }
 
-template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2>
+// SPO_RS_L1_PIPE (read at every launch, like SPO_RS_SAFE): 0 = layer 1's hand-off in one batch (the form before the two-batch
+// one), anything else / unset = two batches where that form is built (two row groups, one GPU, KIN = 64: at KIN = 32, one tile per
+// batch, it measured slower than the one-batch form -- profiles/rs_l1_pipe/step_times.txt).  Same bits.
+bool rs_l1_pipe() { const char* e = getenv("SPO_RS_L1_PIPE"); return !(e && *e == '0'); }
+
+// Threshold of the joint clip's fast path: the largest float thr with thr <= (0.999 mg)^2 (formed in double), or -1.
+// Claim: for every float t with 0 <= t <= thr, the float32 evaluation of min(1, mg / (sqrtf(t) + 1e-6f)) is exactly 1.0f.
+//   Let s = sqrt(t) <= 0.999 mg (exact arithmetic; the double product's own rounding, 2^-53 relative, is covered by the margin).
+//   n = sqrtf(t) <= s (1 + 2^-24);  d = fl(n + 1e-6f) <= (n + c)(1 + 2^-24) with c = (float)1e-6 < 1.0000001e-6, so
+//   d <= 0.999 mg (1 + 2^-23 + 2^-48) + 1.0000002e-6 < mg - (0.001 mg - 1.2e-7 mg - 1.0000002e-6).
+//   For mg >= 2e-3 the bracket is >= 2e-6 - 2.4e-10 - 1.0000002e-6 > 0: d < mg, the exact quotient mg / d is > 1, and a
+//   correctly rounded (or merely monotone) division of mg by d < mg cannot return less than mg / mg = 1: coef >= 1 -> min gives 1.0f.
+//   Below 2e-3 (0.001 mg no longer dominates the 1e-6 and the roundings), for mg that is not a number, and for mg <= 0: -1, the
+//   test "total_sq <= thr" is then false for every norm and the exact expression runs as before.  (0.999 mg)^2 beyond the float
+//   range: FLT_MAX -- every finite t then has sqrt(t) <= 0.999 mg.  Between thr and the true boundary the exact expression runs.
+float rs_clip_threshold(float mg) {
+  if (!(mg >= 2e-3f)) return -1.f;
+  const double lim = 0.999 * (double)mg, lim2 = lim * lim;
+  if (!(lim2 < (double)FLT_MAX)) return FLT_MAX;
+  float thr = (float)lim2;
+  if ((double)thr > lim2) thr = nextafterf(thr, 0.f);
+  return thr;
+}
+
+template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false>
 int rs_launch_k(const RsArgs& a, hipStream_t st) {
   const size_t sh = RsLds<KIN, NCT>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
   const int dslot = current_device_slot();
   if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs)");
     attr_done[dslot] = true;
   }
-  hipLaunchKernelGGL((ppo_update_rs_kernel<KIN, R, PROF, XW, NCT>), dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), sh, st, a);
+  hipLaunchKernelGGL((ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P>), dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), sh, st, a);
   return 0;
 }
 
@@ -1529,6 +1668,8 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
   a.n_nets = n_nets; a.first_net = 0; a.stale_io = stale_sq_io; a.prof = prof;
   { const char* e = getenv("SPO_RS_SAFE"); a.force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  a.clip_thr_sq = rs_clip_threshold(cfg_host->max_grad_norm);
+  const bool l1p = rs_l1_pipe();
   const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
   SPO_REQUIRE(nsteps < (1ll << 30), "update_rs: too many minibatch steps in one launch");
   if (int rc = rs_scratch(st, &a.zbuf, &a.gran, &a.tag_base, (unsigned)nsteps)) return rc;
@@ -1545,7 +1686,7 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   if (kin == 128) {
     // one instantiation: 32 rows per workgroup (SPO_RS_ROWS=16 is not read above 64 observations) and no instrumented build --
     // a profile buffer set through spo_debug_set_update_profile is left untouched by these launches (tools/phase_profile_rs.py
-    // measures KIN <= 64 only)
+    // measures KIN = 64 only)
     SPO_REQUIRE(spo_update_rs128_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, n_nets),
                 "update_rs: no KIN = 128 form for obs_dim %d, batch %d, %d networks", cfg_host->obs_dim, cfg_host->batch, n_nets);
     return rs_launch_k<128, 2, false>(a, st);
@@ -1553,7 +1694,12 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
 #define RS_GO(K)                                                                                  \
   {                                                                                               \
     if (rows16) { if (prof && K == 64) return rs_launch_k<K, 4, (K == 64), 0, 1>(a, st); return rs_launch_k<K, 4, false, 0, 1>(a, st); } \
-    if (R == 2) return rs_launch_k<K, 2, false>(a, st);                                           \
+    if (R == 2) {                                                                                 \
+      /* the instrumented instantiations of the default form (KIN = 64, two row groups), only with a profile buffer set */ \
+      if (prof && K == 64) return l1p ? rs_launch_k<K, 2, (K == 64), 0, 2, (K == 64)>(a, st) : rs_launch_k<K, 2, (K == 64)>(a, st); \
+      if (l1p && K == 64) return rs_launch_k<K, 2, false, 0, 2, (K == 64)>(a, st);                \
+      return rs_launch_k<K, 2, false>(a, st);                                                     \
+    }                                                                                             \
     return rs_launch_k<K, 4, false>(a, st);                                                       \
   }
   if (kin == 16) RS_GO(16) else if (kin == 32) RS_GO(32) else RS_GO(64)
@@ -1579,6 +1725,7 @@ int spo::rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t
   a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
   a.n_nets = 3; a.first_net = 0; a.stale_io = nullptr; a.prof = nullptr; a.prof_wg = -1;
   { const char* e = getenv("SPO_RS_SAFE"); a.force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  a.clip_thr_sq = -1.f;                                                    // (the data-parallel forms have no fast path)
   for (int r = 0; r < 8; ++r) a.xr_region[r] = r < world ? regions[r] : nullptr;
   a.xr_rank = rank; a.xr_step0 = step0; a.rsx_off = rsx_off;
   const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
@@ -1656,18 +1803,18 @@ int rsm_scratch(hipStream_t st, char** base, unsigned* tag_base, unsigned nsteps
   return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
 }
 
-template <int KIN>
+template <int KIN, bool L1P>
 int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   const size_t sh = RsLds<KIN, 2>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
   const int dslot = current_device_slot();
   if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_multi_kernel<KIN>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_multi_kernel<KIN, L1P>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs_multi)");
     attr_done[dslot] = true;
   }
-  hipLaunchKernelGGL((ppo_update_rs_multi_kernel<KIN>), dim3(rs_multi_grid(n_replicas)), dim3(512), sh, st, table_dev, n_replicas);
+  hipLaunchKernelGGL((ppo_update_rs_multi_kernel<KIN, L1P>), dim3(rs_multi_grid(n_replicas)), dim3(512), sh, st, table_dev, n_replicas);
   return 0;
 }
 }  // namespace
@@ -1698,6 +1845,13 @@ extern "C" int spo_rs_multi_block_map(int block, int n_replicas, int* replica, i
   if (work && replica) *replica = r;
   if (work && wg) *wg = w;
   return work ? 1 : 0;
+}
+
+extern "C" int spo_debug_clip_threshold(float max_grad_norm, float* thr_sq_out_host) {
+  SPO_REQUIRE(thr_sq_out_host, "clip_threshold: null pointer");
+  SPO_REQUIRE(max_grad_norm >= 0.f, "clip_threshold: max_grad_norm %g is negative or not a number", (double)max_grad_norm);
+  *thr_sq_out_host = rs_clip_threshold(max_grad_norm);
+  return 0;
 }
 
 extern "C" int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset) {
@@ -1763,6 +1917,7 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
     a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
     a.tag_base = tag_base;
     a.n_nets = 3; a.first_net = 0; a.stale_io = nullptr; a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
+    a.clip_thr_sq = rs_clip_threshold(p.cfg.max_grad_norm);
     tab[r].a = a;
     tab[r].active = p.active ? 1 : 0;
     n_active += tab[r].active;
@@ -1775,8 +1930,11 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
   if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_Z_BYTES, st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : c0.obs_dim <= 64 ? 64 : 128;
-  int rc = kin == 16 ? rs_multi_launch_k<16>(table_dev, n_replicas, st) : kin == 32 ? rs_multi_launch_k<32>(table_dev, n_replicas, st)
-         : kin == 64 ? rs_multi_launch_k<64>(table_dev, n_replicas, st) : rs_multi_launch_k<128>(table_dev, n_replicas, st);
+  const bool l1p = rs_l1_pipe();                                           // (the form the single launch takes: batched == stand-alone bits)
+  int rc = kin == 16 ? rs_multi_launch_k<16, false>(table_dev, n_replicas, st)
+         : kin == 32 ? rs_multi_launch_k<32, false>(table_dev, n_replicas, st)
+         : kin == 64 ? (l1p ? rs_multi_launch_k<64, true>(table_dev, n_replicas, st) : rs_multi_launch_k<64, false>(table_dev, n_replicas, st))
+                     : rs_multi_launch_k<128, false>(table_dev, n_replicas, st);
   if (rc) return rc;
   SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_multi");
   return 0;

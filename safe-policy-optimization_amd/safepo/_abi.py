@@ -119,6 +119,7 @@ PROTOTYPES = {
     "spo_update_rs_multi_matches_single": (c_int, [c_int, c_int, c_int]),
     "spo_rs_multi_block_map": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "spo_debug_rs_multi_counters": (c_int, [P, c_int]),
+    "spo_debug_clip_threshold": (c_int, [c_float, POINTER(c_float)]),
     "spo_ppo_lag_update_iter_ks": (c_int, [P, P, P, c_int64] + [P] * 7 + [c_int64, POINTER(PpoCfg), P, P, P]),
     "spo_ppo_lag_grad_ks": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex_ks": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,

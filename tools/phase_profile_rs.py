@@ -1,6 +1,7 @@
 """Debug tool: interval breakdown of the ROW-SPLIT persistent update kernel (csrc/update_rs.hip): cycles per interval of the step
-for column wave 0 and optimiser wave 0 of the last workgroup (the actor's second row group).
-Usage (GPU box): python tools/phase_profile_rs.py"""
+for column wave 0 and optimiser wave 0 of one workgroup -- SPO_RS_PROF_WG = 2 x network + row group; default 5, the actor's second
+row group -- of the default form (two row groups, KIN = 64; SPO_RS_L1_PIPE=0: its one-batch layer-1 hand-off).
+Usage (GPU box): [SPO_RS_PROF_WG=k] [SPO_RS_L1_PIPE=0] python tools/phase_profile_rs.py"""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "safe-policy-optimization_amd"))
@@ -39,7 +40,7 @@ opt = ["wait b3 + loss log + preloads", "wait b4 (images)", "dW2 dW3 + stores", 
        "(poll retries, layers 2/3)", "(poll retries, layer 1)"]
 for row, names, title in ((0, col, "column wave 0"), (1, opt, "optimiser wave 0")):
     tot = p[row][:10].sum()
-    print(f"{title} of the actor's last row group: total {tot/steps:.0f} cycles/step")
+    print(f"{title} of workgroup {os.environ.get('SPO_RS_PROF_WG', '5')} (2 x network + row group): total {tot/steps:.0f} cycles/step")
     for i, n in enumerate(names):
         if n:
             unit = "" if i >= 10 else f"  {100*p[row][i]/max(tot,1):5.1f}%"
