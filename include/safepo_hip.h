@@ -269,6 +269,55 @@ int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg);
  * and clipped / redone steps are summed over the runs into spo_debug_update_counters.  Synchronises the device. */
 int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset);
 
+/* Seed-batched critic fit: S INDEPENDENT runs of the CPO family (own critics, optimiser state, buffers, shuffle, cfg scalars,
+ * stale actor-gradient norm) take the minibatch steps of one critic-fit iteration in ONE persistent launch of the row-split kernel,
+ * every run on its own eight workgroups (2 critics x 4 row groups) of one XCD; run r sits on XCD r mod 8, runs r, r + 8, r + 16
+ * share one.  Per run the arithmetic is that of spo_critic_fit_iter on the four-row-group row-split form, bit for bit.  At most
+ * 24 runs: three per XCD are 24 working blocks of one CU each on an XCD's 32 CUs -- the 8-CU slack per XCD that co-residency of
+ * the PPO form rests on (32 runs would need every CU of every XCD).  Every run has its own exchange slots, norm granules,
+ * placement census and error word (the int at byte 64 of ITS sync_ws) and its own stale_sq_io.  A run with active == 0 is skipped:
+ * nothing of it is read or written.  The launch keeps one scratch block of its own per (device, stream), sized for 24 runs
+ * (24 x 6 MiB of exchange slots + 30 KB of granules and argument table: ~151 MB; the PPO form's block is separate and unchanged),
+ * allocated at the first call together with a pinned ring of argument tables (not under stream capture; the call itself is not
+ * capturable), freed by spo_update_scratch_release. */
+#define SPO_RS_CRITIC_MAX_REPLICAS 24
+typedef struct {
+  float *theta, *adam_m, *adam_v;
+  int64_t adam_step;            /* optimiser steps this run has taken (adam_step_host of spo_critic_fit_iter) */
+  const float *obs, *target_r, *target_c;
+  const int32_t* perm;          /* (perm and losses_out may be NULL in a run with active == 0) */
+  float* losses_out;            /* [num_minibatches][3]; columns 0 and 1 are written */
+  float* stale_sq_io;           /* the run's ||actor.grad||^2, in / out (spo_critic_fit_iter); not NULL */
+  void* sync_ws;                /* >= 72 bytes: its first 64 bytes are zeroed as spo_critic_fit_iter does, the error word is at byte 64 */
+  spo_ppo_cfg cfg;              /* obs_dim, act_dim, batch equal over the runs; the scalars are the run's own */
+  int active;
+} spo_critic_fit_replica;
+
+/* One critic-fit iteration (ceil(M / batch) steps) for every active run of reps_host[n_replicas] (a HOST array).  Checked on the
+ * host before anything is enqueued: 1 <= n_replicas <= SPO_RS_CRITIC_MAX_REPLICAS, equal obs_dim / act_dim / batch, a supported
+ * shape (spo_critic_fit_multi_supported), null pointers, no two runs sharing theta, sync_ws or stale_sq_io, a stream under
+ * capture.  All runs inactive: returns 0 with nothing enqueued.  Does not read SPO_UPDATE_FORM: the caller decides whether to
+ * batch (spo_critic_fit_multi_matches_single).  SPO_RS_SAFE=1 forces write-through exchange stores as in the single launch. */
+int spo_critic_fit_iter_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream);
+
+/* 1 exactly where spo_update_rs_supported(D, A, batch, 2), 65 <= batch <= 128 (the four-row-group form; batches up to 64 run
+ * two row groups in the single launch and are not batched here) and 1 <= n_replicas <= SPO_RS_CRITIC_MAX_REPLICAS. */
+int spo_critic_fit_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas);
+
+/* 1 where spo_critic_fit_iter would itself run this shape on the four-row-group row-split form under this process's routing
+ * (SPO_UPDATE_FORM >= 3, read once per process): batching is bit-for-bit neutral exactly there. */
+int spo_critic_fit_multi_matches_single(int obs_dim, int act_dim, int batch);
+
+/* The critic-batched launch's block -> (run, workgroup 0..7) mapping, the function the kernel itself uses: the grid has
+ * 64 * ceil(n_replicas / 8) blocks; block b has XCD label b & 7 and serves run 8 * ((b >> 3) / 8) + (b & 7) as workgroup
+ * (b >> 3) % 8.  Returns 1 and fills replica / wg, or 0 for a block without work (run >= n_replicas, block outside the grid, or
+ * n_replicas outside [1, SPO_RS_CRITIC_MAX_REPLICAS]). */
+int spo_rs_critic_multi_block_map(int block, int n_replicas, int* replica, int* wg);
+
+/* spo_debug_rs_multi_counters for the critic-batched launches: {runs that took part, of those: on the write-through path} since
+ * the last reset.  spo_debug_rs_multi_counters itself counts the PPO launches only, as before.  Synchronises the device. */
+int spo_debug_rs_critic_multi_counters(unsigned long long* out2_host, int reset);
+
 /* The row-split kernel's one-GPU forms up to 64 observations skip the joint clip's coefficient arithmetic on a step whose joint squared gradient norm is
  * at most a per-launch threshold, computed on the host from max_grad_norm so that min(1, max_grad_norm / (sqrtf(t) + 1e-6f)) is
  * exactly 1.0f in float32 for every 0 <= t <= threshold (the largest float not above (0.999 max_grad_norm)^2; derivation in

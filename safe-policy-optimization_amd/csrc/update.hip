@@ -3130,6 +3130,12 @@ extern "C" int spo_update_rs_multi_matches_single(int obs_dim, int act_dim, int 
   return (rs_takes(&c, 3) && spo::rs_row_groups(obs_dim, batch) == 2) ? 1 : 0;
 }
 
+extern "C" int spo_critic_fit_multi_matches_single(int obs_dim, int act_dim, int batch) {
+  spo_ppo_cfg c{};
+  c.obs_dim = obs_dim; c.act_dim = act_dim; c.batch = batch;
+  return (batch > 64 && rs_takes(&c, 2) && spo::rs_row_groups(obs_dim, batch) == 4) ? 1 : 0;
+}
+
 extern "C" int spo_ppo_lag_update_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                                        const float* obs, const float* act, const float* logp_old,
                                        const float* target_r, const float* target_c, const float* adv,

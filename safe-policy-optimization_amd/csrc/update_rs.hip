@@ -55,6 +55,7 @@ constexpr int RS_MAX_R = 4;
 constexpr unsigned RS_SPIN_LIMIT = 1u << 22;
 constexpr int RS_NPHASE = 12;
 constexpr int RS_MULTI_WG = 6;                    // replica-batched launch: workgroups per replica (3 networks x 2 row groups)
+constexpr int RS_CRITIC_MULTI_WG = 8;             // ... of the critic fit (2 critics x 4 row groups)
 
 template <int KIN, int NCT>
 struct RsLds {                                   // floats; NCT = 16-column tiles per workgroup (2: 32 rows of a minibatch, 1: 16)
@@ -1471,13 +1472,15 @@ __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
 // label, six consecutive ones serve one replica: replica r sits on label r & 7, replicas r, r + 8, ... share an XCD and its L2
 // (at most SPO_RS_MAX_REPLICAS / 8 = 4 of them: 24 workgroups of one CU each on the XCD's 32 CUs).  Host and device share this
 // function (spo_rs_multi_block_map).  False: the block has no work.
-__host__ __device__ inline bool rs_multi_map(int block, int n_replicas, int* replica, int* wg) {
+// `wgs`: workgroups per replica -- RS_MULTI_WG for the PPO-Lagrangian step, RS_CRITIC_MULTI_WG for the critic fit (there replicas
+// r, r + 8, r + 16 share an XCD: SPO_RS_CRITIC_MAX_REPLICAS / 8 = 3 of them, again 24 workgroups on the XCD's 32 CUs).
+__host__ __device__ inline bool rs_multi_map(int block, int n_replicas, int wgs, int* replica, int* wg) {
   const int x = block & 7, k = block >> 3;
-  *replica = 8 * (k / RS_MULTI_WG) + x;
-  *wg = k % RS_MULTI_WG;
+  *replica = 8 * (k / wgs) + x;
+  *wg = k % wgs;
   return *replica < n_replicas;
 }
-inline int rs_multi_grid(int n_replicas) { return 8 * RS_MULTI_WG * ((n_replicas + 7) / 8); }
+inline int rs_multi_grid(int n_replicas, int wgs) { return 8 * wgs * ((n_replicas + 7) / 8); }
 
 // One replica's arguments as the kernel reads them from the device table (32 of them do not fit the kernel-argument segment):
 // its own exchange slots, granules + census words, tag base and err word -- the step itself is rs_body's, unchanged.
@@ -1485,17 +1488,20 @@ struct RsMultiEntry { RsArgs a; int active; };
 
 // {replicas that ran a launch, of those: on the write-through path (the census found them on more than one XCD, or SPO_RS_SAFE=1)}
 __device__ unsigned long long g_rs_multi_counters[2];
+__device__ unsigned long long g_rs_critic_multi_counters[2];      // ... of the critic-fit launches
 
-template <int KIN, bool L1P>
+// R row groups x NN networks per replica: <KIN, L1P> (2 x 3) is the PPO-Lagrangian step; <KIN, false, 4, 2> is the critic fit
+// (cpo.py:534-571, minibatches of 65 .. 128 rows) -- per replica the step of ppo_update_rs_kernel<KIN, 4> with n_nets = 2.
+template <int KIN, bool L1P, int R = 2, int NN = 3>
 __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiEntry* __restrict__ table, int n_replicas) {
   int rep, wg;
-  if (!rs_multi_map((int)blockIdx.x, n_replicas, &rep, &wg)) return;
+  if (!rs_multi_map((int)blockIdx.x, n_replicas, NN * R, &rep, &wg)) return;
   if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the replica)
   const RsArgs a = table[rep].a;                 // uniform address: scalar loads, once
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const red = lds + RsLds<KIN, 2>::RED;
   const int tid = threadIdx.x;
-  // ---- placement census, as in ppo_update_rs_kernel but PER REPLICA: over the replica's six workgroups, in its own census words
+  // ---- placement census, as in ppo_update_rs_kernel but PER REPLICA: over the replica's NN * R workgroups, in its own census words
   bool fast;
   {
     unsigned long long* const xid = a.gran + RS_GRAN_WORDS;
@@ -1505,7 +1511,7 @@ __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiE
       __hip_atomic_store(xid + wg, ((unsigned long long)a.tag_base << 32) | myx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    if (tid < RS_MULTI_WG) {
+    if (tid < NN * R) {
       unsigned long long v = __hip_atomic_load(xid + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       unsigned spins = 0;
       while ((unsigned)(v >> 32) != a.tag_base) {
@@ -1520,11 +1526,16 @@ __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiE
     __syncthreads();
   }
   if (wg == 0 && tid == 0) {
-    __hip_atomic_fetch_add(&g_rs_multi_counters[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!fast) __hip_atomic_fetch_add(&g_rs_multi_counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (NN == 3) {
+      __hip_atomic_fetch_add(&g_rs_multi_counters[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!fast) __hip_atomic_fetch_add(&g_rs_multi_counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      __hip_atomic_fetch_add(&g_rs_critic_multi_counters[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!fast) __hip_atomic_fetch_add(&g_rs_critic_multi_counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
-  if (fast) rs_body<KIN, 2, true, false, 0, 2, true, L1P>(a, lds, wg);
-  else rs_body<KIN, 2, false, false, 0, 2, true, L1P>(a, lds, wg);
+  if (fast) rs_body<KIN, R, true, false, 0, 2, true, L1P>(a, lds, wg);
+  else rs_body<KIN, R, false, false, 0, 2, true, L1P>(a, lds, wg);
 }
 
 // Exchange scratch: the partial-gradient slots and the norm granules, ordinary device memory.  One block per (device, stream),
@@ -1741,21 +1752,29 @@ int spo::rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t
 
 // ---------------------------------------------------------------------------------------------------- replica-batched launch
 namespace {
-// Exchange scratch of the replica-batched launch, one block per (device, stream), allocated on first use for the full
-// SPO_RS_MAX_REPLICAS (never under capture, like rs_scratch): [replica] exchange slots of two row groups -- contiguous, so ONE
-// hipMemsetAsync re-arms the first n_replicas of them per launch -- then [replica] granules + census words, then the argument table.
-constexpr size_t RSM_Z_BYTES = rs_z_bytes(2);
+// Exchange scratch of a replica-batched launch, one block per (device, stream) and FORM (the PPO-Lagrangian step: two row groups,
+// SPO_RS_MAX_REPLICAS; the critic fit: four row groups, SPO_RS_CRITIC_MAX_REPLICAS -- a block of its own, so that the first one
+// does not grow), allocated on that form's first use for its full replica count (never under capture, like rs_scratch):
+// [replica] exchange slots -- contiguous, so ONE hipMemsetAsync re-arms the first n_replicas of them per launch -- then [replica]
+// granules + census words, then the argument table.
 constexpr size_t RSM_G_STRIDE = (RS_G_BYTES + 255) / 256 * 256;
-constexpr size_t RSM_G_OFF = (size_t)SPO_RS_MAX_REPLICAS * RSM_Z_BYTES;
-constexpr size_t RSM_T_OFF = RSM_G_OFF + (size_t)SPO_RS_MAX_REPLICAS * RSM_G_STRIDE;
-constexpr size_t RSM_BYTES = RSM_T_OFF + (size_t)SPO_RS_MAX_REPLICAS * sizeof(RsMultiEntry);
+struct RsmLayout {
+  size_t z_bytes;                                  // exchange slots of one replica
+  int max_reps;
+  constexpr size_t g_off() const { return (size_t)max_reps * z_bytes; }
+  constexpr size_t t_off() const { return g_off() + (size_t)max_reps * RSM_G_STRIDE; }
+  constexpr size_t bytes() const { return t_off() + (size_t)max_reps * sizeof(RsMultiEntry); }
+};
+constexpr RsmLayout RSM_PPO{rs_z_bytes(2), SPO_RS_MAX_REPLICAS};                 // ~49 MB
+constexpr RsmLayout RSM_CRITIC{rs_z_bytes(4), SPO_RS_CRITIC_MAX_REPLICAS};       // 24 x 6 MiB of slots + 30 KB: ~151 MB
 // The argument table leaves the host from pinned memory: RSM_TAB_RING tables per entry, used in turn, each with an event recorded
 // behind its copy -- a table is rewritten only once the copy that read it last has completed, so a launch makes the host wait
 // only when RSM_TAB_RING launches are already queued behind one another.
 constexpr int RSM_TAB_RING = 4;
 struct RsmEntry { int dev; void* stream; char* base; unsigned tag; RsMultiEntry* tab_host; hipEvent_t ev[RSM_TAB_RING]; unsigned calls; };
-RsmEntry g_rsm[RS_SCRATCH_MAX] = {};
-int g_rsm_n = 0;
+struct RsmPool { RsmLayout lay; RsmEntry e[RS_SCRATCH_MAX]; int n; };
+RsmPool g_rsm{RSM_PPO, {}, 0};
+RsmPool g_rsm_critic{RSM_CRITIC, {}, 0};
 
 void rsm_free(RsmEntry& e) {
   if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(replica-batched rs scratch)");
@@ -1766,71 +1785,113 @@ void rsm_free(RsmEntry& e) {
 }
 
 // The caller holds g_rs_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot).
-int rsm_scratch(hipStream_t st, char** base, unsigned* tag_base, unsigned nsteps, RsMultiEntry** tab_host, hipEvent_t* ev) {
+int rsm_scratch(RsmPool& pool, hipStream_t st, char** base, unsigned* tag_base, unsigned nsteps, RsMultiEntry** tab_host, hipEvent_t* ev) {
   const int dev = current_device_slot();
+  const size_t bytes = pool.lay.bytes();
   RsmEntry* e = nullptr;
-  for (int i = 0; i < g_rsm_n; ++i)
-    if (g_rsm[i].dev == dev && g_rsm[i].stream == (void*)st) e = &g_rsm[i];
+  for (int i = 0; i < pool.n; ++i)
+    if (pool.e[i].dev == dev && pool.e[i].stream == (void*)st) e = &pool.e[i];
   if (!e) {
-    if (g_rsm_n == RS_SCRATCH_MAX)
+    if (pool.n == RS_SCRATCH_MAX)
       return spo::fail(-1, "replica-batched update: more than %d (device, stream) pairs hold exchange scratch in this process; "
                            "call spo_update_scratch_release(stream) for streams that are gone", RS_SCRATCH_MAX);
     RsmEntry n{};
     n.dev = dev; n.stream = (void*)st; n.tag = 16u;
     void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, RSM_BYTES), "hipMalloc(replica-batched rs scratch)")) return rc;
+    if (int rc = spo::hip_check(hipMalloc(&p, bytes), "hipMalloc(replica-batched rs scratch)")) return rc;
     n.base = static_cast<char*>(p);
-    if (int rc = spo::hip_check(hipMemset(p, 0, RSM_BYTES), "hipMemset(replica-batched rs scratch)")) { rsm_free(n); return rc; }
+    if (int rc = spo::hip_check(hipMemset(p, 0, bytes), "hipMemset(replica-batched rs scratch)")) { rsm_free(n); return rc; }
     if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(replica-batched rs scratch)")) { rsm_free(n); return rc; }
     void* h = nullptr;
-    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)RSM_TAB_RING * SPO_RS_MAX_REPLICAS * sizeof(RsMultiEntry), hipHostMallocDefault),
+    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)RSM_TAB_RING * pool.lay.max_reps * sizeof(RsMultiEntry), hipHostMallocDefault),
                                 "hipHostMalloc(replica table)")) { rsm_free(n); return rc; }
     n.tab_host = static_cast<RsMultiEntry*>(h);
     for (int i = 0; i < RSM_TAB_RING; ++i)
       if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(replica table)")) {
         rsm_free(n); return rc;
       }
-    g_rsm[g_rsm_n] = n;
-    e = &g_rsm[g_rsm_n++];
+    pool.e[pool.n] = n;
+    e = &pool.e[pool.n++];
   }
   *base = e->base;
   *tag_base = e->tag;
   e->tag += nsteps + 2u;
   const unsigned slot = e->calls++ % RSM_TAB_RING;
-  *tab_host = e->tab_host + (size_t)slot * SPO_RS_MAX_REPLICAS;
+  *tab_host = e->tab_host + (size_t)slot * pool.lay.max_reps;
   *ev = e->ev[slot];
   // (an event that was never recorded is complete)
   return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
 }
 
-template <int KIN, bool L1P>
-int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
-  const size_t sh = RsLds<KIN, 2>::SIZE * sizeof(float);
-  static bool attr_done[SPO_MAX_DEVICES] = {};
+int rsm_release(RsmPool& pool, int dev, void* stream_or_null, int all) {
+  int freed = 0;
+  for (int i = 0; i < pool.n;) {
+    if (pool.e[i].dev == dev && (all || pool.e[i].stream == stream_or_null)) {
+      rsm_free(pool.e[i]);
+      pool.e[i] = pool.e[--pool.n];
+      pool.e[pool.n] = RsmEntry{};
+      ++freed;
+    } else ++i;
+  }
+  return freed;
+}
+
+// Launch helper of both replica-batched kernels (WGS workgroups per replica).
+template <typename K>
+int rs_multi_launch(K kernel, bool* attr_done, size_t sh, int wgs, const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   const int dslot = current_device_slot();
   if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_multi_kernel<KIN, L1P>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs_multi)");
     attr_done[dslot] = true;
   }
-  hipLaunchKernelGGL((ppo_update_rs_multi_kernel<KIN, L1P>), dim3(rs_multi_grid(n_replicas)), dim3(512), sh, st, table_dev, n_replicas);
+  hipLaunchKernelGGL(kernel, dim3(rs_multi_grid(n_replicas, wgs)), dim3(512), sh, st, table_dev, n_replicas);
   return 0;
+}
+
+template <int KIN, bool L1P>
+int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  return rs_multi_launch(&ppo_update_rs_multi_kernel<KIN, L1P, 2, 3>, attr_done, RsLds<KIN, 2>::SIZE * sizeof(float), RS_MULTI_WG, table_dev,
+                         n_replicas, st);
+}
+
+template <int KIN>
+int rs_critic_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  return rs_multi_launch(&ppo_update_rs_multi_kernel<KIN, false, 4, 2>, attr_done, RsLds<KIN, 2>::SIZE * sizeof(float), RS_CRITIC_MULTI_WG, table_dev,
+                         n_replicas, st);
+}
+
+int rs_counters_rw(const void* symbol, unsigned long long* out2_host, int reset) {
+  if (int rc = spo::hip_check(hipMemcpyFromSymbol(out2_host, symbol, 16), "hipMemcpyFromSymbol")) return rc;
+  if (reset) {
+    unsigned long long z[2] = {0, 0};
+    return spo::hip_check(hipMemcpyToSymbol(symbol, z, 16), "hipMemcpyToSymbol");
+  }
+  return 0;
+}
+
+int rs_block_map_query(int block, int n_replicas, int max_reps, int wgs, int* replica, int* wg) {
+  if (n_replicas < 1 || n_replicas > max_reps || block < 0 || block >= rs_multi_grid(n_replicas, wgs)) return 0;
+  int r = 0, w = 0;
+  const bool work = rs_multi_map(block, n_replicas, wgs, &r, &w);
+  if (work && replica) *replica = r;
+  if (work && wg) *wg = w;
+  return work ? 1 : 0;
+}
+
+int rs_force_safe() { const char* e = getenv("SPO_RS_SAFE"); return (e && *e && *e != '0') ? 1 : 0; }
+
+bool stream_is_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
 }
 }  // namespace
 
 int spo::rs_multi_scratch_release(int dev, void* stream_or_null, int all) {
   std::lock_guard<std::mutex> lk(g_rs_mu);
-  int freed = 0;
-  for (int i = 0; i < g_rsm_n;) {
-    if (g_rsm[i].dev == dev && (all || g_rsm[i].stream == stream_or_null)) {
-      rsm_free(g_rsm[i]);
-      g_rsm[i] = g_rsm[--g_rsm_n];
-      g_rsm[g_rsm_n] = RsmEntry{};
-      ++freed;
-    } else ++i;
-  }
-  return freed;
+  return rsm_release(g_rsm, dev, stream_or_null, all) + rsm_release(g_rsm_critic, dev, stream_or_null, all);
 }
 
 extern "C" int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas) {
@@ -1839,12 +1900,11 @@ extern "C" int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch
 }
 
 extern "C" int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
-  if (n_replicas < 1 || n_replicas > SPO_RS_MAX_REPLICAS || block < 0 || block >= rs_multi_grid(n_replicas)) return 0;
-  int r = 0, w = 0;
-  const bool work = rs_multi_map(block, n_replicas, &r, &w);
-  if (work && replica) *replica = r;
-  if (work && wg) *wg = w;
-  return work ? 1 : 0;
+  return rs_block_map_query(block, n_replicas, SPO_RS_MAX_REPLICAS, RS_MULTI_WG, replica, wg);
+}
+
+extern "C" int spo_rs_critic_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
+  return rs_block_map_query(block, n_replicas, SPO_RS_CRITIC_MAX_REPLICAS, RS_CRITIC_MULTI_WG, replica, wg);
 }
 
 extern "C" int spo_debug_clip_threshold(float max_grad_norm, float* thr_sq_out_host) {
@@ -1856,12 +1916,12 @@ extern "C" int spo_debug_clip_threshold(float max_grad_norm, float* thr_sq_out_h
 
 extern "C" int spo_debug_rs_multi_counters(unsigned long long* out2_host, int reset) {
   SPO_REQUIRE(out2_host, "rs_multi_counters: null pointer");
-  if (int rc = spo::hip_check(hipMemcpyFromSymbol(out2_host, HIP_SYMBOL(g_rs_multi_counters), 16), "hipMemcpyFromSymbol")) return rc;
-  if (reset) {
-    unsigned long long z[2] = {0, 0};
-    return spo::hip_check(hipMemcpyToSymbol(HIP_SYMBOL(g_rs_multi_counters), z, 16), "hipMemcpyToSymbol");
-  }
-  return 0;
+  return rs_counters_rw(HIP_SYMBOL(g_rs_multi_counters), out2_host, reset);
+}
+
+extern "C" int spo_debug_rs_critic_multi_counters(unsigned long long* out2_host, int reset) {
+  SPO_REQUIRE(out2_host, "rs_critic_multi_counters: null pointer");
+  return rs_counters_rw(HIP_SYMBOL(g_rs_critic_multi_counters), out2_host, reset);
 }
 
 extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host, int n_replicas, int64_t M, void* stream) {
@@ -1889,20 +1949,16 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
                   "update_iter_multi: replicas %d and %d share theta or sync_ws", q, r);
   }
   hipStream_t st = (hipStream_t)stream;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return spo::fail(-1, "update_iter_multi: the stream is under capture (the argument table is copied from host memory at "
-                           "every call: not a graph node)");
-  }
-  int force_safe;
-  { const char* e = getenv("SPO_RS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  if (stream_is_capturing(st))
+    return spo::fail(-1, "update_iter_multi: the stream is under capture (the argument table is copied from host memory at "
+                         "every call: not a graph node)");
+  const int force_safe = rs_force_safe();
   std::lock_guard<std::mutex> lk(g_rs_mu);                                 // (until the table's copy and its event are enqueued)
   char* base = nullptr;
   unsigned tag_base = 0;
   RsMultiEntry* tab = nullptr;
   hipEvent_t tab_ev = nullptr;
-  if (int rc = rsm_scratch(st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
+  if (int rc = rsm_scratch(g_rsm, st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
   int n_active = 0;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_update_replica& p = reps_host[r];
@@ -1910,8 +1966,8 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
     a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
     a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
     a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
-    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_Z_BYTES);
-    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_G_OFF + (size_t)r * RSM_G_STRIDE);
+    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_PPO.z_bytes);
+    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_PPO.g_off() + (size_t)r * RSM_G_STRIDE);
     a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
     a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
     a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
@@ -1923,12 +1979,12 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
     n_active += tab[r].active;
   }
   if (n_active == 0) return 0;
-  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_T_OFF);
+  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_PPO.t_off());
   if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(RsMultiEntry), hipMemcpyHostToDevice, st),
                               "hipMemcpyAsync(replica table)")) return rc;
   if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
-  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_Z_BYTES, st), "hipMemsetAsync(rs slots)")) return rc;
+  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_PPO.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : c0.obs_dim <= 64 ? 64 : 128;
   const bool l1p = rs_l1_pipe();                                           // (the form the single launch takes: batched == stand-alone bits)
   int rc = kin == 16 ? rs_multi_launch_k<16, false>(table_dev, n_replicas, st)
@@ -1937,5 +1993,84 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
                      : rs_multi_launch_k<128, false>(table_dev, n_replicas, st);
   if (rc) return rc;
   SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_multi");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- replica-batched critic fit
+extern "C" int spo_critic_fit_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas) {
+  if (n_replicas < 1 || n_replicas > SPO_RS_CRITIC_MAX_REPLICAS || batch < 65 || batch > 128) return 0;
+  return spo_update_rs_supported(obs_dim, act_dim, batch, 2) ? 1 : 0;
+}
+
+extern "C" int spo_critic_fit_iter_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "critic_fit_iter_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_RS_CRITIC_MAX_REPLICAS, "critic_fit_iter_multi: %d replicas outside [1, %d]",
+              n_replicas, SPO_RS_CRITIC_MAX_REPLICAS);
+  SPO_REQUIRE(M > 0, "critic_fit_iter_multi: bad sizes");
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  SPO_REQUIRE(spo_critic_fit_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, n_replicas),
+              "critic_fit_iter_multi: no replica-batched form for obs_dim %d, act_dim %d, batch %d (spo_critic_fit_multi_supported)",
+              c0.obs_dim, c0.act_dim, c0.batch);
+  const int64_t nsteps = (M + c0.batch - 1) / c0.batch;
+  SPO_REQUIRE(nsteps < (1ll << 30), "critic_fit_iter_multi: too many minibatch steps in one launch");
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_replica& p = reps_host[r];
+    SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.target_r && p.target_c && p.stale_sq_io && p.sync_ws &&
+                    ((p.perm && p.losses_out) || !p.active), "critic_fit_iter_multi: null pointer in replica %d", r);
+    SPO_REQUIRE(p.adam_step >= 0, "critic_fit_iter_multi: replica %d: negative adam_step", r);
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "critic_fit_iter_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
+                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+    for (int q = 0; q < r; ++q)
+      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws && reps_host[q].stale_sq_io != p.stale_sq_io,
+                  "critic_fit_iter_multi: replicas %d and %d share theta, sync_ws or stale_sq_io", q, r);
+  }
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) n_active += reps_host[r].active ? 1 : 0;
+  if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
+  hipStream_t st = (hipStream_t)stream;
+  if (stream_is_capturing(st))
+    return spo::fail(-1, "critic_fit_iter_multi: the stream is under capture (the argument table is copied from host memory at "
+                         "every call: not a graph node)");
+  const int force_safe = rs_force_safe();
+  std::lock_guard<std::mutex> lk(g_rs_mu);                                 // (until the table's copy and its event are enqueued)
+  char* base = nullptr;
+  unsigned tag_base = 0;
+  RsMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  if (int rc = rsm_scratch(g_rsm_critic, st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_replica& p = reps_host[r];
+    RsArgs a{};                                                            // (as rs_update_launch fills it for spo_critic_fit_iter)
+    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
+    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c;
+    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
+    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_CRITIC.z_bytes);
+    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_CRITIC.g_off() + (size_t)r * RSM_G_STRIDE);
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
+    a.tag_base = tag_base;
+    a.n_nets = 2; a.first_net = 0; a.stale_io = p.stale_sq_io; a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
+    a.clip_thr_sq = rs_clip_threshold(p.cfg.max_grad_norm);
+    tab[r].a = a;
+    tab[r].active = p.active ? 1 : 0;
+    // what spo_critic_fit_iter does to sync_ws at every call
+    if (p.active)
+      if (int rc = spo::hip_check(hipMemsetAsync(p.sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
+  }
+  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_CRITIC.t_off());
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(RsMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
+  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_CRITIC.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
+  const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : 64;
+  int rc = kin == 16 ? rs_critic_multi_launch_k<16>(table_dev, n_replicas, st)
+         : kin == 32 ? rs_critic_multi_launch_k<32>(table_dev, n_replicas, st)
+                     : rs_critic_multi_launch_k<64>(table_dev, n_replicas, st);
+  if (rc) return rc;
+  SPO_LAUNCH_CHECK("spo_critic_fit_iter_multi");
   return 0;
 }

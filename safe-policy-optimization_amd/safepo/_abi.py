@@ -32,6 +32,13 @@ class UpdateReplica(Structure):
                 ("perm", c_void_p), ("losses_out", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg), ("active", c_int)]
 
 
+class CriticFitReplica(Structure):
+    """spo_critic_fit_replica (include/safepo_hip.h): one run of a seed-batched critic-fit launch."""
+    _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step", c_int64), ("obs", c_void_p),
+                ("target_r", c_void_p), ("target_c", c_void_p), ("perm", c_void_p), ("losses_out", c_void_p),
+                ("stale_sq_io", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg), ("active", c_int)]
+
+
 class MaNet(Structure):
     """spo_ma_net (include/safepo_hip.h)."""
     _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_blocks", c_int32), ("out_dim", c_int32),
@@ -74,6 +81,7 @@ WIDE_ACTOR_CLIP, WIDE_ACTOR_SURR, WIDE_ACTOR_KLPEN = 0, 1, 2     # spo_wide_acto
 KLPEN_SUMS = 8                                     # include/safepo_hip.h SPO_KLPEN_SUMS (floats of spo_kl_penalty_grad's sums)
 GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GAE_PARTIAL_STRIDE (doubles per workgroup)
 RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS_MAX_REPLICAS
+RS_CRITIC_MAX_REPLICAS = 24                        # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -119,6 +127,11 @@ PROTOTYPES = {
     "spo_update_rs_multi_matches_single": (c_int, [c_int, c_int, c_int]),
     "spo_rs_multi_block_map": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "spo_debug_rs_multi_counters": (c_int, [P, c_int]),
+    "spo_critic_fit_iter_multi": (c_int, [POINTER(CriticFitReplica), c_int, c_int64, P]),
+    "spo_critic_fit_multi_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_critic_fit_multi_matches_single": (c_int, [c_int, c_int, c_int]),
+    "spo_rs_critic_multi_block_map": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_rs_critic_multi_counters": (c_int, [P, c_int]),
     "spo_debug_clip_threshold": (c_int, [c_float, POINTER(c_float)]),
     "spo_ppo_lag_update_iter_ks": (c_int, [P, P, P, c_int64] + [P] * 7 + [c_int64, POINTER(PpoCfg), P, P, P]),
     "spo_ppo_lag_grad_ks": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, P, P]),

@@ -1,5 +1,6 @@
 """Seed-batched PPO-Lagrangian: S independent runs (own seed, policy, buffer, optimiser state) on one GPU whose minibatch
 steps share ONE persistent launch (spo_ppo_lag_update_iter_multi, csrc/update_rs.hip): run r on its own six co-XCD workgroups.
+CPOEngineGroup does the same for the critic fit of the second-order scripts (spo_critic_fit_iter_multi: eight workgroups per run).
 Per run nothing changes -- the arithmetic of a step is the single launch's, bit for bit, and every run draws its random numbers
 from its own generator state (ReplicaRNG), so run r of a group is the stand-alone run with its seed.
 
@@ -65,7 +66,35 @@ class ReplicaRNG:
         return False
 
 
-class PPOLagEngineGroup:
+class _EngineGroup:
+    """What the groups below share: the runs' generator states and their error words."""
+
+    engines, rngs = (), None
+
+    def __len__(self):
+        return len(self.engines)
+
+    def rng(self, i: int):
+        """Context of run i's random-number state (a no-op context without rngs)."""
+        return self.rngs[i] if self.rngs is not None else contextlib.nullcontext()
+
+    def check_sync_error(self) -> None:
+        """The engine's check_sync_error per run (every run has its own error word); the message names the run."""
+        es = self.engines
+        if all(torch.is_tensor(getattr(e, "sync_ws", None)) for e in es):
+            codes = torch.stack([e.sync_ws[8] for e in es]).cpu().tolist()       # one read for all runs
+        else:
+            codes = [1] * len(es)
+        for i, e in enumerate(es):
+            if not codes[i]:
+                continue
+            try:
+                e.check_sync_error()
+            except _abi.SpoError as err:
+                raise _abi.SpoError(f"replica {i} of {len(es)}: {err}") from None
+
+
+class PPOLagEngineGroup(_EngineGroup):
     """S ordinary one-GPU PPOLagEngines of one shape (observations, actions, rows, minibatch size) on one device.
     `rngs`: one ReplicaRNG per engine -- the default shuffle of run i is then drawn under rngs[i]."""
 
@@ -91,13 +120,6 @@ class PPOLagEngineGroup:
         # (anything else that has PPOLagEngine's methods -- a recording stand-in in a test -- is stepped one by one)
         self._native = all(isinstance(e, PPOLagEngine) for e in engines)
         self.lib = _abi.load() if self._native else None
-
-    def __len__(self):
-        return len(self.engines)
-
-    def rng(self, i: int):
-        """Context of run i's random-number state (a no-op context without rngs)."""
-        return self.rngs[i] if self.rngs is not None else contextlib.nullcontext()
 
     # ------------------------------------------------------------------ one learning iteration of every active run
     def batched(self, cfgs=None) -> bool:
@@ -207,17 +229,113 @@ class PPOLagEngineGroup:
                          "losses": all_losses[i]})
         return outs
 
-    def check_sync_error(self) -> None:
-        """PPOLagEngine.check_sync_error per run (every run has its own error word); the message names the run."""
-        es = self.engines
-        if all(torch.is_tensor(getattr(e, "sync_ws", None)) for e in es):
-            codes = torch.stack([e.sync_ws[8] for e in es]).cpu().tolist()       # one read for all runs
-        else:
-            codes = [1] * len(es)
-        for i, e in enumerate(es):
-            if not codes[i]:
-                continue
-            try:
-                e.check_sync_error()
-            except _abi.SpoError as err:
-                raise _abi.SpoError(f"replica {i} of {len(es)}: {err}") from None
+
+class CPOEngineGroup(_EngineGroup):
+    """S one-GPU CPOEngines (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg) of one shape on one device whose critic fits share ONE
+    persistent launch per iteration (spo_critic_fit_iter_multi, csrc/update_rs.hip): run r on its own eight co-XCD workgroups
+    (2 critics x 4 row groups), each bit for bit its own spo_critic_fit_iter.  The full-batch actor updates already fill the
+    GPU and stay one run after the other.  `rngs`: one ReplicaRNG per engine -- run i's default shuffle is drawn under rngs[i]."""
+
+    def __init__(self, engines, rngs=None):
+        from safepo.single_agent.cpo import CPOEngine
+        engines = list(engines)
+        if not engines:
+            raise ValueError("CPOEngineGroup: no engines")
+        if len(engines) > _abi.RS_CRITIC_MAX_REPLICAS:
+            raise _abi.SpoError(f"CPOEngineGroup: {len(engines)} engines; at most {_abi.RS_CRITIC_MAX_REPLICAS} critic fits share a launch")
+        e0 = engines[0]
+        for i, e in enumerate(engines):
+            if isinstance(e, CPOEngine):
+                if type(e) is not CPOEngine:
+                    raise _abi.SpoError(f"CPOEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
+                                        "CPOEngine (hidden [64, 64], obs_dim <= 64, act_dim <= 16) can be grouped")
+                if e.comm.world_size != 1:
+                    raise _abi.SpoError("CPOEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
+            if (e.D, e.A, e.M) != (e0.D, e0.A, e0.M) or e.dev != e0.dev:
+                raise _abi.SpoError(f"CPOEngineGroup: engine {i} has obs / act / rows / device {e.D} / {e.A} / {e.M} / {e.dev}, "
+                                    f"engine 0 has {e0.D} / {e0.A} / {e0.M} / {e0.dev}")
+        if rngs is not None and len(rngs) != len(engines):
+            raise ValueError("CPOEngineGroup: one ReplicaRNG per engine")
+        self.engines, self.rngs = engines, rngs
+        # (anything else that has CPOEngine's critic_fit -- a recording stand-in in a test -- is fitted one by one)
+        self._native = all(isinstance(e, CPOEngine) for e in engines)
+        self.lib = _abi.load() if self._native else None
+
+    def batched(self, cfgs=None) -> bool:
+        """Does critic_fit_all run one launch per iteration?  Where the four-row-group row-split kernel is the stand-alone
+        form too (spo_critic_fit_multi_matches_single: the library's own routing answers; SPO_UPDATE_FORM < 3 says no), no
+        engine takes its two-replica split form (SPO_CPO_SPLIT=force) and all runs share the minibatch size."""
+        if not self._native:
+            return False
+        cfgs = cfgs or [e._cfg_struct() for e in self.engines]
+        c0 = cfgs[0]
+        if any(c.batch != c0.batch for c in cfgs):
+            return False
+        if not (self.lib.spo_critic_fit_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))
+                and self.lib.spo_critic_fit_multi_matches_single(c0.obs_dim, c0.act_dim, c0.batch)):
+            return False
+        return all(e._split_setup() is None for e in self.engines)
+
+    def fit_iter_all(self, perms, active=None):
+        """One critic-fit iteration (ceil(M / batch) minibatch steps) of every run i with active[i] in ONE launch; adam_step
+        advances per run.  Returns the losses [n_mb, 3] per run (columns 0, 1 are written; None for a run that sat out)."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        if len(perms) != S or len(active) != S:
+            raise ValueError("fit_iter_all: one perm and one active flag per engine")
+        cfgs = [e._cfg_struct() for e in self.engines]
+        e0 = self.engines[0]
+        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
+        reps = (_abi.CriticFitReplica * S)()
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            d = e.buffer.data
+            perm = perms[i] if active[i] else None
+            if perm is not None:
+                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            r = reps[i]
+            r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
+            r.obs, r.target_r, r.target_c = _abi.ptr(d["obs"]), _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"])
+            r.perm, r.losses_out, r.stale_sq_io = _abi.ptr(perm), _abi.ptr(losses[i]), _abi.ptr(e.stale_sq)
+            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
+        _abi.check(self.lib.spo_critic_fit_iter_multi(reps, S, e0.M, _abi.stream_ptr()), "spo_critic_fit_iter_multi")
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                e.adam_step += n_mb
+        return losses
+
+    def critic_fit_all(self, perm_fns=None):
+        """CPOEngine.critic_fit for every run: learning_iters iterations each (a run with fewer sits out the later launches),
+        every iteration's shuffle drawn per run -- under its ReplicaRNG by default -- before that iteration's launch, as the
+        stand-alone loop draws it.  Where not batched(): each engine's own critic_fit, one after the other -- the same results.
+        Returns the list of critic_fit()'s dicts."""
+        es, S = self.engines, len(self.engines)
+
+        def default_perm_fn(i):
+            def fn(it):
+                with self.rng(i):
+                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
+            return fn
+
+        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
+        if len(perm_fns) != S:
+            raise ValueError("critic_fit_all: one perm_fn (or None) per engine")
+        perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+        if not self.batched():
+            return [e.critic_fit(perm_fns[i]) for i, e in enumerate(es)]
+        n_its = [e.cfg["learning_iters"] for e in es]
+        all_losses = [[] for _ in range(S)]
+        for it in range(max(n_its)):
+            active = [it < n for n in n_its]
+            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
+            losses = self.fit_iter_all(perms, active)
+            for i in range(S):
+                if active[i]:
+                    all_losses[i].append(losses[i][:, :2])
+        self.check_sync_error()
+        outs = []
+        for ls in all_losses:
+            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
+            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
+        return outs

@@ -22,12 +22,80 @@ from safepo.common.lagrange import Lagrange
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.single_agent.cpo import _to_dev, make_engine
-from safepo.utils.config import isaac_gym_map, refuse_seed_batch
+from safepo.single_agent.cpo import _to_dev, make_engine, run_seed_batch
+from safepo.utils.config import critic_seed_batch, isaac_gym_map, seed_list
+
+
+def _actor_update(engine, logger, lagrange, comm, device, line_search: bool):
+    """The epoch's multiplier step and trust-region update, logged."""
+    ep_costs = dp_epoch_stat(comm, logger, "Metrics/EpCost", device)
+    lam = None
+    if lagrange is not None:
+        lagrange.update_lagrange_multiplier(ep_costs)
+        lam = lagrange.lagrangian_multiplier
+    engine.buffer.compute_gae(lam, comm)
+    M = engine.M
+    advantage = engine.buffer.adv_mix.reshape(M) if lam is not None else engine.buffer.data["adv_r"].reshape(M)
+    out = engine.trust_region_update(advantage, line_search, logger)
+    misc = {"Misc/Alpha": out["alpha"], "Misc/FinalStepNorm": out["final_step_norm"], "Misc/xHx": out["xHx"],
+            "Misc/gradient_norm": out["gradient_norm"], "Misc/H_inv_g": out["H_inv_g"],
+            "Loss/Loss_actor": out["loss_actor"], "Train/KL": out["kl"]}
+    if line_search:
+        misc["Misc/AcceptanceStep"] = out["acceptance_step"]
+    logger.store(**misc)
+    return out
+
+
+def _log_epoch(logger, args, engine, env, lagrange, line_search, epoch, t_rollout, t_update, t_total):
+    """The epoch's row of progress.csv."""
+    if not logger.logged:
+        logger.log_tabular("Metrics/EpRet")
+        logger.log_tabular("Metrics/EpCost")
+        logger.log_tabular("Metrics/EpLen")
+        logger.log_tabular("Train/Epoch", epoch + 1)
+        logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
+        logger.log_tabular("Train/KL")
+        if lagrange is not None:
+            logger.log_tabular("Train/LagragianMultiplier", lagrange.lagrangian_multiplier)
+        logger.log_tabular("Loss/Loss_reward_critic")
+        logger.log_tabular("Loss/Loss_cost_critic")
+        logger.log_tabular("Loss/Loss_actor")
+        logger.log_tabular("Time/Rollout", t_rollout)
+        logger.log_tabular("Time/Update", t_update)
+        logger.log_tabular("Time/Total", t_total)
+        d = engine.buffer.data
+        logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
+        logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
+        for k in ("Misc/Alpha", "Misc/FinalStepNorm", "Misc/xHx", "Misc/gradient_norm", "Misc/H_inv_g"):
+            logger.log_tabular(k)
+        if line_search:
+            logger.log_tabular("Misc/AcceptanceStep")
+        logger.dump_tabular()
+        if (epoch + 1) % 100 == 0 or epoch == 0:
+            logger.torch_save(itr=epoch)
+            logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
+    else:
+        for k in list(logger.epoch_dict):
+            logger.epoch_dict[k] = []
+
+
+def _new_lagrange(args):
+    return Lagrange(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init,
+                    lagrangian_multiplier_lr=args.lagrangian_multiplier_lr)
 
 
 def run(args, cfg_env, default_cfg: dict, line_search: bool, use_lagrange: bool):
-    refuse_seed_batch(args, "the second-order scripts")
+    if critic_seed_batch(args):
+        def make_extra(r):
+            r.lagrange = _new_lagrange(args) if use_lagrange else None
+
+        return run_seed_batch(
+            args, default_cfg, make_extra=make_extra,
+            rollout=lambda r: r.engine.rollout_epoch(r.env, r.obs, rms=r.rms),
+            actor_update=lambda r, epoch: _actor_update(r.engine, r.logger, r.lagrange, r.engine.comm, r.device, line_search),
+            log_epoch=lambda r, epoch, t_rollout, t_update, t_total: _log_epoch(r.logger, args, r.engine, r.env, r.lagrange, line_search,
+                                                                                epoch, t_rollout, t_update, t_total))
+    args.seed = seed_list(args)[0]      # (`--seeds s` alone is `--seed s`)
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -54,8 +122,7 @@ def run(args, cfg_env, default_cfg: dict, line_search: bool, use_lagrange: bool)
                           hidden_sizes=config["hidden_sizes"]).to(device)
     comm.broadcast_(policy.theta, 0)                       # identical replicas
     engine = make_engine(policy, n_local, local_steps_per_epoch, config, device, comm=comm)
-    lagrange = Lagrange(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init,
-                        lagrangian_multiplier_lr=args.lagrangian_multiplier_lr) if use_lagrange else None
+    lagrange = _new_lagrange(args) if use_lagrange else None
     dict_args = dict(vars(args))
     dict_args.update(config)
     is_root = comm.rank == 0
@@ -78,55 +145,14 @@ def run(args, cfg_env, default_cfg: dict, line_search: bool, use_lagrange: bool)
         rollout_end_time = time.time()
         eval_end_time = rollout_end_time
 
-        ep_costs = dp_epoch_stat(comm, logger, "Metrics/EpCost", device)
-        lam = None
-        if lagrange is not None:
-            lagrange.update_lagrange_multiplier(ep_costs)
-            lam = lagrange.lagrangian_multiplier
-        engine.buffer.compute_gae(lam, comm)
-        M = engine.M
-        advantage = engine.buffer.adv_mix.reshape(M) if lam is not None else engine.buffer.data["adv_r"].reshape(M)
-        out = engine.trust_region_update(advantage, line_search, logger)
-        misc = {"Misc/Alpha": out["alpha"], "Misc/FinalStepNorm": out["final_step_norm"], "Misc/xHx": out["xHx"],
-                "Misc/gradient_norm": out["gradient_norm"], "Misc/H_inv_g": out["H_inv_g"],
-                "Loss/Loss_actor": out["loss_actor"], "Train/KL": out["kl"]}
-        if line_search:
-            misc["Misc/AcceptanceStep"] = out["acceptance_step"]
-        logger.store(**misc)
+        out = _actor_update(engine, logger, lagrange, comm, device, line_search)
         fit = engine.critic_fit()
         engine.buffer.reset()
         logger.store(**{"Loss/Loss_reward_critic": fit["loss_r"], "Loss/Loss_cost_critic": fit["loss_c"]})
         torch.cuda.synchronize(device)
         update_end_time = time.time()
         outs.append(out)
-        if not logger.logged:
-            logger.log_tabular("Metrics/EpRet")
-            logger.log_tabular("Metrics/EpCost")
-            logger.log_tabular("Metrics/EpLen")
-            logger.log_tabular("Train/Epoch", epoch + 1)
-            logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
-            logger.log_tabular("Train/KL")
-            if lagrange is not None:
-                logger.log_tabular("Train/LagragianMultiplier", lagrange.lagrangian_multiplier)
-            logger.log_tabular("Loss/Loss_reward_critic")
-            logger.log_tabular("Loss/Loss_cost_critic")
-            logger.log_tabular("Loss/Loss_actor")
-            logger.log_tabular("Time/Rollout", rollout_end_time - rollout_start_time)
-            logger.log_tabular("Time/Update", update_end_time - eval_end_time)
-            logger.log_tabular("Time/Total", update_end_time - rollout_start_time)
-            d = engine.buffer.data
-            logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
-            logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
-            for k in ("Misc/Alpha", "Misc/FinalStepNorm", "Misc/xHx", "Misc/gradient_norm", "Misc/H_inv_g"):
-                logger.log_tabular(k)
-            if line_search:
-                logger.log_tabular("Misc/AcceptanceStep")
-            logger.dump_tabular()
-            if (epoch + 1) % 100 == 0 or epoch == 0:
-                logger.torch_save(itr=epoch)
-                logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
-        else:
-            for k in list(logger.epoch_dict):
-                logger.epoch_dict[k] = []
+        _log_epoch(logger, args, engine, env, lagrange, line_search, epoch, rollout_end_time - rollout_start_time,
+                   update_end_time - eval_end_time, update_end_time - rollout_start_time)
     logger.close()
     return {"policy": policy, "engine": engine, "outs": outs}

@@ -7,7 +7,9 @@ through `--device-id`, and `--workers` defaults to one per GPU.  `--workers 0` o
 `--seeds-per-run K` (not a reference flag; default 1 = one subprocess per seed, as the reference) puts up to K seeds of one
 (task, algorithm) into ONE subprocess through the scripts' `--seeds`: their updates share one persistent launch (ppo_lag,
 cppo_pid -- and ppo / pg -- on the persistent kernels' shapes); the other algorithms, and HumanoidVelocity, keep one subprocess
-per seed.
+per seed.  `--batch-second-order` (default off) lets cpo / pcpo / rcpo / trpo_lag / trpo / natural_pg join that grouping on
+the tasks whose observations fit the persistent CPO kernels (at most 24 seeds per subprocess), with `--batch-critic-fit True`
+on those commands: their critic fits share one persistent launch per iteration.
 """
 from __future__ import annotations
 
@@ -56,16 +58,32 @@ def parse_args(argv=None):
                    help="seeds of one (task, algorithm) per subprocess (--seeds of the scripts: ppo_lag, ppo, pg, cppo_pid; up to 32.  "
                         "The update's step takes 7.8-7.9 us for all seeds together up to 16 and 8.2 us at 32 where one seed alone takes "
                         "7.7 (60 / 8; profiles/seed_batch/step_times.txt): no knee up to 32, so the largest K the sweep has seeds for)")
+    p.add_argument("--batch-second-order", action="store_true",
+                   help="with --seeds-per-run: also group cpo / pcpo / rcpo / trpo_lag / trpo / natural_pg (at most 24 seeds per "
+                        "subprocess, --batch-critic-fit True on those commands; observations up to 64 values).  One "
+                        "critic-fit step of ALL seeds takes 9.9 / 11.2 / 14.2 us at 8 / 16 / 24 seeds against 9.8 us per seed one after "
+                        "the other (60 / 8; profiles/seed_batch_critic/step_times.txt): the time per seed falls up to the cap, so the "
+                        "largest K the sweep has seeds for.  Default off: these algorithms keep one subprocess per seed")
     return p.parse_args(argv)
 
 
 SEED_BATCHED_ALGOS = ("ppo_lag", "ppo", "pg", "cppo_pid")     # the scripts with a `--seeds` form (persistent-kernel shapes only)
+CRITIC_BATCHED_ALGOS = ("cpo", "pcpo", "rcpo", "trpo_lag", "trpo", "natural_pg")   # ... with --batch-critic-fit True
+CRITIC_BATCH_MAX = 24                                         # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
+WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
 
 
 def _takes_seeds(algo: str, task: str) -> bool:
     """Can `--seeds` carry several seeds for this (algorithm, task)?  HumanoidVelocity (376 / 17) runs on the wide-network
     kernels, which have no seed-batched form."""
     return algo in SEED_BATCHED_ALGOS and "Humanoid" not in task
+
+
+def _takes_critic_batch(algo: str, task: str) -> bool:
+    """Can `--seeds ... --batch-critic-fit True` carry several seeds for this (algorithm, task)?  The full-batch CPO kernels of
+    CPOEngine end at 64 observations: HumanoidVelocity and the Ant / Car / Doggo / Racecar navigation tasks run on WideCPOEngine."""
+    wide = "Humanoid" in task or ("Velocity" not in task and any(task.startswith(f"Safety{r}") for r in WIDE_OBS_NAV_ROBOTS))
+    return algo in CRITIC_BATCHED_ALGOS and not wide
 
 
 def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
@@ -83,11 +101,18 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                 total, per_epoch, envs = 100000000, 200000, 20
             for algo in args.algo:
                 # one command for the whole group where the script takes --seeds, else one per seed as ever
-                batched = len(group) > 1 and _takes_seeds(algo, task)
-                for run in ([group] if batched else [[s] for s in group]):
+                critic = getattr(args, "batch_second_order", False) and _takes_critic_batch(algo, task)
+                runs = [[s] for s in group]
+                if len(group) > 1 and _takes_seeds(algo, task):
+                    runs = [group]
+                elif len(group) > 1 and critic:
+                    runs = [group[i:i + CRITIC_BATCH_MAX] for i in range(0, len(group), CRITIC_BATCH_MAX)]
+                for run in runs:
+                    batched = len(run) > 1
                     commands.append(" ".join([
                         shlex.quote(sys.executable), shlex.quote(os.path.join(script_dir, f"{algo}.py")), "--task", shlex.quote(task),
-                        "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else []) + [
+                        "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else [])
+                        + (["--batch-critic-fit", "True"] if batched and critic else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
                         str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))

@@ -27,7 +27,7 @@ from safepo.common.env import make_sa_mujoco_env
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import isaac_gym_map, refuse_seed_batch, run_as_script
+from safepo.utils.config import critic_seed_batch, isaac_gym_map, run_as_script, seed_list
 
 STEP_FRACTION = 0.8
 CPO_SEARCHING_STEPS = 15
@@ -766,8 +766,79 @@ def _to_dev(x, dev):
     return torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x, dtype=torch.float32, device=dev).contiguous()
 
 
+def _rollout_steps(engine, env, obs, rms, device, local_steps_per_epoch, device_env):
+    """One epoch of collect steps (cpo.py:305-348) -> the observation the next epoch starts from."""
+    for steps in range(local_steps_per_epoch):
+        act = engine.collect_step(steps, obs, rms=rms)
+        action = act if device_env else act.detach().squeeze().cpu().numpy()
+        next_obs, reward, cost, terminated, truncated, info = env.step(action)
+        final_obs = None
+        if "final_observation" in info:
+            fo = info["final_observation"]
+            if not torch.is_tensor(fo):
+                fo = np.array([a if a is not None else np.zeros(obs.shape[-1]) for a in fo])
+            final_obs = _to_dev(fo, device)
+        next_obs = _to_dev(next_obs, device)
+        engine.post_step(steps, next_obs, _to_dev(reward, device), _to_dev(cost, device),
+                         _to_dev(terminated, device), _to_dev(truncated, device), final_obs, rms=rms)
+        obs = next_obs
+    return obs
+
+
+def _actor_update(engine, logger, args, comm, device, _update):
+    """The epoch's policy update (cpo.py:350-532), logged."""
+    engine.buffer.compute_gae(None, comm)
+    ep_costs = dp_epoch_stat(comm, logger, "Metrics/EpCost", device) - args.cost_limit
+    out = engine.policy_update(ep_costs, logger) if _update == "cpo" else engine.pcpo_update(ep_costs, logger)
+    logger.store(**{"Misc/Alpha": out["alpha"], "Misc/FinalStepNorm": out["final_step_norm"], "Misc/xHx": out["xHx"],
+                    "Misc/gradient_norm": out["gradient_norm"], "Misc/H_inv_g": out["H_inv_g"],
+                    "Misc/AcceptanceStep": out["acceptance_step"], "Loss/Loss_actor": out["loss_actor"],
+                    "Train/KL": out["kl"]})
+    return out
+
+
+def _log_epoch(logger, args, engine, env, epoch, t_rollout, t_update, t_total):
+    """The epoch's row of progress.csv."""
+    if not logger.logged:
+        logger.log_tabular("Metrics/EpRet")
+        logger.log_tabular("Metrics/EpCost")
+        logger.log_tabular("Metrics/EpLen")
+        logger.log_tabular("Train/Epoch", epoch + 1)
+        logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
+        logger.log_tabular("Train/KL")
+        logger.log_tabular("Loss/Loss_reward_critic")
+        logger.log_tabular("Loss/Loss_cost_critic")
+        logger.log_tabular("Loss/Loss_actor")
+        logger.log_tabular("Time/Rollout", t_rollout)
+        logger.log_tabular("Time/Update", t_update)
+        logger.log_tabular("Time/Total", t_total)
+        d = engine.buffer.data
+        logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
+        logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
+        logger.log_tabular("Misc/Alpha")
+        logger.log_tabular("Misc/FinalStepNorm")
+        logger.log_tabular("Misc/xHx")
+        logger.log_tabular("Misc/gradient_norm")
+        logger.log_tabular("Misc/H_inv_g")
+        logger.log_tabular("Misc/AcceptanceStep")
+        logger.dump_tabular()
+        if (epoch + 1) % 100 == 0 or epoch == 0:
+            logger.torch_save(itr=epoch)
+            logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
+    else:
+        for k in list(logger.epoch_dict):
+            logger.epoch_dict[k] = []
+
+
 def main(args, cfg_env=None, _update="cpo"):
-    refuse_seed_batch(args, "the second-order scripts")
+    if critic_seed_batch(args):
+        return run_seed_batch(
+            args, default_cfg,
+            rollout=lambda r: _rollout_steps(r.engine, r.env, r.obs, r.rms, r.device, r.local_steps_per_epoch, r.device_env),
+            actor_update=lambda r, epoch: _actor_update(r.engine, r.logger, args, r.engine.comm, r.device, _update),
+            log_epoch=lambda r, epoch, t_rollout, t_update, t_total: _log_epoch(r.logger, args, r.engine, r.env, epoch, t_rollout,
+                                                                                t_update, t_total))
+    args.seed = seed_list(args)[0]      # (`--seeds s` alone is `--seed s`)
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -810,70 +881,121 @@ def main(args, cfg_env=None, _update="cpo"):
     timings = []
     for epoch in range(epochs):
         rollout_start_time = time.time()
-        for steps in range(local_steps_per_epoch):
-            act = engine.collect_step(steps, obs, rms=rms)
-            action = act if device_env else act.detach().squeeze().cpu().numpy()
-            next_obs, reward, cost, terminated, truncated, info = env.step(action)
-            final_obs = None
-            if "final_observation" in info:
-                fo = info["final_observation"]
-                if not torch.is_tensor(fo):
-                    fo = np.array([a if a is not None else np.zeros(obs.shape[-1]) for a in fo])
-                final_obs = _to_dev(fo, device)
-            next_obs = _to_dev(next_obs, device)
-            engine.post_step(steps, next_obs, _to_dev(reward, device), _to_dev(cost, device),
-                             _to_dev(terminated, device), _to_dev(truncated, device), final_obs, rms=rms)
-            obs = next_obs
+        obs = _rollout_steps(engine, env, obs, rms, device, local_steps_per_epoch, device_env)
         engine.drain_episode_events(logger)
         torch.cuda.synchronize(device)
         rollout_end_time = time.time()
         eval_end_time = rollout_end_time
 
         # ---- update policy (cpo.py:350-532) and critics (:534-571)
-        engine.buffer.compute_gae(None, comm)
-        ep_costs = dp_epoch_stat(comm, logger, "Metrics/EpCost", device) - args.cost_limit
-        out = engine.policy_update(ep_costs, logger) if _update == "cpo" else engine.pcpo_update(ep_costs, logger)
-        logger.store(**{"Misc/Alpha": out["alpha"], "Misc/FinalStepNorm": out["final_step_norm"], "Misc/xHx": out["xHx"],
-                        "Misc/gradient_norm": out["gradient_norm"], "Misc/H_inv_g": out["H_inv_g"],
-                        "Misc/AcceptanceStep": out["acceptance_step"], "Loss/Loss_actor": out["loss_actor"],
-                        "Train/KL": out["kl"]})
+        _actor_update(engine, logger, args, comm, device, _update)
         fit = engine.critic_fit()
         engine.buffer.reset()
         logger.store(**{"Loss/Loss_reward_critic": fit["loss_r"], "Loss/Loss_cost_critic": fit["loss_c"]})
         torch.cuda.synchronize(device)
         update_end_time = time.time()
         timings.append((rollout_end_time - rollout_start_time, update_end_time - eval_end_time))
-        if not logger.logged:
-            logger.log_tabular("Metrics/EpRet")
-            logger.log_tabular("Metrics/EpCost")
-            logger.log_tabular("Metrics/EpLen")
-            logger.log_tabular("Train/Epoch", epoch + 1)
-            logger.log_tabular("Train/TotalSteps", (epoch + 1) * args.steps_per_epoch)
-            logger.log_tabular("Train/KL")
-            logger.log_tabular("Loss/Loss_reward_critic")
-            logger.log_tabular("Loss/Loss_cost_critic")
-            logger.log_tabular("Loss/Loss_actor")
-            logger.log_tabular("Time/Rollout", rollout_end_time - rollout_start_time)
-            logger.log_tabular("Time/Update", update_end_time - eval_end_time)
-            logger.log_tabular("Time/Total", update_end_time - rollout_start_time)
-            d = engine.buffer.data
-            logger.log_tabular("Value/RewardAdv", d["adv_r"].mean().item())
-            logger.log_tabular("Value/CostAdv", d["adv_c"].mean().item())
-            logger.log_tabular("Misc/Alpha")
-            logger.log_tabular("Misc/FinalStepNorm")
-            logger.log_tabular("Misc/xHx")
-            logger.log_tabular("Misc/gradient_norm")
-            logger.log_tabular("Misc/H_inv_g")
-            logger.log_tabular("Misc/AcceptanceStep")
-            logger.dump_tabular()
-            if (epoch + 1) % 100 == 0 or epoch == 0:
-                logger.torch_save(itr=epoch)
-                logger.save_state(state_dict={"Normalizer": getattr(env, "obs_rms", None)}, itr=epoch)
-        else:
-            for k in list(logger.epoch_dict):
-                logger.epoch_dict[k] = []
+        _log_epoch(logger, args, engine, env, epoch, rollout_end_time - rollout_start_time, update_end_time - eval_end_time,
+                   update_end_time - rollout_start_time)
     logger.close()
     return {"timings": timings, "policy": policy, "engine": engine}
+
+
+class _SeedRun:
+    """One run of a seed-batched process: what main() holds in local variables, per seed."""
+
+
+def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, make_extra=None):
+    """`--seeds s0 s1 ... --batch-critic-fit True` of the second-order scripts (this one, pcpo, and _second_order.run's four):
+    several seeds in one process on one GPU.  Every seed has its own env, policy, engine, multiplier (make_extra) and logger (in
+    the log directory its own `--seed` run would write) and draws every random number from its own generator state
+    (ReplicaRNG), in the stand-alone order, so each is the stand-alone run of its seed.  Rollout, GAE and the full-batch actor
+    update -- kernels that fill the GPU already -- run seed by seed (`rollout(r)` -> next observation, `actor_update(r, epoch)`);
+    the critic fits of all seeds run through CPOEngineGroup, one launch per iteration.  The Time/ columns hold the wall time of
+    the phase for ALL seeds of the process."""
+    from safepo.common.engine_group import CPOEngineGroup, ReplicaRNG
+    seeds = seed_list(args)
+    if len(set(seeds)) != len(seeds):
+        raise SystemExit(f"--seeds {seeds}: the same seed twice")
+    if len(seeds) > _abi.RS_CRITIC_MAX_REPLICAS:
+        raise SystemExit(f"--seeds: at most {_abi.RS_CRITIC_MAX_REPLICAS} seeds share the critic fit's launch, got {len(seeds)}")
+    if args.device == "cpu":
+        raise RuntimeError("this build runs the CPO hot path on a ROCm GPU only (--device cuda); no CPU fallback")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--seeds with more than one seed does not combine with torchrun (data-parallel runs): one GPU per process")
+    device = torch.device(f"cuda:{args.device_id}")
+    torch.cuda.set_device(device)
+    if args.task in isaac_gym_map:
+        raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
+    config = dict(default_cfg)
+    config.update(getattr(args, "cfg_override", None) or {})
+    log_dirs = getattr(args, "log_dirs", None) or [os.path.join(args.log_dir, "-".join(["seed", str(s).zfill(3)])) for s in seeds]
+    if len(log_dirs) != len(seeds):
+        raise ValueError("args.log_dirs: one directory per seed")
+    env_kwargs = getattr(args, "env_kwargs", None) or {}
+    steps_per_epoch = config.get("steps_per_epoch", args.steps_per_epoch)
+    total_steps = config.get("total_steps", args.total_steps)
+    local_steps_per_epoch = steps_per_epoch // args.num_envs
+    epochs = total_steps // steps_per_epoch
+
+    runs = []
+    for seed, log_dir in zip(seeds, log_dirs):
+        r = _SeedRun()
+        r.seed, r.rng, r.device, r.local_steps_per_epoch = seed, ReplicaRNG(seed, device), device, local_steps_per_epoch
+        with r.rng:                                   # the order of main(): env, policy, engine, multiplier, logger, reset
+            r.env, obs_space, act_space = make_sa_mujoco_env(num_envs=args.num_envs, env_id=args.task, seed=seed, device=device,
+                                                             **env_kwargs)
+            r.device_env = getattr(r.env, "is_device_env", False)
+            r.policy = ActorVCritic(obs_dim=obs_space.shape[0], act_dim=act_space.shape[0],
+                                    hidden_sizes=config["hidden_sizes"]).to(device)
+            if not r.policy.kernels_supported("cpo"):
+                raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "
+                                 f"64, act_dim <= 16); {args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network "
+                                 "kernels: one process per seed")
+            r.engine = CPOEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
+            if make_extra is not None:
+                make_extra(r)
+            dict_args = dict(vars(args))
+            dict_args.update(config)
+            dict_args.update(seed=seed, log_dir=log_dir)          # (what the stand-alone run of this seed records)
+            r.logger = EpochLogger(log_dir=log_dir, seed=str(seed), verbose=True)
+            r.logger.save_config(dict_args)
+            r.logger.setup_torch_saver(r.policy.actor)
+            r.logger.log("Start with training.")
+            r.rms = r.env.fuse_normalize(True) if hasattr(r.env, "fuse_normalize") else None
+            obs, _ = r.env.reset()
+            r.obs = _to_dev(obs, device)
+        runs.append(r)
+    group = CPOEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs])
+
+    timings, outs = [], []
+    for epoch in range(epochs):
+        rollout_start_time = time.time()
+        for r in runs:
+            with r.rng:
+                r.obs = rollout(r)
+            r.engine.drain_episode_events(r.logger)
+        torch.cuda.synchronize(device)
+        rollout_end_time = time.time()
+        epoch_outs = []
+        for r in runs:
+            with r.rng:
+                epoch_outs.append(actor_update(r, epoch))
+        fits = group.critic_fit_all()                  # (the shuffles are drawn under the runs' generator states)
+        for r, fit in zip(runs, fits):
+            r.engine.buffer.reset()
+            r.logger.store(**{"Loss/Loss_reward_critic": fit["loss_r"], "Loss/Loss_cost_critic": fit["loss_c"]})
+        torch.cuda.synchronize(device)
+        update_end_time = time.time()
+        timings.append((rollout_end_time - rollout_start_time, update_end_time - rollout_end_time))
+        outs.append(epoch_outs)
+        for r in runs:
+            log_epoch(r, epoch, rollout_end_time - rollout_start_time, update_end_time - rollout_end_time,
+                      update_end_time - rollout_start_time)
+    for r in runs:
+        r.logger.close()
+    return {"timings": timings, "policies": [r.policy for r in runs], "engines": [r.engine for r in runs], "group": group,
+            "policy": runs[0].policy, "engine": runs[0].engine, "outs": outs}
 
 
 if __name__ == "__main__":

@@ -62,11 +62,30 @@ def seed_list(args) -> list:
     return [int(s) for s in seeds] if seeds else [int(args.seed)]
 
 
-def refuse_seed_batch(args, what: str) -> None:
+def refuse_seed_batch(args, what: str, hint: str = "") -> None:
     """For the scripts without a seed-batched form: more than one seed is an error, not a silent single run."""
     if len(seed_list(args)) > 1:
         raise SystemExit(f"--seeds with more than one seed is not available for {what}: the seed-batched update exists for the "
-                         "PPO-Lagrangian family (ppo_lag, ppo, pg, cppo_pid) on the persistent kernels, one GPU; run one process per seed")
+                         "PPO-Lagrangian family (ppo_lag, ppo, pg, cppo_pid) on the persistent kernels, one GPU; run one process per seed"
+                         + hint)
+
+
+def critic_seed_batch(args) -> bool:
+    """The second-order scripts (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg): several seeds run in one process only with
+    --batch-critic-fit True (their critic fits then share one launch per iteration); without it they are refused as ever."""
+    if len(seed_list(args)) <= 1:
+        return False
+    if not getattr(args, "batch_critic_fit", False):
+        refuse_seed_batch(args, "the second-order scripts",
+                          ".  (Opt in with --batch-critic-fit True: the seeds' critic fits then share one persistent launch.)")
+    return True
+
+
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_critic/step_times.txt)
+CRITIC_BATCH_FIGURES = ("Measured at 60 / 8, 4096 x 128 rows, batch 128: one critic-fit step of ALL seeds takes 9.9 / 11.2 / 14.2 us at 8 / 16 / "
+                        "24 seeds against 9.8 us per seed one after the other (7.9 x / 13.9 x / 16.5 x the aggregate step rate; one seed alone: "
+                        "9.90 against 9.76 us, which is why one seed stays `--seed`); cpo's second epoch with 8 seeds: Time/Update 0.56 s "
+                        "against 3.35 s (profiles/seed_batch_critic/step_times.txt).")
 
 
 def single_agent_args(argv=None):
@@ -78,6 +97,11 @@ def single_agent_args(argv=None):
                              "the run `--seed` of that seed would be, their updates sharing one persistent launch (up to 32 seeds; "
                              "run r is placed on XCD r mod 8; one minibatch step of ALL seeds takes 7.8-7.9 us up to 16 seeds and 8.2 us at 32 "
                              "against 7.7 us for one seed alone at 60 / 8, profiles/seed_batch/step_times.txt).  Default: [--seed], the ordinary single run")
+    parser.add_argument("--batch-critic-fit", type=_bool, default=False,
+                        help="second-order scripts (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg) with --seeds: run the seeds in one "
+                             "process, their critic fits sharing one persistent launch per iteration (up to 24 seeds, eight workgroups "
+                             "each, run r on XCD r mod 8; hidden [64, 64], obs_dim <= 64), each seed the run its `--seed` would be.  "
+                             + CRITIC_BATCH_FIGURES + "  Default False: several seeds are refused for these scripts")
     args = parser.parse_args(argv)
     if args.task in isaac_gym_map:
         raise Exception("Please install isaacgym to run Isaac Gym tasks!")
