@@ -438,6 +438,58 @@ int spo_update_iter_ex(float* theta, float* adam_m, float* adam_v, int64_t adam_
                        const spo_ppo_cfg* cfg_host, int actor_loss, const float* old_mean, const float* old_std,
                        float kl_bound, float pg_coef, int actor_only, float* losses_out, void* sync_ws, void* stream);
 
+/* Seed-batched spo_update_iter_ex (FOCOPS, both stages of CUP): S INDEPENDENT runs (own parameters, optimiser state and clocks,
+ * buffers, shuffle, old distribution, kl_bound, pg_coef, cfg scalars) take the minibatch steps of one learning iteration in ONE
+ * persistent launch of the four-wave kernel, every run on workgroups of its own -- one per network: three, or one with actor_only
+ * -- of one XCD; run r sits on XCD r mod 8, runs r, r + 8, ... share one (at most 32 runs: 96 working blocks of one CU each, 12
+ * per XCD).  The step is the single launch's, unchanged; per run the result equals spo_update_iter_ex bit for bit wherever that
+ * call runs the four-wave kernel itself (spo_update_ex_multi_matches_single).  Every run has its own clip-norm granules (in a
+ * block the library owns, ~16 KB per (device, stream) with the argument table, zeroed by one memset per call; allocated at the
+ * first call together with a pinned host ring of argument tables, never under stream capture; freed by
+ * spo_update_scratch_release) and its own error word, the int at byte 64 of ITS sync_ws; nothing else of sync_ws is touched.  A
+ * run with active == 0 is skipped: nothing of it is read or written.  The call copies its argument table from host memory, so it
+ * is not capturable and is refused under stream capture. */
+#define SPO_UPDATE_EX_MAX_REPLICAS 32
+typedef struct {
+  float *theta, *adam_m, *adam_v;
+  int64_t adam_step_critics, adam_step_actor;   /* the run's two optimiser clocks (spo_update_iter_ex) */
+  const float *obs, *act, *logp_old, *target_r, *target_c, *adv;   /* (the targets may be NULL with actor_only) */
+  const int32_t* perm;          /* (perm and losses_out may be NULL in a run with active == 0) */
+  const float *old_mean, *old_std;              /* (may be NULL with SPO_ACTOR_LOSS_CLIP) */
+  float kl_bound, pg_coef;
+  float* losses_out;            /* [num_minibatches][3]; with actor_only only column 2 is written */
+  void* sync_ws;                /* >= 72 bytes; only the error word at byte 64 is used */
+  spo_ppo_cfg cfg;              /* obs_dim, act_dim, batch equal over the runs; the scalars are the run's own */
+  int active;
+} spo_update_ex_replica;
+
+/* One learning iteration (ceil(M / batch) steps) for every active run of reps_host[n_replicas] (a HOST array); actor_loss and
+ * actor_only hold for the whole launch.  Checked on the host before anything is enqueued: 1 <= n_replicas <=
+ * SPO_UPDATE_EX_MAX_REPLICAS, equal obs_dim / act_dim / batch, the null pointers spo_update_iter_ex checks, the KL-penalty loss
+ * with batch > 64, two runs sharing theta or sync_ws, a stream under capture.  All runs inactive: returns 0 with nothing enqueued.
+ * Does not read SPO_UPDATE_FORM: the caller decides whether to batch (spo_update_ex_multi_matches_single). */
+int spo_update_iter_ex_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss, int actor_only,
+                             void* stream);
+
+/* 1 for the shapes spo_update_iter_ex accepts (1 <= obs_dim <= SPO_MAX_OBS, 1 <= act_dim <= SPO_MAX_ACT, batch >= 1, and
+ * batch <= 64 with the KL-penalty loss) and 1 <= n_replicas <= SPO_UPDATE_EX_MAX_REPLICAS. */
+int spo_update_ex_multi_supported(int obs_dim, int act_dim, int batch, int actor_loss, int n_replicas);
+
+/* 1 where spo_update_iter_ex would itself run this shape on the four-wave kernel under this process's routing, so that batching
+ * is bit-for-bit neutral: always with the KL-penalty loss; with the clipped surrogate only where the main + helper kernel does
+ * not take the launch (obs_dim > 64, or batch > 64, or SPO_UPDATE_FORM < 2; read once per process). */
+int spo_update_ex_multi_matches_single(int obs_dim, int act_dim, int batch, int actor_loss);
+
+/* The launch's block -> (run, workgroup) mapping, the function the kernel itself uses (testable without a GPU): with wgs = 1
+ * (actor_only) or 3 workgroups per run the grid has 8 * wgs * ceil(n_replicas / 8) blocks; block b has XCD label b & 7 and serves
+ * run 8 * ((b >> 3) / wgs) + (b & 7) as workgroup (b >> 3) % wgs.  Returns 1 and fills replica / wg, or 0 for a block without
+ * work (run >= n_replicas, block outside the grid, or n_replicas outside [1, SPO_UPDATE_EX_MAX_REPLICAS]). */
+int spo_update_ex_multi_block_map(int block, int n_replicas, int actor_only, int* replica, int* wg);
+
+/* Measurement aid: {seed-batched launches enqueued, runs that took part in them} since the last reset (out2_host, host array).
+ * Counted on the host when a launch is enqueued: no device access. */
+int spo_debug_update_ex_multi_counters(unsigned long long* out2_host, int reset);
+
 /* ---- Data-parallel FOCOPS / CUP: the split form of spo_update_iter_ex (kernel / all-reduce / optimiser per minibatch step).
  * The KL-penalty loss couples every row of a minibatch through F = mean_i(ind_i) (focops.py:326-337: a [B] tensor minus a [B,1]
  * tensor, the mean of a BxB matrix).  Its gradient is linear in F: g_actor = g_KL + F * g_PG with

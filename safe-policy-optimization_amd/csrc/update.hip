@@ -15,6 +15,7 @@
 // Wave w owns batch columns [16w,16w+16) in forward/backward (transposed chaining, mlp_mfma.h) and
 // rows [16w,16w+16) of every weight-gradient tile (reduction over the 64 batch columns staged
 // through LDS as [feature][batch]).
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -1403,6 +1404,23 @@ template <int KIN, bool PERSIST, bool PROF = false, int AMODE = 0, int XR = 0>
 __global__ __launch_bounds__(256, 1) void ppo_update_kernel(UpdArgs a) {
   if (PERSIST && (blockIdx.x & 7)) return;                     // placement hint, see ppo_update_body
   ppo_update_body<KIN, PERSIST, PROF, AMODE, XR>(a, PERSIST ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+}
+
+// Seed-batched launch of the persistent four-wave step (spo_update_iter_ex_multi): S independent runs (own parameters, optimiser
+// state, buffers, scalars) take the minibatch steps of one learning iteration in ONE launch, run r on its own `wgs` workgroups
+// (one per network: 3, or 1 for the actor alone) of XCD r mod 8 (rs_multi_map, update_rs.h).  The step is ppo_update_body's,
+// unchanged: the body's only exchange is the joint clip-norm granule, and every run's a.slots points at granules of its own (a
+// block the library owns), its a.err at its own error word.  One run's arguments as the kernel reads them from the device table
+// (32 of them do not fit the kernel-argument segment):
+struct UpdMultiEntry { UpdArgs a; int active; };
+
+template <int KIN, int AMODE>
+__global__ __launch_bounds__(256, 1) void ppo_update_multi_kernel(const UpdMultiEntry* __restrict__ table, int n_replicas, int wgs) {
+  int rep, wg;
+  if (!rs_multi_map((int)blockIdx.x, n_replicas, wgs, &rep, &wg)) return;
+  if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the replica)
+  const UpdArgs a = table[rep].a;                // uniform address: scalar loads, once; fields the body never reads are not loaded
+  ppo_update_body<KIN, true, false, AMODE, 0>(a, wg);
 }
 
 // One-grid split form (critic fit at batch 128 on one GPU): BOTH "ranks" of a two-way split of the minibatch live in ONE
@@ -3006,6 +3024,77 @@ int split_local_release(int dev, void* stream_or_null, int all) {
   return freed;
 }
 
+// Scratch of the seed-batched four-wave launch (spo_update_iter_ex_multi), one block per (device, stream), allocated on first use
+// (never under capture) and kept: [run] clip-norm granules [2][4] on a 128-byte line of their own -- contiguous, so ONE
+// hipMemsetAsync zeroes the first n_replicas of them per launch (the tags restart at 1) -- then the argument table.  The table
+// leaves the host from pinned memory: EXM_TAB_RING tables per entry, used in turn, each with an event recorded behind its copy --
+// a table is rewritten only once the copy that read it last has completed.
+constexpr size_t EXM_G_STRIDE = 128;
+constexpr size_t EXM_T_OFF = (size_t)SPO_UPDATE_EX_MAX_REPLICAS * EXM_G_STRIDE;
+constexpr size_t EXM_BYTES = EXM_T_OFF + (size_t)SPO_UPDATE_EX_MAX_REPLICAS * sizeof(UpdMultiEntry);
+constexpr int EXM_TAB_RING = 4, EXM_SCRATCH_MAX = 16;
+struct ExmEntry { int dev; void* stream; char* base; UpdMultiEntry* tab_host; hipEvent_t ev[EXM_TAB_RING]; unsigned calls; };
+ExmEntry g_exm[EXM_SCRATCH_MAX] = {};
+int g_exm_n = 0;
+std::mutex g_exm_mu;
+std::atomic<unsigned long long> g_exm_counters[2];       // {launches enqueued, runs that took part}
+
+void exm_free(ExmEntry& e) {
+  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched update scratch)");
+  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(replica table)");
+  for (int i = 0; i < EXM_TAB_RING; ++i)
+    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(replica table)");
+  e = ExmEntry{};
+}
+
+// The caller holds g_exm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot).
+int exm_scratch(hipStream_t st, char** base, UpdMultiEntry** tab_host, hipEvent_t* ev) {
+  const int dev = current_device_slot();
+  ExmEntry* e = nullptr;
+  for (int i = 0; i < g_exm_n; ++i)
+    if (g_exm[i].dev == dev && g_exm[i].stream == (void*)st) e = &g_exm[i];
+  if (!e) {
+    if (g_exm_n == EXM_SCRATCH_MAX)
+      return spo::fail(-1, "update_iter_ex_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                           "spo_update_scratch_release(stream) for streams that are gone", EXM_SCRATCH_MAX);
+    ExmEntry n{};
+    n.dev = dev; n.stream = (void*)st;
+    void* p = nullptr;
+    if (int rc = spo::hip_check(hipMalloc(&p, EXM_BYTES), "hipMalloc(seed-batched update scratch)")) return rc;
+    n.base = static_cast<char*>(p);
+    void* h = nullptr;
+    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)EXM_TAB_RING * SPO_UPDATE_EX_MAX_REPLICAS * sizeof(UpdMultiEntry),
+                                              hipHostMallocDefault), "hipHostMalloc(replica table)")) { exm_free(n); return rc; }
+    n.tab_host = static_cast<UpdMultiEntry*>(h);
+    for (int i = 0; i < EXM_TAB_RING; ++i)
+      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(replica table)")) {
+        exm_free(n); return rc;
+      }
+    g_exm[g_exm_n] = n;
+    e = &g_exm[g_exm_n++];
+  }
+  *base = e->base;
+  const unsigned slot = e->calls++ % EXM_TAB_RING;
+  *tab_host = e->tab_host + (size_t)slot * SPO_UPDATE_EX_MAX_REPLICAS;
+  *ev = e->ev[slot];
+  // (an event that was never recorded is complete)
+  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
+}
+
+int exm_release(int dev, void* stream_or_null, int all) {
+  std::lock_guard<std::mutex> lk(g_exm_mu);
+  int freed = 0;
+  for (int i = 0; i < g_exm_n;) {
+    if (g_exm[i].dev == dev && (all || g_exm[i].stream == stream_or_null)) {
+      exm_free(g_exm[i]);
+      g_exm[i] = g_exm[--g_exm_n];
+      g_exm[g_exm_n] = ExmEntry{};
+      ++freed;
+    } else ++i;
+  }
+  return freed;
+}
+
 }  // namespace
 // Releases the scratch block of (current device, stream) -- or of every stream of the current device when stream_or_null is
 // NULL and all != 0.  The block is keyed by the raw stream handle, so a process that keeps creating and destroying streams
@@ -3026,6 +3115,7 @@ extern "C" int spo_update_scratch_release(void* stream_or_null, int all) {
   freed += spo::ks_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_multi_scratch_release(dev, stream_or_null, all);
+  freed += exm_release(dev, stream_or_null, all);
   return freed;
 }
 namespace {
@@ -3077,10 +3167,14 @@ int launch_update_h(const UpdArgs& a_in, int blocks, hipStream_t st) {
   return 0;
 }
 
+// Does the main + helper kernel take a persistent clipped-surrogate launch without an in-kernel exchange (launch_update below;
+// spo_update_ex_multi_matches_single answers from it)?
+inline bool h_form_takes(int obs_dim, int batch) { return pick_kin(obs_dim) <= 64 && batch <= 64 && update_form() >= 2; }
+
 template <bool PERSIST, int AMODE = 0, int XR = 0>
 int launch_update(const UpdArgs& a, int blocks, hipStream_t st) {
   const int kin = pick_kin(a.cfg.obs_dim);
-  if (PERSIST && AMODE == 0 && XR == 0 && kin <= 64 && a.cfg.batch <= 64 && update_form() >= 2) {
+  if (PERSIST && AMODE == 0 && XR == 0 && h_form_takes(a.cfg.obs_dim, a.cfg.batch)) {
     if (a.prof && kin == 64) return launch_update_h<64, true>(a, blocks, st);
     if (kin == 16) return launch_update_h<16>(a, blocks, st);
     if (kin == 32) return launch_update_h<32>(a, blocks, st);
@@ -3111,6 +3205,31 @@ int launch_update(const UpdArgs& a, int blocks, hipStream_t st) {
   if (kin == 16) SPO_LAUNCH(16) else if (kin == 32) SPO_LAUNCH(32) else if (kin == 64) SPO_LAUNCH(64) else SPO_LAUNCH(128)
 #undef SPO_LAUNCH
   return 0;
+}
+
+template <int K, int AMODE>
+int launch_update_multi_k(const UpdMultiEntry* table_dev, int n_replicas, int wgs, hipStream_t st) {
+  const size_t sh = UpdLds<K>::SIZE * sizeof(float);
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  const int dslot = current_device_slot();
+  if (!attr_done[dslot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_multi_kernel<K, AMODE>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_multi)");
+    attr_done[dslot] = true;
+  }
+  hipLaunchKernelGGL((ppo_update_multi_kernel<K, AMODE>), dim3(rs_multi_grid(n_replicas, wgs)), dim3(256), sh, st, table_dev, n_replicas,
+                     wgs);
+  return 0;
+}
+
+template <int AMODE>
+int launch_update_multi(int obs_dim, const UpdMultiEntry* table_dev, int n_replicas, int wgs, hipStream_t st) {
+  const int kin = pick_kin(obs_dim);
+  return kin == 16 ? launch_update_multi_k<16, AMODE>(table_dev, n_replicas, wgs, st)
+       : kin == 32 ? launch_update_multi_k<32, AMODE>(table_dev, n_replicas, wgs, st)
+       : kin == 64 ? launch_update_multi_k<64, AMODE>(table_dev, n_replicas, wgs, st)
+                   : launch_update_multi_k<128, AMODE>(table_dev, n_replicas, wgs, st);
 }
 
 int check_cfg(const spo_ppo_cfg* c) {
@@ -3237,6 +3356,113 @@ extern "C" int spo_update_iter_ex(float* theta, float* adam_m, float* adam_v, in
     if (int rc = launch_update<true, 0>(a, a.n_nets, st)) return rc;
   }
   SPO_LAUNCH_CHECK("spo_update_iter_ex");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- seed-batched spo_update_iter_ex
+extern "C" int spo_update_ex_multi_supported(int obs_dim, int act_dim, int batch, int actor_loss, int n_replicas) {
+  if (n_replicas < 1 || n_replicas > SPO_UPDATE_EX_MAX_REPLICAS) return 0;
+  if (obs_dim < 1 || obs_dim > SPO_MAX_OBS || act_dim < 1 || act_dim > SPO_MAX_ACT || batch < 1) return 0;
+  if (actor_loss == SPO_ACTOR_LOSS_KL_PENALTY) return batch <= 64 ? 1 : 0;
+  return actor_loss == SPO_ACTOR_LOSS_CLIP ? 1 : 0;
+}
+
+extern "C" int spo_update_ex_multi_matches_single(int obs_dim, int act_dim, int batch, int actor_loss) {
+  if (!spo_update_ex_multi_supported(obs_dim, act_dim, batch, actor_loss, 1)) return 0;
+  // launch_update<true, 1> always ends on the four-wave kernel; launch_update<true, 0> only where the main + helper form does not apply
+  return (actor_loss == SPO_ACTOR_LOSS_KL_PENALTY || !h_form_takes(obs_dim, batch)) ? 1 : 0;
+}
+
+extern "C" int spo_update_ex_multi_block_map(int block, int n_replicas, int actor_only, int* replica, int* wg) {
+  const int wgs = actor_only ? 1 : 3;
+  if (n_replicas < 1 || n_replicas > SPO_UPDATE_EX_MAX_REPLICAS || block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
+  int r = 0, w = 0;
+  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
+  if (work && replica) *replica = r;
+  if (work && wg) *wg = w;
+  return work ? 1 : 0;
+}
+
+extern "C" int spo_debug_update_ex_multi_counters(unsigned long long* out2_host, int reset) {
+  SPO_REQUIRE(out2_host, "update_ex_multi_counters: null pointer");
+  for (int i = 0; i < 2; ++i) out2_host[i] = reset ? g_exm_counters[i].exchange(0ull) : g_exm_counters[i].load();
+  return 0;
+}
+
+extern "C" int spo_update_iter_ex_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss,
+                                        int actor_only, void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "update_iter_ex_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_UPDATE_EX_MAX_REPLICAS, "update_iter_ex_multi: %d replicas outside [1, %d]",
+              n_replicas, SPO_UPDATE_EX_MAX_REPLICAS);
+  SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || actor_loss == SPO_ACTOR_LOSS_KL_PENALTY,
+              "update_iter_ex_multi: unknown actor_loss %d", actor_loss);
+  SPO_REQUIRE(M > 0, "update_iter_ex_multi: bad sizes");
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  if (int rc = check_cfg(&c0)) return rc;
+  // the indicator fraction couples every sample of a minibatch: one 64-column pass must hold the whole minibatch
+  SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || c0.batch <= 64,
+              "update_iter_ex_multi: KL-penalty loss with batch_size %d > 64 is not supported", c0.batch);
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_ex_replica& p = reps_host[r];
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "update_iter_ex_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
+                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+    SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.act && p.logp_old && p.adv && p.sync_ws &&
+                    ((p.perm && p.losses_out) || !p.active), "update_iter_ex_multi: null pointer in replica %d", r);
+    SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || (p.old_mean && p.old_std),
+                "update_iter_ex_multi: old distribution is NULL in replica %d", r);
+    SPO_REQUIRE(actor_only || (p.target_r && p.target_c), "update_iter_ex_multi: critic targets are NULL in replica %d", r);
+    SPO_REQUIRE(p.adam_step_critics >= 0 && p.adam_step_actor >= 0, "update_iter_ex_multi: replica %d: negative adam_step", r);
+    for (int q = 0; q < r; ++q)
+      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
+                  "update_iter_ex_multi: replicas %d and %d share theta or sync_ws", q, r);
+    n_active += p.active ? 1 : 0;
+  }
+  if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return spo::fail(-1, "update_iter_ex_multi: the stream is under capture (the argument table is copied from host memory at "
+                           "every call: not a graph node)");
+  }
+  const int wgs = actor_only ? 1 : 3;
+  std::lock_guard<std::mutex> lk(g_exm_mu);                                // (until the table's copy and its event are enqueued)
+  char* base = nullptr;
+  UpdMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  if (int rc = exm_scratch(st, &base, &tab, &tab_ev)) return rc;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_ex_replica& p = reps_host[r];
+    UpdArgs a{};                                                           // (as spo_update_iter_ex fills it)
+    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
+    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
+    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
+    a.slots = reinterpret_cast<unsigned long long*>(base + (size_t)r * EXM_G_STRIDE);      // the run's own granules
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step_critics);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step_critics);
+    a.pow_b1_actor = pow((double)p.cfg.beta1, (double)p.adam_step_actor);
+    a.pow_b2_actor = pow((double)p.cfg.beta2, (double)p.adam_step_actor);
+    a.first_net = actor_only ? 2 : 0; a.n_nets = wgs; a.stale_sq = 0.f; a.stale_io = nullptr;
+    a.old_mean = p.old_mean; a.old_std = p.old_std; a.kl_bound = p.kl_bound; a.pg_coef = p.pg_coef;
+    tab[r].a = a;
+    tab[r].active = p.active ? 1 : 0;
+  }
+  UpdMultiEntry* const table_dev = reinterpret_cast<UpdMultiEntry*>(base + EXM_T_OFF);
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(UpdMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  // the tags restart at 1 with every launch: every run's granules start as zero
+  if (int rc = spo::hip_check(hipMemsetAsync(base, 0, (size_t)n_replicas * EXM_G_STRIDE, st), "hipMemsetAsync(granules)")) return rc;
+  int rc = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY ? launch_update_multi<1>(c0.obs_dim, table_dev, n_replicas, wgs, st)
+                                                   : launch_update_multi<0>(c0.obs_dim, table_dev, n_replicas, wgs, st);
+  if (rc) return rc;
+  SPO_LAUNCH_CHECK("spo_update_iter_ex_multi");
+  g_exm_counters[0] += 1ull;
+  g_exm_counters[1] += (unsigned long long)n_active;
   return 0;
 }
 

@@ -24,4 +24,18 @@ int rs_counters(unsigned long long* out2_host, int reset);
 int rs_row_groups(int obs_dim, int batch);
 // scratch blocks of the replica-batched launch (spo_ppo_lag_update_iter_multi), freed by spo_update_scratch_release
 int rs_multi_scratch_release(int dev, void* stream_or_null, int all);
+// Block map of the replica-batched launches (update_rs.hip: ppo_update_rs_multi_kernel; update.hip: ppo_update_multi_kernel).
+// Workgroups are dealt to the XCDs round-robin by block index (a placement hint: speed only), so block b carries XCD label b & 7;
+// of the blocks with one label, `wgs` consecutive ones serve one replica: replica r sits on label r & 7, replicas r, r + 8, ...
+// share an XCD and its L2.  Host and device share this function (spo_rs_multi_block_map and its kin).  False: the block has no work.
+// `wgs`: workgroups per replica -- 6 for the PPO-Lagrangian step (at most SPO_RS_MAX_REPLICAS / 8 = 4 replicas per XCD: 24 workgroups
+// of one CU each on the XCD's 32 CUs), 8 for the critic fit (SPO_RS_CRITIC_MAX_REPLICAS / 8 = 3 per XCD, again 24), and the number of
+// networks (3, or 1 actor alone) for the four-wave step of spo_update_iter_ex_multi (at most 4 replicas: 12 workgroups per XCD).
+__host__ __device__ inline bool rs_multi_map(int block, int n_replicas, int wgs, int* replica, int* wg) {
+  const int x = block & 7, k = block >> 3;
+  *replica = 8 * (k / wgs) + x;
+  *wg = k % wgs;
+  return *replica < n_replicas;
+}
+inline int rs_multi_grid(int n_replicas, int wgs) { return 8 * wgs * ((n_replicas + 7) / 8); }
 }  // namespace spo

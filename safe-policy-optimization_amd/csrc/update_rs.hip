@@ -1467,20 +1467,8 @@ __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
 }
 
 // ---- replica-batched launch: S independent PPO-Lagrangian runs (own parameters, buffers, optimiser state) take their minibatch
-// steps in ONE persistent launch, each on its own six workgroups (3 networks x 2 row groups) of one XCD.  Workgroups are dealt to
-// the XCDs round-robin by block index (the placement hint above), so block b carries XCD label b & 7; of the blocks with one
-// label, six consecutive ones serve one replica: replica r sits on label r & 7, replicas r, r + 8, ... share an XCD and its L2
-// (at most SPO_RS_MAX_REPLICAS / 8 = 4 of them: 24 workgroups of one CU each on the XCD's 32 CUs).  Host and device share this
-// function (spo_rs_multi_block_map).  False: the block has no work.
-// `wgs`: workgroups per replica -- RS_MULTI_WG for the PPO-Lagrangian step, RS_CRITIC_MULTI_WG for the critic fit (there replicas
-// r, r + 8, r + 16 share an XCD: SPO_RS_CRITIC_MAX_REPLICAS / 8 = 3 of them, again 24 workgroups on the XCD's 32 CUs).
-__host__ __device__ inline bool rs_multi_map(int block, int n_replicas, int wgs, int* replica, int* wg) {
-  const int x = block & 7, k = block >> 3;
-  *replica = 8 * (k / wgs) + x;
-  *wg = k % wgs;
-  return *replica < n_replicas;
-}
-inline int rs_multi_grid(int n_replicas, int wgs) { return 8 * wgs * ((n_replicas + 7) / 8); }
+// steps in ONE persistent launch, each on its own six workgroups (3 networks x 2 row groups) of one XCD; the block map
+// (rs_multi_map, rs_multi_grid) is in update_rs.h, shared with update.hip's seed-batched four-wave launch.
 
 // One replica's arguments as the kernel reads them from the device table (32 of them do not fit the kernel-argument segment):
 // its own exchange slots, granules + census words, tag base and err word -- the step itself is rs_body's, unchanged.

@@ -39,6 +39,15 @@ class CriticFitReplica(Structure):
                 ("stale_sq_io", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg), ("active", c_int)]
 
 
+class UpdateExReplica(Structure):
+    """spo_update_ex_replica (include/safepo_hip.h): one run of a seed-batched spo_update_iter_ex launch (FOCOPS, CUP)."""
+    _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step_critics", c_int64),
+                ("adam_step_actor", c_int64), ("obs", c_void_p), ("act", c_void_p), ("logp_old", c_void_p), ("target_r", c_void_p),
+                ("target_c", c_void_p), ("adv", c_void_p), ("perm", c_void_p), ("old_mean", c_void_p), ("old_std", c_void_p),
+                ("kl_bound", c_float), ("pg_coef", c_float), ("losses_out", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg),
+                ("active", c_int)]
+
+
 class MaNet(Structure):
     """spo_ma_net (include/safepo_hip.h)."""
     _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_blocks", c_int32), ("out_dim", c_int32),
@@ -82,6 +91,7 @@ KLPEN_SUMS = 8                                     # include/safepo_hip.h SPO_KL
 GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GAE_PARTIAL_STRIDE (doubles per workgroup)
 RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS_MAX_REPLICAS
 RS_CRITIC_MAX_REPLICAS = 24                        # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
+UPDATE_EX_MAX_REPLICAS = 32                        # include/safepo_hip.h SPO_UPDATE_EX_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -161,6 +171,11 @@ PROTOTYPES = {
     "spo_critic_fit_iter": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,
                                    c_float, c_float, c_int, P, P, P]),
+    "spo_update_iter_ex_multi": (c_int, [POINTER(UpdateExReplica), c_int, c_int64, c_int, c_int, P]),
+    "spo_update_ex_multi_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "spo_update_ex_multi_matches_single": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_update_ex_multi_block_map": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_update_ex_multi_counters": (c_int, [P, c_int]),
     "spo_kl_penalty_grad": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, c_float, c_float, c_int, P, P, P, P]),
     "spo_clip_adam_ex": (c_int, [P] * 6 + [c_int64, c_int64, c_float, c_float, c_int, POINTER(PpoCfg), P, P]),
     "spo_clip_adam_ex_then_grad": (c_int, [P] * 4 + [c_int64, c_int64, c_float, c_int] + [P] * 7 + [c_int, POINTER(PpoCfg), P, P]),

@@ -1,5 +1,6 @@
 """Seed-batched PPO-Lagrangian: S independent runs (own seed, policy, buffer, optimiser state) on one GPU whose minibatch
 steps share ONE persistent launch (spo_ppo_lag_update_iter_multi, csrc/update_rs.hip): run r on its own six co-XCD workgroups.
+FOCOPS and CUP go through the same group on spo_update_iter_ex_multi (csrc/update.hip: the four-wave step, one workgroup per network).
 CPOEngineGroup does the same for the critic fit of the second-order scripts (spo_critic_fit_iter_multi: eight workgroups per run).
 Per run nothing changes -- the arithmetic of a step is the single launch's, bit for bit, and every run draws its random numbers
 from its own generator state (ReplicaRNG), so run r of a group is the stand-alone run with its seed.
@@ -227,6 +228,162 @@ class PPOLagEngineGroup(_EngineGroup):
             means = torch.cat(all_losses[i], 0).mean(0).tolist() if all_losses[i] else [float("nan")] * 3
             outs.append({"stop_iter": stop_iter[i], "kl": kl[i], "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2],
                          "losses": all_losses[i]})
+        return outs
+
+
+    # ------------------------------------------------------------------ FOCOPS / CUP: spo_update_iter_ex of every active run
+    def batched_ex(self, actor_loss: int, cfgs=None) -> bool:
+        """Does learning_iter_ex_all run as one launch (spo_update_iter_ex_multi)?  Where the stand-alone spo_update_iter_ex runs
+        the four-wave kernel itself (spo_update_ex_multi_matches_single: the library's own routing answers -- always with the
+        KL-penalty loss; with the clipped surrogate where the main + helper kernel does not take the launch, i.e. above 64
+        observations under default routing) and all runs share the minibatch size."""
+        if not self._native:
+            return False
+        cfgs = cfgs or [e._cfg_struct() for e in self.engines]
+        c0 = cfgs[0]
+        if any(c.batch != c0.batch for c in cfgs):
+            return False
+        return bool(self.lib.spo_update_ex_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss), len(self.engines))
+                    and self.lib.spo_update_ex_multi_matches_single(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss)))
+
+    def learning_iter_ex_all(self, perms, advs, actor_loss: int = 0, kl_bounds=None, pg_coefs=None, actor_only: bool = False,
+                             active=None):
+        """PPOLagEngine.learning_iter_ex(perms[i], advs[i], actor_loss, kl_bounds[i], pg_coefs[i], actor_only) for every run i
+        with active[i] (default: all): one spo_update_iter_ex_multi launch where batched_ex(actor_loss), else one launch per
+        run -- the same results.  The run's adam_step (or, with actor_only, adam_step_actor_extra) advances exactly as
+        learning_iter_ex advances it.  Returns the per-minibatch losses [n_mb, 3] per run (None for a run that sat out)."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        kl_bounds = [float("inf")] * S if kl_bounds is None else list(kl_bounds)
+        pg_coefs = [0.0] * S if pg_coefs is None else list(pg_coefs)
+        if not (len(perms) == len(advs) == len(active) == len(kl_bounds) == len(pg_coefs) == S):
+            raise ValueError("learning_iter_ex_all: one perm, adv, kl_bound, pg_coef and active flag per engine")
+        cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
+        if not self.batched_ex(actor_loss, cfgs):
+            return [e.learning_iter_ex(perms[i], advs[i], actor_loss, kl_bounds[i], pg_coefs[i], actor_only) if active[i] else None
+                    for i, e in enumerate(self.engines)]
+        e0 = self.engines[0]
+        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
+        reps = (_abi.UpdateExReplica * S)()
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            d = e.buffer.data
+            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
+            perm = perms[i] if active[i] else None
+            if perm is not None:
+                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+                losses[i] = torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=e.dev)
+            adv = _abi.require_gpu_tensor(advs[i], "adv", torch.float32)
+            r = reps[i]
+            r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
+            r.adam_step_critics, r.adam_step_actor = e.adam_step, e.adam_step + e.adam_step_actor_extra
+            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(adv)
+            r.perm, r.old_mean, r.old_std = _abi.ptr(perm), _abi.ptr(e.mean_old), _abi.ptr(e.std_old)
+            r.kl_bound, r.pg_coef, r.losses_out = float(kl_bounds[i]), float(pg_coefs[i]), _abi.ptr(losses[i])
+            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
+        _abi.check(self.lib.spo_update_iter_ex_multi(reps, S, e0.M, int(actor_loss), int(bool(actor_only)), _abi.stream_ptr()),
+                   "spo_update_iter_ex_multi")
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                if actor_only:
+                    e.adam_step_actor_extra += n_mb
+                else:
+                    e.adam_step += n_mb
+        return losses
+
+    def _default_perm_fns(self, perm_fns):
+        es, S = self.engines, len(self.engines)
+
+        def default_perm_fn(i):
+            def fn(it):
+                with self.rng(i):
+                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
+            return fn
+
+        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
+        if len(perm_fns) != S:
+            raise ValueError("one perm_fn (or None) per engine")
+        return [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+
+    def _kl_stopped_loop_all(self, perm_fns, it0s, launch):
+        """PPOLagEngine._kl_stopped_loop for every run, one `launch(perms, active)` per pass: run i draws the shuffle
+        perm_fns[i](it0s[i] + it) at the start of pass `it` and none after it stopped (its own target_kl, its own learning_iters);
+        a run that stopped sits out the later launches.  The KLs of a pass are read in one host read.
+        Returns (losses, stop_iter, kl), each a list over the runs."""
+        es, S = self.engines, len(self.engines)
+        n_its = [e.cfg["learning_iters"] for e in es]
+        active = [n > 0 for n in n_its]
+        all_losses, stop_iter, kl = [[] for _ in range(S)], [0] * S, [1.0] * S
+        it = 0
+        while any(active):
+            idx = [i for i in range(S) if active[i]]
+            perms = [perm_fns[i](it0s[i] + it) if active[i] else None for i in range(S)]
+            losses = launch(perms, list(active))
+            for i in idx:
+                all_losses[i].append(losses[i])
+                es[i].kl_launch()
+            for i, v in zip(idx, self._read_kls(idx)):
+                kl[i] = v
+                stop_iter[i] += 1
+                if v > es[i].cfg["target_kl"] or it + 1 >= n_its[i]:
+                    active[i] = False
+            it += 1
+        return all_losses, stop_iter, kl
+
+    def update_focops(self, lams, perm_fns=None, focops_lam: float = 1.5):
+        """PPOLagEngine.update_focops for every run: GAE and the old-distribution snapshot seed by seed, then the KL-stopped
+        loop with one spo_update_iter_ex_multi launch per pass.  Returns the list of update_focops()'s dicts."""
+        es, S = self.engines, len(self.engines)
+        if len(lams) != S:
+            raise ValueError("update_focops: one multiplier per engine")
+        perm_fns = self._default_perm_fns(perm_fns)
+        for e, lam in zip(es, lams):
+            e.buffer.compute_gae(lam, e.comm)
+            e.snapshot_old_distribution()
+        advs = [e.buffer.adv_mix for e in es]
+        kl_bounds, pg_coefs = [e.cfg["target_kl"] for e in es], [1.0 / focops_lam] * S
+        losses, stop_iter, kl = self._kl_stopped_loop_all(perm_fns, [0] * S, lambda perms, active: self.learning_iter_ex_all(
+            perms, advs, _abi.ACTOR_LOSS_KL_PENALTY, kl_bounds, pg_coefs, False, active))
+        self.check_sync_error()
+        outs = []
+        for i, e in enumerate(es):
+            e.buffer.reset()
+            means = torch.cat(losses[i], 0).mean(0).tolist()
+            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2],
+                         "losses": losses[i]})
+        return outs
+
+    def update_cup(self, lams, perm_fns=None, cup_lambda: float = 0.95):
+        """PPOLagEngine.update_cup for every run: stage one (clipped surrogate on adv_r) for all runs, the second snapshot run by
+        run, then stage two (the actor alone, KL penalty) -- run i's shuffle index going on from its own stage-one stop_iter.
+        A stage is one launch per pass where batched_ex says so for its loss, else one launch per run per pass (under default
+        routing: stage one up to 64 observations, which the stand-alone run puts on the main + helper kernel)."""
+        es, S = self.engines, len(self.engines)
+        if len(lams) != S:
+            raise ValueError("update_cup: one multiplier per engine")
+        perm_fns = self._default_perm_fns(perm_fns)
+        for e in es:
+            e.buffer.compute_gae(0.0, e.comm)              # lambda 0: adv_mix == adv_r exactly (cup.py:285)
+            e.snapshot_old_distribution()
+        adv_r = [e.buffer.adv_mix for e in es]
+        losses, stop_iter, kl = self._kl_stopped_loop_all(perm_fns, [0] * S, lambda perms, active: self.learning_iter_ex_all(
+            perms, adv_r, _abi.ACTOR_LOSS_CLIP, None, None, False, active))
+        for e in es:
+            e.snapshot_old_distribution()                  # cup.py:355-358
+        coefs = [(1 - e.cfg["gamma"] * cup_lambda) / (1 - e.cfg["gamma"]) for e in es]
+        adv_c = [e.buffer.data["adv_c"] for e in es]
+        pg_coefs = [-float(lam) * coef for lam, coef in zip(lams, coefs)]
+        losses2, stop_iter2, kl2 = self._kl_stopped_loop_all(perm_fns, stop_iter, lambda perms, active: self.learning_iter_ex_all(
+            perms, adv_c, _abi.ACTOR_LOSS_KL_PENALTY, [float("inf")] * S, pg_coefs, True, active))
+        self.check_sync_error()
+        outs = []
+        for i, e in enumerate(es):
+            e.buffer.reset()
+            means = torch.cat(losses[i], 0).mean(0).tolist()
+            outs.append({"stop_iter": stop_iter[i], "second_stage_stop_iter": stop_iter2[i], "kl": kl2[i], "kl_first_stage": kl[i],
+                         "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2], "losses": losses[i],
+                         "second_stage_losses": losses2[i]})
         return outs
 
 

@@ -105,9 +105,10 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
         variant: str = "ppo"):
     """variant: "ppo" (clipped surrogate family), "focops" (focops.py:279-367) or "cup" (cup.py:279-405)."""
     if len(seed_list(args)) > 1:
-        if variant != "ppo":
-            refuse_seed_batch(args, "focops and cup")
-        return run_seed_batch(args, cfg_env, default_cfg, multiplier, clip)
+        if variant != "ppo" and not getattr(args, "batch_update", False):
+            refuse_seed_batch(args, "focops and cup",
+                              ".  (Opt in with --batch-update True: the seeds' minibatch steps then share one persistent launch.)")
+        return run_seed_batch(args, cfg_env, default_cfg, multiplier, clip, variant)
     args.seed = seed_list(args)[0]      # (`--seeds s` alone is `--seed s`)
     random.seed(args.seed)
     np.random.seed(args.seed)
@@ -233,8 +234,8 @@ class _SeedRun:
     """One run of a seed-batched process: what run() holds in local variables, per seed."""
 
 
-def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, clip: float | None):
-    """`--seeds s0 s1 ...`: run() for several seeds in one process on one GPU.  Every seed has its own env, policy, engine,
+def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, clip: float | None, variant: str = "ppo"):
+    """`--seeds s0 s1 ...`: run() for several seeds in one process on one GPU (variant "focops" / "cup": with --batch-update True).  Every seed has its own env, policy, engine,
     multiplier and logger (in the log directory its own `--seed` run would write) and draws every random number from its own
     generator state (ReplicaRNG), so each is the stand-alone run of its seed; rollout, evaluation, multiplier update and logging
     run seed by seed, the update runs through PPOLagEngineGroup -- the seeds' minibatch steps in one persistent launch.  The
@@ -283,8 +284,9 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
                                  "kernels: one process per seed")
             r.engine = PPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
             if multiplier == "adam":
+                upper = {"focops": FOCOPS_NU, "cup": CUP_NU}.get(variant)          # focops.py:136, cup.py:136
                 r.lagrange = Lagrange(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init,
-                                      lagrangian_multiplier_lr=args.lagrangian_multiplier_lr, lagrangian_upper_bound=None)
+                                      lagrangian_multiplier_lr=args.lagrangian_multiplier_lr, lagrangian_upper_bound=upper)
             elif multiplier == "pid":
                 r.lagrange = PIDLagrangian(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init)
             else:
@@ -326,7 +328,12 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
                 r.lagrange.update_lagrange_multiplier(ep_costs)
             lams.append(r.lagrange.lagrangian_multiplier if r.lagrange is not None else 0.0)
             r.engine.lr_factor = 1.0 - epoch / epochs if epochs > 0 else 1.0
-        outs = group.update(lams)                      # (the shuffles are drawn under the runs' generator states)
+        if variant == "focops":                        # (the shuffles are drawn under the runs' generator states)
+            outs = group.update_focops(lams, focops_lam=FOCOPS_LAM)
+        elif variant == "cup":
+            outs = group.update_cup(lams, cup_lambda=CUP_LAMBDA)
+        else:
+            outs = group.update(lams)
         torch.cuda.synchronize(device)
         update_end_time = time.time()
         next_lr = 3e-4 * (1.0 - min(epoch + 1, epochs) / epochs)
@@ -334,7 +341,7 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
         for r, out in zip(runs, outs):
             r.logger.store(**{"Loss/Loss_reward_critic": out["loss_r"], "Loss/Loss_cost_critic": out["loss_c"],
                               "Loss/Loss_actor": out["loss_pi"]})
-            _log_epoch(r.logger, args, out, "ppo", r.lagrange, epoch, next_lr, r.engine, r.env, True,
+            _log_epoch(r.logger, args, out, variant, r.lagrange, epoch, next_lr, r.engine, r.env, True,
                        t_rollout=rollout_end_time - rollout_start_time, t_eval=eval_end_time - rollout_end_time,
                        t_update=update_end_time - eval_end_time, t_total=update_end_time - rollout_start_time)
     for r in runs:

@@ -9,7 +9,9 @@ through `--device-id`, and `--workers` defaults to one per GPU.  `--workers 0` o
 cppo_pid -- and ppo / pg -- on the persistent kernels' shapes); the other algorithms, and HumanoidVelocity, keep one subprocess
 per seed.  `--batch-second-order` (default off) lets cpo / pcpo / rcpo / trpo_lag / trpo / natural_pg join that grouping on
 the tasks whose observations fit the persistent CPO kernels (at most 24 seeds per subprocess), with `--batch-critic-fit True`
-on those commands: their critic fits share one persistent launch per iteration.
+on those commands: their critic fits share one persistent launch per iteration.  `--batch-focops-cup` (default off) does the
+same for focops / cup with `--batch-update True` (up to 32 seeds per subprocess): their minibatch steps share one persistent launch
+per pass.
 """
 from __future__ import annotations
 
@@ -19,6 +21,8 @@ import shlex
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
+
+from safepo.utils.config import KLPEN_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -64,11 +68,15 @@ def parse_args(argv=None):
                         "critic-fit step of ALL seeds takes 9.9 / 11.2 / 14.2 us at 8 / 16 / 24 seeds against 9.8 us per seed one after "
                         "the other (60 / 8; profiles/seed_batch_critic/step_times.txt): the time per seed falls up to the cap, so the "
                         "largest K the sweep has seeds for.  Default off: these algorithms keep one subprocess per seed")
+    p.add_argument("--batch-focops-cup", action="store_true",
+                   help="with --seeds-per-run: also group focops / cup (--batch-update True on those commands; HumanoidVelocity "
+                        "excepted).  " + KLPEN_BATCH_FIGURES + "  Default off: these algorithms keep one subprocess per seed")
     return p.parse_args(argv)
 
 
 SEED_BATCHED_ALGOS = ("ppo_lag", "ppo", "pg", "cppo_pid")     # the scripts with a `--seeds` form (persistent-kernel shapes only)
 CRITIC_BATCHED_ALGOS = ("cpo", "pcpo", "rcpo", "trpo_lag", "trpo", "natural_pg")   # ... with --batch-critic-fit True
+KLPEN_BATCHED_ALGOS = ("focops", "cup")                       # ... with --batch-update True (persistent-kernel shapes only)
 CRITIC_BATCH_MAX = 24                                         # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
 
@@ -77,6 +85,12 @@ def _takes_seeds(algo: str, task: str) -> bool:
     """Can `--seeds` carry several seeds for this (algorithm, task)?  HumanoidVelocity (376 / 17) runs on the wide-network
     kernels, which have no seed-batched form."""
     return algo in SEED_BATCHED_ALGOS and "Humanoid" not in task
+
+
+def _takes_klpen_batch(algo: str, task: str) -> bool:
+    """Can `--seeds ... --batch-update True` carry several seeds for this (algorithm, task)?  As _takes_seeds: every task but
+    HumanoidVelocity runs on the persistent kernels (up to 128 observations)."""
+    return algo in KLPEN_BATCHED_ALGOS and "Humanoid" not in task
 
 
 def _takes_critic_batch(algo: str, task: str) -> bool:
@@ -102,8 +116,9 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
             for algo in args.algo:
                 # one command for the whole group where the script takes --seeds, else one per seed as ever
                 critic = getattr(args, "batch_second_order", False) and _takes_critic_batch(algo, task)
+                klpen = getattr(args, "batch_focops_cup", False) and _takes_klpen_batch(algo, task)
                 runs = [[s] for s in group]
-                if len(group) > 1 and _takes_seeds(algo, task):
+                if len(group) > 1 and (_takes_seeds(algo, task) or klpen):
                     runs = [group]
                 elif len(group) > 1 and critic:
                     runs = [group[i:i + CRITIC_BATCH_MAX] for i in range(0, len(group), CRITIC_BATCH_MAX)]
@@ -112,7 +127,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                     commands.append(" ".join([
                         shlex.quote(sys.executable), shlex.quote(os.path.join(script_dir, f"{algo}.py")), "--task", shlex.quote(task),
                         "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else [])
-                        + (["--batch-critic-fit", "True"] if batched and critic else []) + [
+                        + (["--batch-critic-fit", "True"] if batched and critic else [])
+                        + (["--batch-update", "True"] if batched and klpen else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
                         str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))

@@ -88,12 +88,19 @@ CRITIC_BATCH_FIGURES = ("Measured at 60 / 8, 4096 x 128 rows, batch 128: one cri
                         "against 3.35 s (profiles/seed_batch_critic/step_times.txt).")
 
 
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_klpen/step_times.txt)
+KLPEN_BATCH_FIGURES = ("Measured at 4096 x 128 rows, batch 64: one FOCOPS step of ALL seeds takes 12.7 / 12.9 / 13.0 us at 8 / 16 / 32 seeds (60 / 8) against "
+                       "12.2 us per seed one after the other (7.6 x / 15.1 x / 30.0 x the aggregate step rate; 72 / 2 the same ratios; CUP's second "
+                       "stage 7.7 x / 15.4 x / 30.7 x), no knee up to 32; one seed alone: 12.62 against 12.16 us, which is why one seed stays "
+                       "`--seed` (profiles/seed_batch_klpen/step_times.txt).")
+
+
 def single_agent_args(argv=None):
     """-> (args, cfg_env).  cfg_env is {} for non-Isaac tasks (reference config.py:172-191)."""
     parser = build_parser()
     # (not a reference flag, so not in build_parser's table) several independent runs in ONE process on one GPU
     parser.add_argument("--seeds", type=int, nargs="+", default=None,
-                        help="seed-batched run (ppo_lag, ppo, pg, cppo_pid): one env / policy / optimiser / logger per seed, each "
+                        help="seed-batched run (ppo_lag, ppo, pg, cppo_pid; focops and cup with --batch-update True): one env / policy / optimiser / logger per seed, each "
                              "the run `--seed` of that seed would be, their updates sharing one persistent launch (up to 32 seeds; "
                              "run r is placed on XCD r mod 8; one minibatch step of ALL seeds takes 7.8-7.9 us up to 16 seeds and 8.2 us at 32 "
                              "against 7.7 us for one seed alone at 60 / 8, profiles/seed_batch/step_times.txt).  Default: [--seed], the ordinary single run")
@@ -102,6 +109,11 @@ def single_agent_args(argv=None):
                              "process, their critic fits sharing one persistent launch per iteration (up to 24 seeds, eight workgroups "
                              "each, run r on XCD r mod 8; hidden [64, 64], obs_dim <= 64), each seed the run its `--seed` would be.  "
                              + CRITIC_BATCH_FIGURES + "  Default False: several seeds are refused for these scripts")
+    parser.add_argument("--batch-update", type=_bool, default=False,
+                        help="focops and cup with --seeds: run the seeds in one process, their minibatch steps sharing one persistent "
+                             "launch per pass (spo_update_iter_ex_multi: up to 32 seeds, one workgroup per network each, run r on XCD "
+                             "r mod 8; hidden [64, 64], obs_dim <= 128, act_dim <= 16), each seed the run its `--seed` would be.  "
+                             + KLPEN_BATCH_FIGURES + "  Default False: several seeds are refused for these scripts")
     args = parser.parse_args(argv)
     if args.task in isaac_gym_map:
         raise Exception("Please install isaacgym to run Isaac Gym tasks!")
