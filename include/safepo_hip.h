@@ -222,6 +222,26 @@ int spo_update_rs_supported(int obs_dim, int act_dim, int batch, int n_nets);
  * steps; nothing is redone in it, the second counter counts its steps whose joint clip was active. */
 int spo_update_rs128_supported(int obs_dim, int act_dim, int batch, int n_nets);
 
+/* Staged minibatch inputs of the row-split PPO-Lagrangian step (two row groups, obs_dim <= 64, one GPU).  What a step reads of the
+ * buffer depends only on perm, the buffer and the shapes, so spo_ppo_lag_update_iter gathers it in a full-machine pre-pass on the
+ * caller's stream, once per launch, into one record per minibatch step -- x[64][KIN] with pad features zero, the same transposed,
+ * act[64][16], logp_old / adv / target_r / target_c[64]; KIN = 16 / 32 / 64, columns past `batch` zero -- and the persistent kernel
+ * reads records instead of gathering in its step.  Same bits.  The block belongs to the (device, stream) pair like the exchange
+ * scratch, grows on demand (never inside a capture: such a launch gathers in the kernel unless the block is already large
+ * enough) and is freed by spo_update_scratch_release.  Environment, read at every launch: SPO_RS_STAGE=0 turns it off,
+ * SPO_RS_STAGE_MAX_MB (default 1024) bounds the block -- a launch that would need more, or 2 GiB or more, gathers in the kernel,
+ * and so does the one-batch A/B form of the 33-64-observation kernel (SPO_RS_L1_PIPE=0).
+ * spo_rs_stage_bytes: the block's size for a launch of M samples ((M + batch - 1) / batch records), 0 where the staged form does
+ * not apply (obs_dim > 64, batch > 64 -- the critic fit's 128-row minibatches --, SPO_RS_ROWS=16).  Needs no GPU. */
+int64_t spo_rs_stage_bytes(int obs_dim, int act_dim, int batch, int64_t M);
+/* Form of the last row-split launch on the current device: 0 = gathered in the kernel, 1 = staged inputs, 2 = staged inputs with
+ * the x^T operand of layer 1's weight gradient kept as an LDS image (SPO_RS_STAGE=2, A/B form). */
+int spo_debug_rs_last_staged(void);
+/* The staging pre-pass alone, into out_dev (device memory, 16-byte aligned, out_bytes >= spo_rs_stage_bytes(...)). */
+int spo_debug_rs_stage(const float* obs, const float* act, const float* logp_old, const float* target_r, const float* target_c,
+                       const float* adv, const int32_t* perm, int64_t M, int obs_dim, int act_dim, int batch, void* out_dev,
+                       int64_t out_bytes, void* stream);
+
 /* Seed-batched PPO-Lagrangian: S INDEPENDENT runs (own parameters, optimiser state, buffers, shuffle, cfg scalars) take the
  * minibatch steps of one learning iteration in ONE persistent launch of the row-split kernel, every run on its own six workgroups
  * (3 networks x 2 row groups) of one XCD; run r sits on XCD r mod 8, so up to eight runs have an XCD each and runs r, r + 8, ...

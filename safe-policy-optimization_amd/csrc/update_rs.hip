@@ -57,13 +57,13 @@ constexpr int RS_NPHASE = 12;
 constexpr int RS_MULTI_WG = 6;                    // replica-batched launch: workgroups per replica (3 networks x 2 row groups)
 constexpr int RS_CRITIC_MULTI_WG = 8;             // ... of the critic fit (2 critics x 4 row groups)
 
-template <int KIN, int NCT>
+template <int KIN, int NCT, bool NOXT = false>
 struct RsLds {                                   // floats; NCT = 16-column tiles per workgroup (2: 32 rows of a minibatch, 1: 16)
   using L = NetLds<KIN>;
   static constexpr int LDC = 16 * NCT + 4;       // [feature][batch] LDS row stride
   static constexpr int LS = L::SIZE;             // log_std mirror (16), then 1 / sigma^2 (16) and log_std + log sqrt(2 pi) (16) per action
-  static constexpr int XT = LS + 48;             // two x^T images (double-buffered across steps)
-  static constexpr int H1T = XT + 2 * KIN * LDC;
+  static constexpr int XT = LS + 48;             // two x^T images (double-buffered across steps); NOXT: none (staged inputs, x^T from the record)
+  static constexpr int H1T = XT + (NOXT ? 0 : 2 * KIN * LDC);
   static constexpr int H2T = H1T + HID * LDC;
   static constexpr int DZ2T = H2T + HID * LDC;
   static constexpr int DZ1T = DZ2T + HID * LDC;
@@ -101,6 +101,8 @@ struct RsArgs {
   int xr_rank;
   unsigned xr_step0;
   unsigned long long rsx_off;
+  const char* stage;                   // staged minibatch inputs (STG instantiations): record s at stage + s * RsStage<KIN>::BYTES
+  unsigned stage_bytes;                // ... and the bytes of its nsteps records (< 2^31: read through a buffer descriptor)
 };
 constexpr size_t rs_z_bytes(int R) { return (size_t)2 * 3 * R * R * RS_NS * 4096; }
 constexpr int RS_GRAN_WORDS = 2 * RS_MAX_R * 3 * 4;
@@ -120,6 +122,83 @@ struct RsCol {                         // per-column inputs of one minibatch, pr
   f4 actv;
   float t0, t1;                        // critic: target ; actor: logp_old, adv
 };
+
+// ---- staged minibatch inputs (STG instantiations of rs_body).  What a step reads of the buffer depends on perm, the buffer and the
+// shapes only, not on the parameters; gathered by the persistent kernel it is done six times over (3 networks x 2 row groups) on
+// the CUs whose instruction issue is the step: sample index, 64-bit row addresses, clamps, pad selects, the x^T image.  A
+// full-machine pre-pass (rs_stage_inputs_kernel, once per launch: every learning iteration draws its own permutation) writes one
+// RECORD per minibatch step instead, byte offsets below, every float a bit copy of a buffer element or +0.0f:
+//   x[c][k]   c < 64, k < KIN : observation of column c, pad features k >= D zero       (column lanes: f4 at [gcol][16 nt + 4 q])
+//   xT[k][c]                  : the same values transposed                              (dW1's operand: f4 at [16 nt + j][32 hf + 16 r4 + 4 q])
+//   act[c][16]                : entries >= A zero
+//   logp_old[c], adv[c], tgt_r[c], tgt_c[c]
+// Column c of step s is sample perm[s B + (c < ncols ? c : 0)], ncols = min(B, M - s B) -- perm_pos of rs_body; columns c >= B
+// (batch < 64) are zeros: their loss and gradient terms are masked (cv), so what they hold changes no bit of the result.
+template <int KIN>
+struct RsStage {
+  static constexpr unsigned X = 0;
+  static constexpr unsigned XT = 64u * KIN * 4u;
+  static constexpr unsigned ACT = 2u * 64u * KIN * 4u;
+  static constexpr unsigned LOGP = ACT + 64u * 16u * 4u;
+  static constexpr unsigned ADV = LOGP + 256u;
+  static constexpr unsigned TGT_R = ADV + 256u;
+  static constexpr unsigned TGT_C = TGT_R + 256u;
+  static constexpr unsigned BYTES = TGT_C + 256u;
+  static_assert(BYTES % 256u == 0, "record stride: a multiple of 256 bytes");
+};
+
+// One workgroup of 256 lanes per minibatch step: the gather lands in an LDS tile (row stride KIN + 1: both read-outs conflict-free),
+// and every part of the record leaves as consecutive lanes writing consecutive words.
+template <int KIN>
+__global__ __launch_bounds__(256) void rs_stage_inputs_kernel(const float* __restrict__ obs, const float* __restrict__ act,
+                                                              const float* __restrict__ logp_old, const float* __restrict__ adv,
+                                                              const float* __restrict__ tgt_r, const float* __restrict__ tgt_c,
+                                                              const int32_t* __restrict__ perm, int64_t M, int D, int A, int B,
+                                                              char* __restrict__ out) {
+  using G = RsStage<KIN>;
+  __shared__ float tile[64 * (KIN + 1)];
+  __shared__ int64_t smp_s[64];
+  const int tid = threadIdx.x;
+  const int64_t s = blockIdx.x;
+  const int64_t base = s * B;
+  const int64_t rem = M - base;
+  const int ncols = (int)(rem < B ? rem : B);
+  char* const rec = out + s * (int64_t)G::BYTES;
+  if (tid < 64) smp_s[tid] = tid < B ? (int64_t)perm[base + (tid < ncols ? tid : 0)] : (int64_t)-1;
+  __syncthreads();
+  {
+    const int c = tid >> 2, k0 = tid & 3;
+    const int64_t smp = smp_s[c];
+    const float* const row = obs + (smp < 0 ? 0 : smp) * D;
+#pragma unroll
+    for (int i = 0; i < KIN / 4; ++i) {
+      const int k = k0 + 4 * i;
+      tile[c * (KIN + 1) + k] = (smp >= 0 && k < D) ? row[k] : 0.f;
+    }
+  }
+  __syncthreads();
+  float* const xo = reinterpret_cast<float*>(rec + G::X);
+  float* const xto = reinterpret_cast<float*>(rec + G::XT);
+#pragma unroll
+  for (int i = 0; i < 64 * KIN / 256; ++i) {
+    const int idx = tid + 256 * i;
+    xo[idx] = tile[(idx / KIN) * (KIN + 1) + (idx % KIN)];
+    xto[idx] = tile[(idx & 63) * (KIN + 1) + (idx >> 6)];
+  }
+  float* const ao = reinterpret_cast<float*>(rec + G::ACT);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + 256 * i, c = idx >> 4, ai = idx & 15;
+    const int64_t smp = smp_s[c];
+    ao[idx] = (smp >= 0 && ai < A) ? act[smp * A + ai] : 0.f;
+  }
+  {
+    const int arr = tid >> 6, c = tid & 63;
+    const int64_t smp = smp_s[c];
+    const float* const src = arr == 0 ? logp_old : arr == 1 ? adv : arr == 2 ? tgt_r : tgt_c;
+    reinterpret_cast<float*>(rec + G::LOGP)[tid] = smp >= 0 ? src[smp] : 0.f;
+  }
+}
 
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 // System-scope 16-byte word at (uniform base) + (32-bit lane offset): the base travels in SGPRs (readfirstlane pins it there), so a
@@ -198,7 +277,9 @@ __device__ __forceinline__ void layer_part(const float* Wl, int ld, const float*
 // half is still being accumulated, and the consumer sums it, takes its L2 / norm terms and runs its speculative Adam while the
 // second half is in flight.  Same slots, parity, cache policy and per-element arithmetic, the norm terms in the same order: the
 // same bits as the one-batch form (SPO_RS_L1_PIPE=0).
-template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2, bool MULTI = false, bool L1P = false>
+// STG: the minibatch inputs come from the records of rs_stage_inputs_kernel (one GPU, R = 2, KIN <= 64) -- 1: the optimiser waves
+// take dW1's x^T operand from the record too and the LDS images are not built; 2: the images stay, written from the staged x.
+template <int KIN, int R, bool FAST, bool PROF, int XW = 0, int NCT = 2, bool MULTI = false, bool L1P = false, int STG = 0>
 __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const int wg_multi = 0) {
   // The launch's pointers as INDIVIDUAL scalar-register pairs.  Read straight from the argument struct they arrive as one
   // s_load_dwordx16 -- a 16-register tuple that the allocator can only spill and restore WHOLE: 16 v_readlane at each of 41 places
@@ -214,7 +295,17 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
   const float* const p_tgt_c = own_sgprs(a.tgt_c);
   const float* const p_adv = own_sgprs(a.adv);
   using L = NetLds<KIN>;
-  using S = RsLds<KIN, NCT>;
+  using S = RsLds<KIN, NCT, STG == 1>;
+  using G = RsStage<KIN <= 64 ? KIN : 64>;
+  static_assert(STG == 0 || (R == 2 && XW == 0 && NCT == 2 && !MULTI && KIN <= 64), "staged inputs are built for one GPU, R = 2, KIN <= 64");
+  // the records are read through a buffer descriptor: base and step offset in scalar registers, a loop-invariant 32-bit lane
+  // offset -- no 64-bit vector address arithmetic per load
+  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(a.stage), 0, (int)a.stage_bytes, 0x00020000);
+  auto stage_f4 = [&](unsigned voff, unsigned soff) -> f4 {
+    const u4 w = __builtin_amdgcn_raw_buffer_load_b128(srsrc, voff, soff, 0);
+    return f4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
+  };
+  auto stage_f1 = [&](unsigned voff, unsigned soff) -> float { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srsrc, voff, soff, 0)); };
   constexpr int LDC = S::LDC;
   constexpr int NT1 = KIN / 16;
   // KIN = 128: layer 1's optimiser state does not fit a 256-register wave the way it is held up to 64 (6 x NT1 f4 of moments,
@@ -316,6 +407,35 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
         }
       }
     };
+    // staged inputs: the record's base in scalar registers, loop-invariant 32-bit lane offsets, 16-byte loads -- nothing to mask
+    const unsigned sx_off = G::X + (unsigned)(gcol * KIN + 4 * q_) * 4u;
+    const unsigned sa_off = G::ACT + (unsigned)(gcol * 16 + 4 * q_) * 4u;
+    const unsigned st0_off = (is_actor ? G::LOGP : net == 0 ? G::TGT_R : G::TGT_C) + (unsigned)gcol * 4u;
+    const unsigned st1_off = G::ADV + (unsigned)gcol * 4u;
+    auto fetch_stg = [&](int64_t s_, RsCol<NT1>& cd) {
+      const unsigned rec = __builtin_amdgcn_readfirstlane((unsigned)s_ * G::BYTES);
+#pragma unroll
+      for (int nt = 0; nt < NT1; ++nt) cd.x[nt] = stage_f4(sx_off + 64u * nt, rec);
+      cd.t0 = stage_f1(st0_off, rec);
+      if (!is_actor) {
+        cd.t1 = 0.f; cd.actv = f4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        cd.t1 = stage_f1(st1_off, rec);
+        cd.actv = stage_f4(sa_off, rec);
+      }
+    };
+    auto settle_stg = [&](RsCol<NT1>& cd) {
+#pragma unroll
+      for (int nt = 0; nt < NT1; ++nt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cd.x[nt][e] = pin(cd.x[nt][e]);
+      cd.t0 = pin(cd.t0);
+      if (is_actor) {
+        cd.t1 = pin(cd.t1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cd.actv[r] = pin(cd.actv[r]);
+      }
+    };
     auto col_loop = [&](auto PARTC) {
     constexpr int PART = decltype(PARTC)::value;
     constexpr int M0 = PART * NOWN;              // own output tiles M0 .. M0 + NOWN - 1; the others are the partner waves'
@@ -326,11 +446,17 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     // x^T image), the rows of minibatch s + 2 are requested, the sample index for s + 3 is loaded.
     RsCol<NT1> nxt, raw;
     int smp2 = 0;
-    fetch((int64_t)a.perm[perm_pos(0)], nxt);
-    if (nsteps > 1) fetch((int64_t)a.perm[perm_pos(1)], raw);
-    if (nsteps > 2) smp2 = a.perm[perm_pos(2)];
-    settle(nxt);
-    if (PART == 0) {
+    if constexpr (STG != 0) {
+      fetch_stg(0, nxt);
+      if (nsteps > 1) fetch_stg(1, raw);
+      settle_stg(nxt);
+    } else {
+      fetch((int64_t)a.perm[perm_pos(0)], nxt);
+      if (nsteps > 1) fetch((int64_t)a.perm[perm_pos(1)], raw);
+      if (nsteps > 2) smp2 = a.perm[perm_pos(2)];
+      settle(nxt);
+    }
+    if (PART == 0 && STG != 1) {
 #pragma unroll
       for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
@@ -361,11 +487,17 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
       }
       if (s + 1 < nsteps) {
         RS_REIDX
-        settle(raw);
-        nxt = raw;
-        if (s + 2 < nsteps) fetch((int64_t)pin(smp2), raw);
-        if (s + 3 < nsteps) smp2 = a.perm[perm_pos(s + 3)];
-        if (PART == 0) {
+        if constexpr (STG != 0) {
+          settle_stg(raw);
+          nxt = raw;
+          if (s + 2 < nsteps) fetch_stg(s + 2, raw);
+        } else {
+          settle(raw);
+          nxt = raw;
+          if (s + 2 < nsteps) fetch((int64_t)pin(smp2), raw);
+          if (s + 3 < nsteps) smp2 = a.perm[perm_pos(s + 3)];
+        }
+        if (PART == 0 && STG != 1) {
           float* const xt = lds + S::XT + (int)((s + 1) & 1) * KIN * LDC;
 #pragma unroll
           for (int nt = 0; nt < NT1; ++nt)
@@ -601,6 +733,7 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
   const bool has_l2 = (l2 != 0.f) || (vcoef != 1.f);                      // (uniform over the workgroup)
   float stale_sq = a.stale_io ? *a.stale_io : 0.f;
   volatile float* const dead = red + 97;
+  const unsigned sxt_off = G::XT + (unsigned)(j_ * 64 + 32 * hf + 4 * q_) * 4u;   // (staged x^T operand of dW1: this lane's offset in a record)
 
   // ---- exchange transport (update_ks.hip): bare floats, 16-byte buffer loads / stores, NaN sentinel
   const __amdgpu_buffer_rsrc_t zrsrc = __builtin_amdgcn_make_buffer_rsrc(a.zbuf, 0, (int)rs_z_bytes(R), 0x00020000);
@@ -873,6 +1006,17 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     f4 gA[7];                                                             // W2 tiles, W3 tile, {db2, db3, loss partial, -}, d(log_std)
     f4 gB[NT1 + 1];                                                       // W1 tiles, {db1, -, -, -}
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // the resets of the previous step are acknowledged by the L2
+    // staged inputs: the x^T operand of dW1 from the step's record (resident since before the launch), 2 NT1 16-byte loads issued
+    // HERE -- the optimiser reaches b4 some 2 k cycles ahead of the column waves and b5 only a few hundred: requested at the
+    // preloads the loads' round trip would sit between b5 and dW1, on the step's chain
+    f4 bxs[STG == 1 ? NCT : 1][STG == 1 ? NTX : 1];
+    if constexpr (STG == 1) {
+      const unsigned rec = __builtin_amdgcn_readfirstlane((unsigned)s * G::BYTES);
+#pragma unroll
+      for (int r4 = 0; r4 < NCT; ++r4)
+#pragma unroll
+        for (int nt = 0; nt < NTX; ++nt) bxs[r4][nt] = stage_f4(sxt_off + 64u * r4, rec + 4096u * nt);
+    }
     RS_STAMP(0)
     __syncthreads();                                                      // b4: h1^T, h2^T, dZ2^T, dO^T complete
     RS_STAMP(1)
@@ -923,12 +1067,19 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
     float pb1;
     {
       RS_REIDX
-      const float* const xt = lds + S::XT + par * KIN * LDC;
+      if constexpr (STG == 1) {
 #pragma unroll
-      for (int r4 = 0; r4 < NCT; ++r4)
+        for (int r4 = 0; r4 < NCT; ++r4)
 #pragma unroll
-        for (int nt = 0; nt < NTX; ++nt)
-          bx[r4][nt] = *reinterpret_cast<const f4*>(xt + (16 * nt + j) * LDC + 16 * r4 + 4 * q);
+          for (int nt = 0; nt < NTX; ++nt) bx[r4][nt] = bxs[r4][nt];                 // (requested at the top of the step)
+      } else {
+        const float* const xt = lds + S::XT + par * KIN * LDC;
+#pragma unroll
+        for (int r4 = 0; r4 < NCT; ++r4)
+#pragma unroll
+          for (int nt = 0; nt < NTX; ++nt)
+            bx[r4][nt] = *reinterpret_cast<const f4*>(xt + (16 * nt + j) * LDC + 16 * r4 + 4 * q);
+      }
       if constexpr (!WIDE) {
 #pragma unroll
         for (int nt = 0; nt < NT1; ++nt)
@@ -1431,11 +1582,11 @@ __device__ __forceinline__ void rs_body(const RsArgs& a, float* const lds, const
 #undef RS_STAMP
 }
 
-template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false>
+template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false, int STG = 0>
 __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
   if (blockIdx.x & 7) return;                    // placement hint (update.hip): the working blocks land on one XCD and share its L2
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* const red = lds + RsLds<KIN, NCT>::RED;
+  float* const red = lds + RsLds<KIN, NCT, STG == 1>::RED;
   const int wg = (int)(blockIdx.x >> 3), tid = threadIdx.x;
   // ---- placement census (update_ks.hip): do all workgroups of the launch share one XCD (one L2)?  Checked, once per launch,
   // over words every placement delivers; not co-resident (or SPO_RS_SAFE=1): write-through exchange stores, same results.
@@ -1462,8 +1613,8 @@ __global__ __launch_bounds__(512) void ppo_update_rs_kernel(RsArgs a) {
     fast = (red[96] == 0.f) && !a.force_safe;
     __syncthreads();
   }
-  if (fast) rs_body<KIN, R, true, PROF, XW, NCT, false, L1P>(a, lds);
-  else rs_body<KIN, R, false, PROF, XW, NCT, false, L1P>(a, lds);
+  if (fast) rs_body<KIN, R, true, PROF, XW, NCT, false, L1P, STG>(a, lds);
+  else rs_body<KIN, R, false, PROF, XW, NCT, false, L1P, STG>(a, lds);
 }
 
 // ---- replica-batched launch: S independent PPO-Lagrangian runs (own parameters, buffers, optimiser state) take their minibatch
@@ -1528,7 +1679,7 @@ __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiE
 
 // Exchange scratch: the partial-gradient slots and the norm granules, ordinary device memory.  One block per (device, stream),
 // allocated on first use (update_ks.hip's scheme): launches on one stream are ordered and share it.
-struct RsEntry { int dev; void* stream; char* base; unsigned tag; };
+struct RsEntry { int dev; void* stream; char* base; unsigned tag; char* stage; size_t stage_bytes; };   // stage: the staged-input block (grown on demand)
 constexpr int RS_SCRATCH_MAX = 16;
 RsEntry g_rs[RS_SCRATCH_MAX] = {};
 int g_rs_n = 0;
@@ -1554,7 +1705,7 @@ int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* t
     if (int rc = spo::hip_check(hipMalloc(&p, RS_Z_MAX + RS_G_BYTES), "hipMalloc(rs scratch)")) return rc;
     if (int rc = spo::hip_check(hipMemset(p, 0, RS_Z_MAX + RS_G_BYTES), "hipMemset(rs scratch)")) { (void)hipFree(p); return rc; }
     if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(rs scratch)")) { (void)hipFree(p); return rc; }
-    g_rs[g_rs_n] = RsEntry{dev, (void*)st, static_cast<char*>(p), 16u};
+    g_rs[g_rs_n] = RsEntry{dev, (void*)st, static_cast<char*>(p), 16u, nullptr, 0};
     e = &g_rs[g_rs_n++];
   }
   *z = reinterpret_cast<float*>(e->base);
@@ -1562,6 +1713,64 @@ int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* t
   *tag_base = e->tag;
   e->tag += nsteps + 2u;                           // (wraps after 4e9 steps: a tag then meets words 2^32 steps old)
   return 0;
+}
+
+// The staged-input block of the stream's scratch entry (made by rs_scratch just before), at least `bytes` long: grown on demand
+// (hipFree waits for the launches that still read the old block), never inside a capture -- *out stays null there unless the
+// block is already large enough, and the launch takes the in-kernel gather.
+int rs_stage_block(hipStream_t st, size_t bytes, char** out) {
+  *out = nullptr;
+  const int dev = current_device_slot();
+  std::lock_guard<std::mutex> lk(g_rs_mu);
+  RsEntry* e = nullptr;
+  for (int i = 0; i < g_rs_n; ++i)
+    if (g_rs[i].dev == dev && g_rs[i].stream == (void*)st) e = &g_rs[i];
+  if (!e) return spo::fail(-1, "row-split update kernel: no scratch entry for this stream");
+  if (e->stage_bytes < bytes) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+    if (e->stage) {
+      (void)spo::hip_check(hipFree(e->stage), "hipFree(rs stage)");
+      e->stage = nullptr; e->stage_bytes = 0;
+    }
+    void* p = nullptr;
+    if (int rc = spo::hip_check(hipMalloc(&p, bytes), "hipMalloc(rs stage)")) return rc;
+    e->stage = static_cast<char*>(p); e->stage_bytes = bytes;
+  }
+  *out = e->stage;
+  return 0;
+}
+
+int g_rs_last_staged[SPO_MAX_DEVICES] = {};      // form of the last rs_update_launch per device: 0 in-kernel gather, 1 / 2 staged (STG)
+
+size_t rs_stage_record_bytes(int obs_dim) {
+  return obs_dim <= 16 ? RsStage<16>::BYTES : obs_dim <= 32 ? RsStage<32>::BYTES : RsStage<64>::BYTES;
+}
+
+// SPO_RS_STAGE (read at every launch): 0 = in-kernel gather; 2 = staged inputs with the x^T operand of dW1 kept as an LDS image
+// (built for the default form only: KIN = 64, two-batch hand-off; elsewhere it means 1); anything else / unset = staged inputs,
+// x^T from the record.  SPO_RS_STAGE_MAX_MB: the largest staging block a launch may ask for (default 1024).
+int rs_stage_form() {
+  const char* e = getenv("SPO_RS_STAGE");
+  if (e && *e == '0') return 0;
+  return (e && *e == '2') ? 2 : 1;
+}
+size_t rs_stage_max_bytes() {
+  const char* e = getenv("SPO_RS_STAGE_MAX_MB");
+  const long long mb = (e && *e) ? atoll(e) : 1024;
+  return mb <= 0 ? 0 : (size_t)mb << 20;
+}
+
+template <int KIN>
+int rs_stage_launch_k(const RsArgs& a, char* out, int64_t nsteps, hipStream_t st) {
+  hipLaunchKernelGGL((rs_stage_inputs_kernel<KIN>), dim3((unsigned)nsteps), dim3(256), 0, st, a.obs, a.act, a.logp_old, a.adv, a.tgt_r,
+                     a.tgt_c, a.perm, a.M, a.cfg.obs_dim, a.cfg.act_dim, a.cfg.batch, out);
+  return 0;
+}
+int rs_stage_launch(const RsArgs& a, char* out, int64_t nsteps, hipStream_t st) {
+  const int D = a.cfg.obs_dim;
+  return D <= 16 ? rs_stage_launch_k<16>(a, out, nsteps, st) : D <= 32 ? rs_stage_launch_k<32>(a, out, nsteps, st)
+                                                                        : rs_stage_launch_k<64>(a, out, nsteps, st);
 }
 
 // SPO_RS_L1_PIPE (read at every launch, like SPO_RS_SAFE): 0 = layer 1's hand-off in one batch (the form before the two-batch
@@ -1588,18 +1797,18 @@ float rs_clip_threshold(float mg) {
   return thr;
 }
 
-template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false>
+template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false, int STG = 0>
 int rs_launch_k(const RsArgs& a, hipStream_t st) {
-  const size_t sh = RsLds<KIN, NCT>::SIZE * sizeof(float);
+  const size_t sh = RsLds<KIN, NCT, STG == 1>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
   const int dslot = current_device_slot();
   if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P, STG>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs)");
     attr_done[dslot] = true;
   }
-  hipLaunchKernelGGL((ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P>), dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), sh, st, a);
+  hipLaunchKernelGGL((ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P, STG>), dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), sh, st, a);
   return 0;
 }
 
@@ -1611,6 +1820,7 @@ int spo::rs_scratch_release(int dev, void* stream_or_null, int all) {
   for (int i = 0; i < g_rs_n;) {
     if (g_rs[i].dev == dev && (all || g_rs[i].stream == stream_or_null)) {
       (void)spo::hip_check(hipFree(g_rs[i].base), "hipFree(rs scratch)");
+      if (g_rs[i].stage) (void)spo::hip_check(hipFree(g_rs[i].stage), "hipFree(rs stage)");
       g_rs[i] = g_rs[--g_rs_n];
       ++freed;
     } else ++i;
@@ -1652,6 +1862,35 @@ int spo::rs_row_groups(int obs_dim, int batch) {
   return (batch <= 64 && !rows16) ? 2 : 4;
 }
 
+// Bytes of the staging block a launch of M samples needs: one record per minibatch step; 0 where the staged form does not apply
+// (more than 64 observations, more than two row groups -- batch > 64: the critic fit's 128-row minibatches; SPO_RS_ROWS=16).
+extern "C" int64_t spo_rs_stage_bytes(int obs_dim, int act_dim, int batch, int64_t M) {
+  if (obs_dim < 1 || obs_dim > 64 || act_dim < 1 || act_dim > SPO_MAX_ACT || batch < 1 || batch > 64 || M < 1) return 0;
+  if (spo::rs_row_groups(obs_dim, batch) != 2) return 0;
+  const int64_t nsteps = (M + batch - 1) / batch;
+  return nsteps * (int64_t)rs_stage_record_bytes(obs_dim);
+}
+
+// Form of the last row-split launch on the current device: 0 = in-kernel gather, 1 = staged inputs, 2 = staged with the LDS image.
+extern "C" int spo_debug_rs_last_staged(void) { return g_rs_last_staged[current_device_slot()]; }
+
+// The staging kernel alone, into a caller's device buffer of at least spo_rs_stage_bytes(...) bytes (16-byte aligned).
+extern "C" int spo_debug_rs_stage(const float* obs, const float* act, const float* logp_old, const float* target_r,
+                                  const float* target_c, const float* adv, const int32_t* perm, int64_t M, int obs_dim,
+                                  int act_dim, int batch, void* out_dev, int64_t out_bytes, void* stream) {
+  SPO_REQUIRE(obs && act && logp_old && target_r && target_c && adv && perm && out_dev, "rs_stage: null pointer");
+  const int64_t need = spo_rs_stage_bytes(obs_dim, act_dim, batch, M);
+  SPO_REQUIRE(need > 0, "rs_stage: no staged form for obs_dim %d, act_dim %d, batch %d", obs_dim, act_dim, batch);
+  SPO_REQUIRE(out_bytes >= need, "rs_stage: the buffer holds %lld bytes, %lld needed", (long long)out_bytes, (long long)need);
+  SPO_REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 15) == 0, "rs_stage: the buffer is not 16-byte aligned");
+  RsArgs a{};
+  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv; a.perm = perm; a.M = M;
+  a.cfg.obs_dim = obs_dim; a.cfg.act_dim = act_dim; a.cfg.batch = batch;
+  if (int rc = rs_stage_launch(a, static_cast<char*>(out_dev), (M + batch - 1) / batch, (hipStream_t)stream)) return rc;
+  SPO_LAUNCH_CHECK("spo_debug_rs_stage");
+  return 0;
+}
+
 // Called by spo_ppo_lag_update_iter / spo_critic_fit_iter (update.hip) when the shape is supported and SPO_UPDATE_FORM selects it.
 int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host, const float* obs, const float* act,
                           const float* logp_old, const float* target_r, const float* target_c, const float* adv,
@@ -1682,6 +1921,23 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
   if (int rc = spo::hip_check(hipMemsetAsync(a.zbuf, 0xFF, R == 2 ? rs_z_bytes(2) : rs_z_bytes(4), st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = cfg_host->obs_dim <= 16 ? 16 : cfg_host->obs_dim <= 32 ? 32 : cfg_host->obs_dim <= 64 ? 64 : 128;
+  // ---- staged inputs (the PPO-Lagrangian step, two row groups, KIN <= 64): the pre-pass on this stream, then the STG kernel.
+  // (SPO_RS_L1_PIPE=0 at KIN = 64, the one-batch A/B form, has no STG instantiation: it gathers in the kernel as before.)
+  int stg = 0;
+  if (n_nets == 3 && !(kin == 64 && !l1p) && (stg = rs_stage_form()) != 0) {
+    const size_t bytes = (size_t)spo_rs_stage_bytes(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, M);
+    char* block = nullptr;
+    if (bytes != 0 && bytes <= rs_stage_max_bytes() && bytes < ((size_t)1 << 31))
+      if (int rc = rs_stage_block(st, bytes, &block)) return rc;
+    if (block) {
+      if (int rc = rs_stage_launch(a, block, nsteps, st)) return rc;
+      a.stage = block; a.stage_bytes = (unsigned)bytes;
+      if (kin != 64) stg = 1;                                              // (the LDS-image form exists for the default kernel only)
+    } else {
+      stg = 0;
+    }
+  }
+  g_rs_last_staged[current_device_slot()] = stg;
   if (kin == 128) {
     // one instantiation: 32 rows per workgroup (SPO_RS_ROWS=16 is not read above 64 observations) and no instrumented build --
     // a profile buffer set through spo_debug_set_update_profile is left untouched by these launches (tools/phase_profile_rs.py
@@ -1693,6 +1949,12 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
 #define RS_GO(K)                                                                                  \
   {                                                                                               \
     if (rows16) { if (prof && K == 64) return rs_launch_k<K, 4, (K == 64), 0, 1>(a, st); return rs_launch_k<K, 4, false, 0, 1>(a, st); } \
+    if (R == 2 && stg) {                                                                          \
+      /* staged inputs (KIN = 64: the two-batch form only); the instrumented instantiation as below */ \
+      if (prof && K == 64) return rs_launch_k<K, 2, (K == 64), 0, 2, (K == 64), 1>(a, st);        \
+      if (stg == 2 && K == 64) return rs_launch_k<K, 2, false, 0, 2, (K == 64), (K == 64 ? 2 : 1)>(a, st); \
+      return rs_launch_k<K, 2, false, 0, 2, (K == 64), 1>(a, st);                                 \
+    }                                                                                             \
     if (R == 2) {                                                                                 \
       /* the instrumented instantiations of the default form (KIN = 64, two row groups), only with a profile buffer set */ \
       if (prof && K == 64) return l1p ? rs_launch_k<K, 2, (K == 64), 0, 2, (K == 64)>(a, st) : rs_launch_k<K, 2, (K == 64)>(a, st); \

@@ -132,6 +132,9 @@ PROTOTYPES = {
     "spo_ks_supported": (c_int, [c_int, c_int, c_int]),
     "spo_update_rs_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "spo_update_rs128_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_rs_stage_bytes": (c_int64, [c_int, c_int, c_int, c_int64]),
+    "spo_debug_rs_last_staged": (c_int, []),
+    "spo_debug_rs_stage": (c_int, [P] * 7 + [c_int64, c_int, c_int, c_int, P, c_int64, P]),
     "spo_ppo_lag_update_iter_multi": (c_int, [POINTER(UpdateReplica), c_int, c_int64, P]),
     "spo_update_rs_multi_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "spo_update_rs_multi_matches_single": (c_int, [c_int, c_int, c_int]),
