@@ -434,6 +434,31 @@ int spo_cpo128_linesearch_eval(const float* theta, const float* obs, const float
                                int64_t rows, int obs_dim, int act_dim, double* partial_ws, int partial_capacity,
                                double* sums3_out, void* stream);
 
+/* ---- CPO full-batch primitives for obs_dim 129..512 and act_dim 1..32 (HumanoidVelocity's 376 / 17 in
+ * single_agent/benchmark.py:5-44), hidden [64, 64]: W1 is streamed through LDS in 64-feature slices, the output layer is
+ * two 16-row tiles.  Same argument meaning, layouts and workspaces as their spo_cpo128_* namesakes; obs_dim / act_dim
+ * outside that range fail with -2, naming the dimension, before any device work.
+ *   spo_cpo512_supported        1 exactly for 129 <= obs_dim <= 512 and 1 <= act_dim <= 32 (host code, no GPU needed)
+ *   spo_cpo512_num_partials     workgroups = partial vectors for `rows` rows (sizes partial_ws / loss_ws)
+ *   spo_cpo512_surrogate_grad   cpo.py:356-365, :372-381
+ *   spo_cpo512_fvp              cpo.py:132-157 (one launch + the fixed-order reduction)
+ *   spo_cpo512_linesearch_eval  cpo.py:473-491
+ *   spo_cpo512_actor_mean       cpo.py:361: mean_out[rows, act_dim] = actor.mean(obs), by the forward pass of
+ *                               spo_cpo512_linesearch_eval (same products, same order: KL == 0.0 at unchanged parameters) */
+int spo_cpo512_supported(int obs_dim, int act_dim);
+int spo_cpo512_num_partials(int64_t rows);
+int spo_cpo512_surrogate_grad(const float* theta, const float* obs, const float* act, const float* logp_old,
+                              const float* adv, float sign, int64_t rows, int obs_dim, int act_dim,
+                              float* partial_ws, double* loss_ws, float* grad_out, double* loss_sum_out, void* stream);
+int spo_cpo512_fvp(const float* theta, const float* obs, const float* vec, int64_t rows, int obs_dim, int act_dim,
+                   float* partial_ws, double* loss_ws, float* out, void* stream);
+int spo_cpo512_linesearch_eval(const float* theta, const float* obs, const float* act, const float* logp_old,
+                               const float* adv_r, const float* adv_c, const float* mean_old, const float* log_std_old,
+                               int64_t rows, int obs_dim, int act_dim, double* partial_ws, int partial_capacity,
+                               double* sums3_out, void* stream);
+int spo_cpo512_actor_mean(const float* theta, const float* obs, float* mean_out, int64_t rows, int obs_dim, int act_dim,
+                          void* stream);
+
 int spo_critic_fit_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                         const float* obs, const float* target_r, const float* target_c, const int32_t* perm,
                         int64_t M, const spo_ppo_cfg* cfg_host, float* stale_sq_io, float* losses_out,

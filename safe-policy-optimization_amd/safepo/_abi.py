@@ -171,6 +171,12 @@ PROTOTYPES = {
     "spo_cpo128_surrogate_grad": (c_int, [P] * 5 + [c_float, c_int64, c_int, c_int, P, P, P, P, P]),
     "spo_cpo128_fvp": (c_int, [P, P, P, c_int64, c_int, c_int, P, P, P, P]),
     "spo_cpo128_linesearch_eval": (c_int, [P] * 8 + [c_int64, c_int, c_int, P, c_int, P, P]),
+    "spo_cpo512_supported": (c_int, [c_int, c_int]),
+    "spo_cpo512_num_partials": (c_int, [c_int64]),
+    "spo_cpo512_surrogate_grad": (c_int, [P] * 5 + [c_float, c_int64, c_int, c_int, P, P, P, P, P]),
+    "spo_cpo512_fvp": (c_int, [P, P, P, c_int64, c_int, c_int, P, P, P, P]),
+    "spo_cpo512_linesearch_eval": (c_int, [P] * 8 + [c_int64, c_int, c_int, P, c_int, P, P]),
+    "spo_cpo512_actor_mean": (c_int, [P, P, P, c_int64, c_int, c_int, P]),
     "spo_critic_fit_iter": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,
                                    c_float, c_float, c_int, P, P, P]),

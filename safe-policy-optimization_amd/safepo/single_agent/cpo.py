@@ -540,7 +540,9 @@ class WideCPOEngine(_WideOps, CPOEngine):
       line search sums     spo_mlp_forward -> spo_wide_linesearch_sums                                  (cpo.py:473-491)
     With hidden [64, 64], 65 <= obs_dim <= 128 and act_dim <= 16 (Car / Racecar / Doggo / Ant) the three primitives run on the
     KIN = 128 forms of the LDS-resident full-batch kernels instead (spo_cpo128_*: whole local batch per call, no row chunks;
-    `_actor_on_full_batch_kernels`; SPO_CPO_OBS128=0 keeps the chunked wide path).
+    `_actor_on_full_batch_kernels`; SPO_CPO_OBS128=0 keeps the chunked wide path).  With hidden [64, 64], 129 <= obs_dim <= 512
+    and act_dim <= 32 (HumanoidVelocity: 376 / 17) they run on the streamed-W1 forms (spo_cpo512_*: W1 in 64-feature slices through
+    LDS, two output tiles; `_actor_on_streamed_kernels`; SPO_CPO_OBS512=0 keeps the chunked wide path).
     The critic fit keeps the persistent two-critic kernel whenever the CRITICS fit it (hidden [64, 64], obs_dim <= 128: their
     layout does not depend on act_dim), else runs minibatch by minibatch on the wide kernels with the actor's stale gradient
     kept in the flat gradient vector so the joint clip sees and rescales it (cpo.py:557).  Data-parallel like CPOEngine: the
@@ -565,18 +567,31 @@ class WideCPOEngine(_WideOps, CPOEngine):
         self._actor_on_full_batch_kernels = (list(policy.hidden_sizes) == [64, 64]
                                              and bool(self.lib.spo_cpo128_supported(self.D, self.A))
                                              and os.environ.get("SPO_CPO_OBS128", "1") != "0")
-        if self._actor_on_full_batch_kernels:
-            nparts = self.lib.spo_cpo128_num_partials(self.M)
+        self._actor_on_streamed_kernels = (list(policy.hidden_sizes) == [64, 64]
+                                           and bool(self.lib.spo_cpo512_supported(self.D, self.A))
+                                           and os.environ.get("SPO_CPO_OBS512", "1") != "0")
+        if self._actor_on_full_batch_kernels or self._actor_on_streamed_kernels:
+            nparts = (self.lib.spo_cpo512_num_partials if self._actor_on_streamed_kernels
+                      else self.lib.spo_cpo128_num_partials)(self.M)
             self.partial_ws = torch.empty(nparts * self.Pa, dtype=torch.float32, device=self.dev)
             self.loss_ws = torch.empty(nparts, dtype=torch.float64, device=self.dev)
 
     def _alloc_full_batch_workspaces(self) -> None:
-        self.partial_ws = self.loss_ws = None           # allocated in __init__ when the KIN = 128 full-batch kernels are used
+        self.partial_ws = self.loss_ws = None           # allocated in __init__ when the full-batch kernels are used
 
     def snapshot_old_distribution(self) -> None:
         if self._actor_on_full_batch_kernels:
             # the means the line-search kernel will reproduce bit for bit at unchanged parameters (same LDS-resident forward)
             return PPOLagEngine.snapshot_old_distribution(self)
+        if self._actor_on_streamed_kernels:
+            # ... and here by the streamed forward the line-search kernel shares with spo_cpo512_actor_mean
+            _abi.check(self.lib.spo_cpo512_actor_mean(_abi.ptr(self.policy.theta), _abi.ptr(self.buffer.data["obs"]),
+                                                      _abi.ptr(self.mean_old), self.M, self.D, self.A, _abi.stream_ptr()),
+                       "spo_cpo512_actor_mean")
+            off = self.policy.log_std_offset
+            self.logstd_old.copy_(self.policy.theta[off:off + self.A])
+            torch.exp(self.logstd_old, out=self.std_old)
+            return None
         return super().snapshot_old_distribution()
 
     def _feature_split_critic_fit_ok(self, cfg) -> bool:
@@ -598,13 +613,15 @@ class WideCPOEngine(_WideOps, CPOEngine):
         return self.policy.theta[self.ls_off:self.ls_off + self.A]
 
     def _surrogate_grad_local(self, adv: torch.Tensor, sign: float) -> torch.Tensor:
-        if self._actor_on_full_batch_kernels:
+        if self._actor_on_full_batch_kernels or self._actor_on_streamed_kernels:
+            fn, name = ((self.lib.spo_cpo512_surrogate_grad, "spo_cpo512_surrogate_grad") if self._actor_on_streamed_kernels
+                        else (self.lib.spo_cpo128_surrogate_grad, "spo_cpo128_surrogate_grad"))
             d = self.buffer.data
             g = torch.empty(self.Pa, dtype=torch.float32, device=self.dev)
-            _abi.check(self.lib.spo_cpo128_surrogate_grad(
+            _abi.check(fn(
                 _abi.ptr(self.policy.theta), _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"]),
                 _abi.ptr(adv), float(sign), self.M, self.D, self.A, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws),
-                _abi.ptr(g), _abi.ptr(self.loss_sum), _abi.stream_ptr()), "spo_cpo128_surrogate_grad")
+                _abi.ptr(g), _abi.ptr(self.loss_sum), _abi.stream_ptr()), name)
             return g
         w, lib, d = self.wide, self.lib, self.buffer.data
         adv, logp_old = adv.reshape(-1), d["log_prob"].view(-1)
@@ -624,11 +641,13 @@ class WideCPOEngine(_WideOps, CPOEngine):
         return g
 
     def _fvp_local(self, v: torch.Tensor) -> torch.Tensor:
-        if self._actor_on_full_batch_kernels:
+        if self._actor_on_full_batch_kernels or self._actor_on_streamed_kernels:
+            fn, name = ((self.lib.spo_cpo512_fvp, "spo_cpo512_fvp") if self._actor_on_streamed_kernels
+                        else (self.lib.spo_cpo128_fvp, "spo_cpo128_fvp"))
             out = torch.empty(self.Pa, dtype=torch.float32, device=self.dev)
-            _abi.check(self.lib.spo_cpo128_fvp(_abi.ptr(self.policy.theta), _abi.ptr(self.buffer.data["obs"]), _abi.ptr(v),
+            _abi.check(fn(_abi.ptr(self.policy.theta), _abi.ptr(self.buffer.data["obs"]), _abi.ptr(v),
                                                self.M, self.D, self.A, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws),
-                                               _abi.ptr(out), _abi.stream_ptr()), "spo_cpo128_fvp")
+                                               _abi.ptr(out), _abi.stream_ptr()), name)
             return out
         w, lib = self.wide, self.lib
         tangent = v[self.A:].contiguous()
@@ -647,13 +666,15 @@ class WideCPOEngine(_WideOps, CPOEngine):
         return out
 
     def _linesearch_sums_local(self, adv_a, adv_b) -> None:
-        if self._actor_on_full_batch_kernels:
+        if self._actor_on_full_batch_kernels or self._actor_on_streamed_kernels:
+            fn, name = ((self.lib.spo_cpo512_linesearch_eval, "spo_cpo512_linesearch_eval") if self._actor_on_streamed_kernels
+                        else (self.lib.spo_cpo128_linesearch_eval, "spo_cpo128_linesearch_eval"))
             d = self.buffer.data
-            _abi.check(self.lib.spo_cpo128_linesearch_eval(
+            _abi.check(fn(
                 _abi.ptr(self.policy.theta), _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"]),
                 _abi.ptr(adv_a), _abi.ptr(adv_b), _abi.ptr(self.mean_old), _abi.ptr(self.logstd_old),
                 self.M, self.D, self.A, _abi.ptr(self.ls_partials), self.ls_partials.numel(), _abi.ptr(self.ls_sums),
-                _abi.stream_ptr()), "spo_cpo128_linesearch_eval")
+                _abi.stream_ptr()), name)
             return
         w, lib, d = self.wide, self.lib, self.buffer.data
         adv_a, adv_b, logp_old = adv_a.reshape(-1), adv_b.reshape(-1), d["log_prob"].view(-1)
