@@ -675,6 +675,60 @@ int spo_critic_fit_iter_split(float* theta0, float* adam_m0, float* adam_v0, flo
                               float* stale_sq_io0, float* stale_sq_io1, float* losses0, float* losses1, void* sync_ws0,
                               void* sync_ws1, void* const* regions2, uint32_t step0, void* stream);
 int spo_p2p_selftest_one_grid(void* const* regions2, uint32_t step0, int iters, int32_t* result4_dev, void* stream);
+
+/* Seed-batched one-grid split critic fit (cpo.py:534-571 at batch_size 128 and 65-128 observations -- the Car / Racecar / Doggo /
+ * Ant tasks of the default sweep, single_agent/benchmark.py:5-44): the spo_critic_fit_iter_split launches of S INDEPENDENT runs
+ * (own critics and second replica, optimiser state, buffers, shuffle, cfg scalars, stale actor-gradient norms, exchange regions,
+ * step tag) as ONE persistent launch per critic-fit iteration.  Run r has four workgroups of its own on XCD label r mod 8
+ * (workgroups 0, 1: the first replica's two critics on rows perm0; 2, 3: the second's on perm1), runs r, r + 8, ... share an XCD.
+ * Per run the arithmetic is spo_critic_fit_iter_split's, bit for bit: the same step body and the same placement census, taken per
+ * run -- a run whose four workgroups sit on one XCD exchanges through that XCD's L2 (a cached pair of regions the library owns),
+ * any other through its own uncached pair regions2[0..1]; SPO_CPO_SPLIT_L2=0 puts every run on the uncached pair.  At most 32
+ * runs: four per XCD are 16 working blocks of one CU each on an XCD's 32 CUs (the other batched launches stop at 24).
+ * The library keeps one block per (device, stream) for this launch: per run a cached pair of exchange regions (the prefix the
+ * world-2 doubling form touches, 2 x 3 194 880 bytes), the clip-norm granules of both replicas (256 bytes), 256 bytes of census
+ * words and a census tag, then the argument table -- 6 390 016 cleared bytes per run, 204.5 MB at 32 runs; allocated at the first
+ * call and grown to the largest S seen (never under stream capture; the call itself is refused there: its argument table is
+ * copied from host memory), cleared for the S runs of a launch by one memset, freed by spo_update_scratch_release.
+ * Of sync_ws0 / sync_ws1 only the error words (the int at byte 64) are used.  A run with active == 0 is skipped: nothing of it is
+ * read or written, and its pointers may be NULL. */
+#define SPO_CRITIC_SPLIT_MAX_REPLICAS 32
+typedef struct {
+  float *theta0, *adam_m0, *adam_v0;       /* first replica: the run's own parameters and moments */
+  float *theta1, *adam_m1, *adam_v1;       /* second replica: a copy of the first at the start of the critic fit */
+  int64_t adam_step;                       /* optimiser steps this run has taken (adam_step_host of spo_critic_fit_iter_split) */
+  const float *obs, *target_r, *target_c;
+  const int32_t *perm0, *perm1;            /* M_half rows each: columns 0-63 / 64-127 of every 128-row minibatch */
+  float *stale_sq_io0, *stale_sq_io1;      /* ||actor.grad||^2 of both replicas, in / out */
+  float *losses0, *losses1;                /* [ceil(M_half / batch)][3] each; columns 0 and 1 are written */
+  void *sync_ws0, *sync_ws1;               /* >= 72 bytes each; only the error word at byte 64 is used */
+  void* regions2[2];                       /* the run's uncached pair (spo_p2p_alloc) */
+  uint32_t step0;                          /* the run's step tag; the launch consumes ceil(M_half / batch) tags from it */
+  spo_ppo_cfg cfg;                         /* obs_dim, act_dim, batch (rows per half, <= 64) equal over the runs */
+  int active;
+} spo_critic_fit_split_replica;
+
+/* One critic-fit iteration (ceil(M_half / batch) steps) for every active run of reps_host[n_replicas] (a HOST array).  Checked on
+ * the host before anything is enqueued: a null table, 1 <= n_replicas <= SPO_CRITIC_SPLIT_MAX_REPLICAS, M_half > 0, equal obs_dim
+ * / act_dim / batch, a supported shape (spo_critic_fit_split_multi_supported), null pointers and a negative adam_step of an active
+ * run, two runs sharing theta or sync_ws (either replica), a run whose two replicas alias, a stream under capture.  All runs
+ * inactive: returns 0 with nothing enqueued. */
+int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replica* reps_host, int n_replicas, int64_t M_half, void* stream);
+
+/* 1 for 65 <= obs_dim <= 128 (the KIN = 128 form; up to 64 observations default routing never takes the split form and
+ * spo_critic_fit_iter_multi covers the range), 1 <= batch <= 64 (rows per half) and 1 <= n_replicas <=
+ * SPO_CRITIC_SPLIT_MAX_REPLICAS. */
+int spo_critic_fit_split_multi_supported(int obs_dim, int batch, int n_replicas);
+
+/* The launch's block -> (run, workgroup 0..3) mapping, the function the kernel itself uses: the grid has 32 * ceil(n_replicas / 8)
+ * blocks; block b has XCD label b & 7 and serves run 8 * ((b >> 3) / 4) + (b & 7) as workgroup (b >> 3) % 4.  Returns 1 and fills
+ * replica / wg, or 0 for a block without work (run >= n_replicas, block outside the grid, or n_replicas outside the cap). */
+int spo_critic_fit_split_multi_block_map(int block, int n_replicas, int* replica, int* wg);
+
+/* Measurement aid: {launches enqueued, runs that took part, of those: runs whose census chose the shared-L2 body} since the last
+ * reset (out3_host, host array).  The first two are counted on the host; the third is a word per run the kernel stores into,
+ * read back here (synchronises the device once a launch has been made). */
+int spo_debug_critic_fit_split_multi_counters(unsigned long long* out3_host, int reset);
 int spo_ppo_lag_update_iter_dp(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host, const float* obs,
                                const float* act, const float* logp_old, const float* target_r, const float* target_c,
                                const float* adv, const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host,

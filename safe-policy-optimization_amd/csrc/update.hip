@@ -1493,6 +1493,36 @@ __global__ __launch_bounds__(256, 1) void ppo_update_split_kernel(UpdArgs a0, Up
   }
 }
 
+// Seed-batched one-grid split form (spo_critic_fit_iter_split_multi): the split critic fit of S independent runs in ONE launch,
+// run r on its own four workgroups of XCD label r & 7 (rs_multi_map with 4 workgroups per run) -- workgroups 0, 1 run the first
+// replica's arguments, 2, 3 the second's, exactly as ppo_update_split_kernel deals them.  Body and census are the single launch's,
+// unchanged; the census is taken per run, on the run's own words and tag, so every run decides by itself between the shared-L2
+// body and the uncached one.  One run's two argument structs as the kernel reads them from the device table -- each loaded whole
+// from a uniform address and chosen by a block-uniform branch around two calls (see the note above ppo_update_body: no struct is
+// indexed or patched).  Word SPLITM_COUNT_WORD of a run's census words counts its launches on the shared-L2 body (one plain store
+// by one lane of workgroup 0; launches on a stream are ordered, nobody else writes the word).
+struct UpdSplitMultiEntry { UpdArgs a0; UpdArgs a1; int active; };
+constexpr int SPLITM_WGS = 4, SPLITM_COUNT_WORD = 31;
+
+template <int KIN>
+__global__ __launch_bounds__(256, 1) void ppo_update_split_multi_kernel(const UpdSplitMultiEntry* __restrict__ table, int n_replicas) {
+  int rep, wg;
+  if (!rs_multi_map((int)blockIdx.x, n_replicas, SPLITM_WGS, &rep, &wg)) return;
+  if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the run)
+  const UpdArgs a0 = table[rep].a0;              // uniform address: scalar loads, once (the census reads the first replica's words)
+  const bool local = split_census(a0, wg);
+  if (local && wg == 0 && threadIdx.x == 0)
+    st_granule(a0.xr_census + SPLITM_COUNT_WORD, ld_granule(a0.xr_census + SPLITM_COUNT_WORD) + 1ull);
+  if (wg < 2) {
+    if (local) ppo_update_body<KIN, true, false, 0, 4>(a0, wg);
+    else ppo_update_body<KIN, true, false, 0, 2>(a0, wg);
+  } else {
+    const UpdArgs a1 = table[rep].a1;
+    if (local) ppo_update_body<KIN, true, false, 0, 4>(a1, wg - 2);
+    else ppo_update_body<KIN, true, false, 0, 2>(a1, wg - 2);
+  }
+}
+
 // =====================================================================================================================
 // Main + helper waves: ppo_update_h_kernel (512 threads per network).
 //
@@ -3095,6 +3125,122 @@ int exm_release(int dev, void* stream_or_null, int all) {
   return freed;
 }
 
+// Per-run state of the seed-batched split critic fit (spo_critic_fit_iter_split_multi), one block per (device, stream) beside
+// g_split_local, allocated on first use (never under capture), grown to the largest S seen and kept:
+//   [run] { cached exchange region of replica 0, of replica 1 (xr_region[2], [3]), clip-norm granules of replica 0, of replica 1 }
+//   [run] 256 bytes of census words        [run] argument table entry
+// The exchange of this form is recursive doubling at world 2 (xr_allreduce_rd16, LOCAL): one round (k = 0), two networks, two
+// parities -- the slots ((parity * XR_MAX_WORLD + 0) * 3 + net), net < 2, i.e. nothing at or beyond slot XR_MAX_WORLD * 3 + 2 of a
+// region.  So a run's cached region is that PREFIX of an exchange region (26 slots of 122 880 bytes = 3 194 880 bytes instead of
+// XR_REGION_BYTES), and a run costs 2 * 3 194 880 + 256 bytes of cleared state: 6 390 016 bytes, 204.5 MB at 32 runs.  The run
+// parts are contiguous, so ONE hipMemsetAsync clears regions and granules of the S runs of a launch (tags restart with every
+// engine; the granule tags restart at 1 with every launch).  The census words are not cleared: every run has a census tag of
+// its own that goes up with every launch it takes part in.
+constexpr size_t SPLITM_REGION_BYTES = (size_t)(XR_MAX_WORLD * 3 + 2) * XR_SLOT_WORDS * 8;
+constexpr size_t SPLITM_G_BYTES = 128;                                       // [2][4] granules on a line of their own
+constexpr size_t SPLITM_RUN_BYTES = 2 * SPLITM_REGION_BYTES + 2 * SPLITM_G_BYTES;
+constexpr size_t SPLITM_CENSUS_BYTES = 256;
+static_assert(SPLITM_REGION_BYTES <= XR_REGION_BYTES && SPLITM_REGION_BYTES % 4096 == 0, "a prefix of an exchange region");
+static_assert((SPLITM_COUNT_WORD + 1) * 8 <= (int)SPLITM_CENSUS_BYTES && SPLITM_COUNT_WORD >= 16 + 2 * 2, "census words 0-3, 16-19 + counter");
+constexpr int SPLITM_TAB_RING = 4, SPLITM_SCRATCH_MAX = 8;
+struct SplitMultiState {
+  int dev; void* stream; char* base; int cap;
+  unsigned tag[SPO_CRITIC_SPLIT_MAX_REPLICAS];
+  UpdSplitMultiEntry* tab_host; hipEvent_t ev[SPLITM_TAB_RING]; unsigned calls;
+  size_t census_off() const { return (size_t)cap * SPLITM_RUN_BYTES; }
+  size_t table_off() const { return census_off() + (size_t)cap * SPLITM_CENSUS_BYTES; }
+  size_t bytes() const { return table_off() + (size_t)cap * sizeof(UpdSplitMultiEntry); }
+};
+SplitMultiState g_splitm[SPLITM_SCRATCH_MAX] = {};
+int g_splitm_n = 0;
+std::mutex g_splitm_mu;
+std::atomic<unsigned long long> g_splitm_counters[3];    // {launches enqueued, runs that took part, shared-L2 runs of blocks that are gone}
+
+// sum of the runs' shared-L2 counters of one block (synchronises the device); reset: zeroes them
+int splitm_read_l2(SplitMultiState& e, unsigned long long* sum, bool reset) {
+  *sum = 0;
+  if (!e.base || e.cap == 0) return 0;
+  if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(split counters)")) return rc;
+  char* const w = e.base + e.census_off() + (size_t)SPLITM_COUNT_WORD * 8;
+  unsigned long long host[SPO_CRITIC_SPLIT_MAX_REPLICAS];
+  if (int rc = spo::hip_check(hipMemcpy2D(host, 8, w, SPLITM_CENSUS_BYTES, 8, (size_t)e.cap, hipMemcpyDeviceToHost),
+                              "hipMemcpy2D(split counters)")) return rc;
+  for (int r = 0; r < e.cap; ++r) *sum += host[r];
+  if (reset) return spo::hip_check(hipMemset2D(w, SPLITM_CENSUS_BYTES, 0, 8, (size_t)e.cap), "hipMemset2D(split counters)");
+  return 0;
+}
+
+void splitm_free(SplitMultiState& e) {
+  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched split scratch)");
+  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(split replica table)");
+  for (int i = 0; i < SPLITM_TAB_RING; ++i)
+    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(split replica table)");
+  e = SplitMultiState{};
+}
+
+// The caller holds g_splitm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot) and
+// has checked that the stream is not under capture.
+int splitm_scratch(hipStream_t st, int n_replicas, SplitMultiState** out, UpdSplitMultiEntry** tab_host, hipEvent_t* ev) {
+  const int dev = current_device_slot();
+  SplitMultiState* e = nullptr;
+  for (int i = 0; i < g_splitm_n; ++i)
+    if (g_splitm[i].dev == dev && g_splitm[i].stream == (void*)st) e = &g_splitm[i];
+  if (!e) {
+    if (g_splitm_n == SPLITM_SCRATCH_MAX)
+      return spo::fail(-1, "critic_fit_iter_split_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                           "spo_update_scratch_release(stream) for streams that are gone", SPLITM_SCRATCH_MAX);
+    SplitMultiState n{};
+    n.dev = dev; n.stream = (void*)st;
+    void* h = nullptr;
+    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)SPLITM_TAB_RING * SPO_CRITIC_SPLIT_MAX_REPLICAS * sizeof(UpdSplitMultiEntry),
+                                              hipHostMallocDefault), "hipHostMalloc(split replica table)")) return rc;
+    n.tab_host = static_cast<UpdSplitMultiEntry*>(h);
+    for (int i = 0; i < SPLITM_TAB_RING; ++i)
+      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(split replica table)")) {
+        splitm_free(n); return rc;
+      }
+    for (unsigned& t : n.tag) t = 1u;
+    g_splitm[g_splitm_n] = n;
+    e = &g_splitm[g_splitm_n++];
+  }
+  if (n_replicas > e->cap) {
+    // grow: the old block may still be in use by launches on the stream -- hipFree waits for the device; the runs' shared-L2
+    // counts move to the host, their census tags carry on (the new words are zero, a tag is never 0)
+    unsigned long long carry = 0;
+    if (int rc = splitm_read_l2(*e, &carry, false)) return rc;
+    g_splitm_counters[2] += carry;
+    if (e->base) { if (int rc = spo::hip_check(hipFree(e->base), "hipFree(seed-batched split scratch)")) return rc; }
+    e->base = nullptr; e->cap = 0;
+    SplitMultiState sized = *e;
+    sized.cap = n_replicas;
+    void* p = nullptr;
+    if (int rc = spo::hip_check(hipMalloc(&p, sized.bytes()), "hipMalloc(seed-batched split scratch)")) return rc;
+    if (int rc = spo::hip_check(hipMemset(p, 0, sized.bytes()), "hipMemset(seed-batched split scratch)")) { (void)hipFree(p); return rc; }
+    e->base = static_cast<char*>(p); e->cap = n_replicas;
+  }
+  *out = e;
+  const unsigned slot = e->calls++ % SPLITM_TAB_RING;
+  *tab_host = e->tab_host + (size_t)slot * SPO_CRITIC_SPLIT_MAX_REPLICAS;
+  *ev = e->ev[slot];
+  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(split replica table)");    // (never recorded: complete)
+}
+
+int splitm_release(int dev, void* stream_or_null, int all) {
+  std::lock_guard<std::mutex> lk(g_splitm_mu);
+  int freed = 0;
+  for (int i = 0; i < g_splitm_n;) {
+    if (g_splitm[i].dev == dev && (all || g_splitm[i].stream == stream_or_null)) {
+      unsigned long long carry = 0;
+      if (splitm_read_l2(g_splitm[i], &carry, false) == 0) g_splitm_counters[2] += carry;
+      splitm_free(g_splitm[i]);
+      g_splitm[i] = g_splitm[--g_splitm_n];
+      g_splitm[g_splitm_n] = SplitMultiState{};
+      ++freed;
+    } else ++i;
+  }
+  return freed;
+}
+
 }  // namespace
 // Releases the scratch block of (current device, stream) -- or of every stream of the current device when stream_or_null is
 // NULL and all != 0.  The block is keyed by the raw stream handle, so a process that keeps creating and destroying streams
@@ -3116,6 +3262,7 @@ extern "C" int spo_update_scratch_release(void* stream_or_null, int all) {
   freed += spo::rs_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_multi_scratch_release(dev, stream_or_null, all);
   freed += exm_release(dev, stream_or_null, all);
+  freed += splitm_release(dev, stream_or_null, all);
   return freed;
 }
 namespace {
@@ -3834,6 +3981,149 @@ extern "C" int spo_critic_fit_iter_split(float* theta0, float* adam_m0, float* a
   if (kin == 16) SPO_SPLIT(16) else if (kin == 32) SPO_SPLIT(32) else if (kin == 64) SPO_SPLIT(64) else SPO_SPLIT(128)
 #undef SPO_SPLIT
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_split");
+  return 0;
+}
+
+// ---- seed-batched one-grid split critic fit: the launch above for S independent runs in ONE grid (ppo_update_split_multi_kernel)
+extern "C" int spo_critic_fit_split_multi_supported(int obs_dim, int batch, int n_replicas) {
+  return (obs_dim >= 65 && obs_dim <= 128 && batch >= 1 && batch <= 64 && n_replicas >= 1 &&
+          n_replicas <= SPO_CRITIC_SPLIT_MAX_REPLICAS) ? 1 : 0;
+}
+
+extern "C" int spo_critic_fit_split_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
+  if (!replica || !wg || n_replicas < 1 || n_replicas > SPO_CRITIC_SPLIT_MAX_REPLICAS || block < 0 ||
+      block >= spo::rs_multi_grid(n_replicas, SPLITM_WGS)) return 0;
+  return spo::rs_multi_map(block, n_replicas, SPLITM_WGS, replica, wg) ? 1 : 0;
+}
+
+extern "C" int spo_debug_critic_fit_split_multi_counters(unsigned long long* out3_host, int reset) {
+  SPO_REQUIRE(out3_host, "critic_fit_split_multi_counters: null pointer");
+  for (int i = 0; i < 3; ++i) out3_host[i] = reset ? g_splitm_counters[i].exchange(0ull) : g_splitm_counters[i].load();
+  std::lock_guard<std::mutex> lk(g_splitm_mu);
+  if (g_splitm_n == 0) return 0;                                           // (no block: no device access)
+  const int dev = current_device_slot();
+  for (int i = 0; i < g_splitm_n; ++i) {
+    if (g_splitm[i].dev != dev) continue;
+    unsigned long long l2 = 0;
+    if (int rc = splitm_read_l2(g_splitm[i], &l2, reset != 0)) return rc;
+    out3_host[2] += l2;
+  }
+  return 0;
+}
+
+extern "C" int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replica* reps_host, int n_replicas, int64_t M_half,
+                                               void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "critic_fit_iter_split_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_CRITIC_SPLIT_MAX_REPLICAS, "critic_fit_iter_split_multi: %d replicas outside [1, %d]",
+              n_replicas, SPO_CRITIC_SPLIT_MAX_REPLICAS);
+  SPO_REQUIRE(M_half > 0, "critic_fit_iter_split_multi: bad sizes");
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_split_replica& p = reps_host[r];
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "critic_fit_iter_split_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
+                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+  }
+  if (int rc = check_cfg(&c0)) return rc;
+  SPO_REQUIRE(spo_critic_fit_split_multi_supported(c0.obs_dim, c0.batch, n_replicas),
+              "critic_fit_iter_split_multi: no seed-batched split form for obs_dim %d, batch %d per half "
+              "(spo_critic_fit_split_multi_supported: 65 <= obs_dim <= 128, batch <= 64)", c0.obs_dim, c0.batch);
+  SPO_REQUIRE((M_half + c0.batch - 1) / c0.batch < (1ll << 30), "critic_fit_iter_split_multi: too many minibatch steps in one launch");
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_split_replica& p = reps_host[r];
+    if (p.active) {
+      SPO_REQUIRE(p.theta0 && p.adam_m0 && p.adam_v0 && p.theta1 && p.adam_m1 && p.adam_v1 && p.obs && p.target_r && p.target_c &&
+                      p.perm0 && p.perm1 && p.losses0 && p.losses1 && p.sync_ws0 && p.sync_ws1 && p.stale_sq_io0 && p.stale_sq_io1 &&
+                      p.regions2[0] && p.regions2[1], "critic_fit_iter_split_multi: null pointer in replica %d", r);
+      SPO_REQUIRE(p.regions2[0] != p.regions2[1], "critic_fit_iter_split_multi: replica %d: one exchange region twice", r);
+      SPO_REQUIRE(p.adam_step >= 0, "critic_fit_iter_split_multi: replica %d: negative adam_step", r);
+      ++n_active;
+    }
+    // (a pointer a run that sits out leaves NULL is nobody's: only named arrays are compared)
+    SPO_REQUIRE((!p.theta0 || p.theta0 != p.theta1) && (!p.adam_m0 || p.adam_m0 != p.adam_m1) && (!p.adam_v0 || p.adam_v0 != p.adam_v1) &&
+                    (!p.sync_ws0 || p.sync_ws0 != p.sync_ws1) && (!p.losses0 || p.losses0 != p.losses1) &&
+                    (!p.stale_sq_io0 || p.stale_sq_io0 != p.stale_sq_io1),
+                "critic_fit_iter_split_multi: replica %d: the two halves need separate replicas and outputs", r);
+    for (int q = 0; q < r; ++q) {
+      const spo_critic_fit_split_replica& o = reps_host[q];
+      const void* const th[2] = {p.theta0, p.theta1}, * const oth[2] = {o.theta0, o.theta1};
+      const void* const ws[2] = {p.sync_ws0, p.sync_ws1}, * const ows[2] = {o.sync_ws0, o.sync_ws1};
+      for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j)
+          SPO_REQUIRE(!(th[i] && th[i] == oth[j]) && !(ws[i] && ws[i] == ows[j]),
+                      "critic_fit_iter_split_multi: replicas %d and %d share theta or sync_ws", q, r);
+    }
+  }
+  if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return spo::fail(-1, "critic_fit_iter_split_multi: the stream is under capture (the argument table is copied from host memory "
+                           "at every call and the scratch block may grow: not a graph node)");
+  }
+  static const bool l2_off = [] { const char* e = getenv("SPO_CPO_SPLIT_L2"); return e && !strcmp(e, "0"); }();
+  std::lock_guard<std::mutex> lk(g_splitm_mu);                             // (until the table's copy and its event are enqueued)
+  SplitMultiState* sm = nullptr;
+  UpdSplitMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  if (int rc = splitm_scratch(st, n_replicas, &sm, &tab, &tab_ev)) return rc;
+  char* const base = sm->base;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_split_replica& p = reps_host[r];
+    tab[r] = UpdSplitMultiEntry{};
+    if (!p.active) continue;                                               // (active == 0: the kernel reads nothing else of the entry)
+    char* const run = base + (size_t)r * SPLITM_RUN_BYTES;
+    UpdArgs a{};                                                           // (as spo_critic_fit_iter_split fills the pair)
+    if (int rc = fill_xr(a, 0, 2, p.regions2, p.step0)) return rc;
+    a.theta = p.theta0; a.adam_m = p.adam_m0; a.adam_v = p.adam_v0;
+    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.perm = p.perm0; a.M = M_half; a.cfg = p.cfg;
+    a.losses = p.losses0;
+    a.slots = reinterpret_cast<unsigned long long*>(run + 2 * SPLITM_REGION_BYTES);        // the run's own granules
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws0) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
+    a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
+    a.first_net = 0; a.n_nets = 2; a.stale_sq = 0.f; a.stale_io = p.stale_sq_io0;
+    if (!l2_off) {                                                         // (SPO_CPO_SPLIT_L2=0: every run on the uncached body)
+      a.xr_region[2] = run; a.xr_region[3] = run + SPLITM_REGION_BYTES;
+      a.xr_census = reinterpret_cast<unsigned long long*>(base + sm->census_off() + (size_t)r * SPLITM_CENSUS_BYTES);
+      a.xr_census_tag = sm->tag[r];
+      sm->tag[r] = sm->tag[r] + 1u ? sm->tag[r] + 1u : 1u;                 // (never 0: fresh census words are zero)
+    }
+    UpdArgs b = a;                     // second replica: same data and configuration, its own parameters / rows / outputs
+    b.xr_rank = 1;
+    b.theta = p.theta1; b.adam_m = p.adam_m1; b.adam_v = p.adam_v1; b.perm = p.perm1; b.losses = p.losses1;
+    b.slots = reinterpret_cast<unsigned long long*>(run + 2 * SPLITM_REGION_BYTES + SPLITM_G_BYTES);
+    b.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws1) + 64);
+    b.stale_io = p.stale_sq_io1;
+    tab[r].a0 = a; tab[r].a1 = b; tab[r].active = 1;
+  }
+  UpdSplitMultiEntry* const table_dev = reinterpret_cast<UpdSplitMultiEntry*>(base + sm->table_off());
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(UpdSplitMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(split replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(split replica table)")) return rc;
+  // one clear for the S runs of the launch: cached regions (tags restart with every engine) and granules (tags restart at 1)
+  if (int rc = spo::hip_check(hipMemsetAsync(base, 0, (size_t)n_replicas * SPLITM_RUN_BYTES, st), "hipMemsetAsync(split exchange)"))
+    return rc;
+  {
+    const size_t sh = UpdLds<128>::SIZE * sizeof(float);
+    static bool attr_done[SPO_MAX_DEVICES] = {};
+    const int dslot = current_device_slot();
+    if (!attr_done[dslot]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_split_multi_kernel<128>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update split multi)");
+      attr_done[dslot] = true;
+    }
+    hipLaunchKernelGGL((ppo_update_split_multi_kernel<128>), dim3(spo::rs_multi_grid(n_replicas, SPLITM_WGS)), dim3(256), sh, st,
+                       table_dev, n_replicas);
+  }
+  SPO_LAUNCH_CHECK("spo_critic_fit_iter_split_multi");
+  g_splitm_counters[0] += 1ull;
+  g_splitm_counters[1] += (unsigned long long)n_active;
   return 0;
 }
 

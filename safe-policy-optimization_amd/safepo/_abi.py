@@ -39,6 +39,15 @@ class CriticFitReplica(Structure):
                 ("stale_sq_io", c_void_p), ("sync_ws", c_void_p), ("cfg", PpoCfg), ("active", c_int)]
 
 
+class CriticFitSplitReplica(Structure):
+    """spo_critic_fit_split_replica (include/safepo_hip.h): one run of a seed-batched split critic-fit launch."""
+    _fields_ = [("theta0", c_void_p), ("adam_m0", c_void_p), ("adam_v0", c_void_p), ("theta1", c_void_p), ("adam_m1", c_void_p),
+                ("adam_v1", c_void_p), ("adam_step", c_int64), ("obs", c_void_p), ("target_r", c_void_p), ("target_c", c_void_p),
+                ("perm0", c_void_p), ("perm1", c_void_p), ("stale_sq_io0", c_void_p), ("stale_sq_io1", c_void_p),
+                ("losses0", c_void_p), ("losses1", c_void_p), ("sync_ws0", c_void_p), ("sync_ws1", c_void_p),
+                ("regions2", c_void_p * 2), ("step0", c_uint32), ("cfg", PpoCfg), ("active", c_int)]
+
+
 class UpdateExReplica(Structure):
     """spo_update_ex_replica (include/safepo_hip.h): one run of a seed-batched spo_update_iter_ex launch (FOCOPS, CUP)."""
     _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step_critics", c_int64),
@@ -92,6 +101,7 @@ GAE_PARTIAL_STRIDE = 16                            # include/safepo_hip.h SPO_GA
 RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS_MAX_REPLICAS
 RS_CRITIC_MAX_REPLICAS = 24                        # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 UPDATE_EX_MAX_REPLICAS = 32                        # include/safepo_hip.h SPO_UPDATE_EX_MAX_REPLICAS
+CRITIC_SPLIT_MAX_REPLICAS = 32                     # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -205,6 +215,10 @@ PROTOTYPES = {
     "spo_p2p_selftest_one_grid": (c_int, [POINTER(c_void_p), c_uint32, c_int, P, P]),
     "spo_critic_fit_iter_split": (c_int, [P] * 6 + [c_int64, P, P, P, P, P, c_int64, POINTER(PpoCfg)] + [P] * 6
                                   + [POINTER(c_void_p), c_uint32, P]),
+    "spo_critic_fit_iter_split_multi": (c_int, [POINTER(CriticFitSplitReplica), c_int, c_int64, P]),
+    "spo_critic_fit_split_multi_supported": (c_int, [c_int, c_int, c_int]),
+    "spo_critic_fit_split_multi_block_map": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_critic_fit_split_multi_counters": (c_int, [P, c_int]),
     "spo_critic_fit_iter_dp": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, c_int, c_int,
                                        POINTER(c_void_p), c_uint32, P]),
     "spo_ppo_lag_update_iter_dp": (c_int, [P, P, P, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), P, P,

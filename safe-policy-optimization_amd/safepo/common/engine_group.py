@@ -391,19 +391,32 @@ class CPOEngineGroup(_EngineGroup):
     """S one-GPU CPOEngines (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg) of one shape on one device whose critic fits share ONE
     persistent launch per iteration (spo_critic_fit_iter_multi, csrc/update_rs.hip): run r on its own eight co-XCD workgroups
     (2 critics x 4 row groups), each bit for bit its own spo_critic_fit_iter.  The full-batch actor updates already fill the
-    GPU and stay one run after the other.  `rngs`: one ReplicaRNG per engine -- run i's default shuffle is drawn under rngs[i]."""
+    GPU and stay one run after the other.  `rngs`: one ReplicaRNG per engine -- run i's default shuffle is drawn under rngs[i].
+    `split_form=True` also admits WideCPOEngines whose critics are on the persistent kernel at 65-128 observations (up to 32):
+    their two-replica split critic fits share one launch per iteration (spo_critic_fit_iter_split_multi, csrc/update.hip: run r
+    on its own four co-XCD workgroups), each bit for bit its own spo_critic_fit_iter_split; see batched_split()."""
 
-    def __init__(self, engines, rngs=None):
-        from safepo.single_agent.cpo import CPOEngine
+    def __init__(self, engines, rngs=None, split_form=False):
+        from safepo.single_agent.cpo import CPOEngine, WideCPOEngine
         engines = list(engines)
         if not engines:
             raise ValueError("CPOEngineGroup: no engines")
-        if len(engines) > _abi.RS_CRITIC_MAX_REPLICAS:
-            raise _abi.SpoError(f"CPOEngineGroup: {len(engines)} engines; at most {_abi.RS_CRITIC_MAX_REPLICAS} critic fits share a launch")
+        self.split_form = bool(split_form)
+
+        def takes_split(e):
+            return (self.split_form and type(e) is WideCPOEngine and getattr(e, "_critics_on_persistent_kernel", False)
+                    and 65 <= e.D <= _abi.MAX_OBS)
+
+        # the split form's launch holds up to 32 runs (four workgroups each) at 65-128 observations; everything else 24
+        cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if takes_split(engines[0]) else _abi.RS_CRITIC_MAX_REPLICAS
+        if len(engines) > cap:
+            raise _abi.SpoError(f"CPOEngineGroup: {len(engines)} engines; at most {cap} critic fits share a launch")
         e0 = engines[0]
         for i, e in enumerate(engines):
             if isinstance(e, CPOEngine):
-                if type(e) is not CPOEngine:
+                if takes_split(e):
+                    pass
+                elif type(e) is not CPOEngine:
                     raise _abi.SpoError(f"CPOEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
                                         "CPOEngine (hidden [64, 64], obs_dim <= 64, act_dim <= 16) can be grouped")
                 if e.comm.world_size != 1:
@@ -462,10 +475,116 @@ class CPOEngineGroup(_EngineGroup):
                 e.adam_step += n_mb
         return losses
 
+    # ------------------------------------------------------------------ the two-replica split form (65-128 observations)
+    def batched_split(self) -> bool:
+        """Does critic_fit_all run the split critic fits of all runs as one launch per iteration
+        (spo_critic_fit_iter_split_multi)?  Only in a group built with split_form=True, where every run steps through
+        minibatches of 128 rows that divide its rows, the library has the form for this shape and run count
+        (spo_critic_fit_split_multi_supported) and every engine's own critic_fit would take the split form too
+        (_split_setup() returns its state: the exchange regions and the second replica's arrays)."""
+        if not (self.split_form and self._native):
+            return False
+        es = self.engines
+        if any(int(e.cfg.get("batch_size", 0)) != 128 for e in es) or es[0].M % 128 != 0:
+            return False
+        if not self.lib.spo_critic_fit_split_multi_supported(es[0].D, 64, len(es)):
+            return False
+        return all(e._split_setup() is not None for e in es)
+
+    @staticmethod
+    def _split_cfg(e):
+        """What WideCPOEngine hands the stand-alone split launch: act_dim capped at MAX_ACT (the critics' layout is act-free),
+        64 rows per half."""
+        cfg = e._cfg_struct()
+        cfg.act_dim = min(cfg.act_dim, _abi.MAX_ACT)
+        cfg.batch = 64
+        return cfg
+
+    def fit_iter_split_all(self, perms, active=None):
+        """One iteration of CPOEngine._critic_fit_split's loop for every run i with active[i] in ONE launch: the shuffle cut
+        into its 64-column halves, both replicas stepped, the run's step tag and adam_step advanced.  Returns (l0 + l1) * 0.5
+        per run ([n_mb, 3], columns 0 and 1 are written; None for a run that sat out)."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        if len(perms) != S or len(active) != S:
+            raise ValueError("fit_iter_split_all: one perm and one active flag per engine")
+        e0 = self.engines[0]
+        n_mb, half = e0.M // 128, e0.M // 2
+        reps = (_abi.CriticFitSplitReplica * S)()
+        halves = [None] * S
+        for i, e in enumerate(self.engines):
+            r = reps[i]
+            r.cfg, r.active = self._split_cfg(e), int(active[i])
+            if not active[i]:
+                continue                                    # (a run that sits out names nothing: nothing of it is touched)
+            st, d = e._split_setup(), e.buffer.data
+            perm = _abi.require_gpu_tensor(perms[i], "perm", torch.int32).view(n_mb, 128)
+            p0, p1 = perm[:, :64].contiguous().view(-1), perm[:, 64:].contiguous().view(-1)
+            l0 = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            l1 = torch.empty_like(l0)
+            halves[i] = (p0, p1, l0, l1)
+            r.theta0, r.adam_m0, r.adam_v0 = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
+            r.theta1, r.adam_m1, r.adam_v1 = _abi.ptr(st["theta1"]), _abi.ptr(st["m1"]), _abi.ptr(st["v1"])
+            r.adam_step = e.adam_step
+            r.obs, r.target_r, r.target_c = _abi.ptr(d["obs"]), _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"])
+            r.perm0, r.perm1 = _abi.ptr(p0), _abi.ptr(p1)
+            r.stale_sq_io0, r.stale_sq_io1 = _abi.ptr(e.stale_sq), _abi.ptr(st["stale1"])
+            r.losses0, r.losses1 = _abi.ptr(l0), _abi.ptr(l1)
+            r.sync_ws0, r.sync_ws1 = _abi.ptr(e.sync_ws), _abi.ptr(st["sync_ws"])
+            r.regions2[0], r.regions2[1] = st["regions"][0], st["regions"][1]
+            r.step0 = st["step"] & 0xFFFFFFFF
+        _abi.check(self.lib.spo_critic_fit_iter_split_multi(reps, S, half, _abi.stream_ptr()), "spo_critic_fit_iter_split_multi")
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                e._split_setup()["step"] += n_mb
+                e.adam_step += n_mb
+                losses[i] = (halves[i][2] + halves[i][3]) * 0.5
+        return losses
+
+    def _critic_fit_all_split(self, perm_fns):
+        """critic_fit_all where batched_split(): CPOEngine._critic_fit_split for every run, one launch per iteration.  An
+        exchange error (a workgroup of the launch was not resident) is not degraded to another form: every run's state is
+        restored and the error raised, naming the run."""
+        es, S = self.engines, len(self.engines)
+        sts = [e._split_setup() for e in es]
+        backups = [(e.policy.theta.clone(), e.adam_m.clone(), e.adam_v.clone(), e.stale_sq.clone(), e.adam_step) for e in es]
+        for e, st in zip(es, sts):                      # the second replica starts as a copy of the first
+            st["theta1"].copy_(e.policy.theta); st["m1"].copy_(e.adam_m); st["v1"].copy_(e.adam_v); st["stale1"].copy_(e.stale_sq)
+        n_its = [e.cfg["learning_iters"] for e in es]
+        all_losses = [[] for _ in range(S)]
+        for it in range(max(n_its)):
+            active = [it < n for n in n_its]
+            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
+            losses = self.fit_iter_split_all(perms, active)
+            for i in range(S):
+                if active[i]:
+                    all_losses[i].append(losses[i][:, :2])
+        # WideCPOEngine.check_sync_error is a no-op: both error words of every run, one host read
+        words = [e.sync_ws[8] for e in es] + [st["sync_ws"][8] for st in sts]
+        codes = [int(c) & 0xFFFFFFFF for c in torch.stack([w.to(torch.int64) for w in words]).cpu().tolist()]
+        bad = [i for i in range(S) if codes[i] | codes[S + i]]
+        if bad:
+            for e, st, b in zip(es, sts, backups):
+                e.sync_ws[8] = 0
+                st["sync_ws"][8] = 0
+                e.policy.theta.copy_(b[0]); e.adam_m.copy_(b[1]); e.adam_v.copy_(b[2]); e.stale_sq.copy_(b[3])
+                e.adam_step = b[4]
+            i = bad[0]
+            raise _abi.SpoError(f"replica {i} of {S}: split critic fit: exchange error {codes[i] | codes[S + i]} (the workgroups of "
+                                "the seed-batched launch were not all resident); every run's critics, moments and stale norm are "
+                                "restored to the start of this critic fit")
+        outs = []
+        for ls in all_losses:
+            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
+            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
+        return outs
+
     def critic_fit_all(self, perm_fns=None):
         """CPOEngine.critic_fit for every run: learning_iters iterations each (a run with fewer sits out the later launches),
         every iteration's shuffle drawn per run -- under its ReplicaRNG by default -- before that iteration's launch, as the
-        stand-alone loop draws it.  Where not batched(): each engine's own critic_fit, one after the other -- the same results.
+        stand-alone loop draws it.  Where batched_split() (a split_form group at 65-128 observations): the same loop on the
+        two-replica split form.  Where neither: each engine's own critic_fit, one after the other -- the same results.
         Returns the list of critic_fit()'s dicts."""
         es, S = self.engines, len(self.engines)
 
@@ -479,6 +598,8 @@ class CPOEngineGroup(_EngineGroup):
         if len(perm_fns) != S:
             raise ValueError("critic_fit_all: one perm_fn (or None) per engine")
         perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+        if self.batched_split():
+            return self._critic_fit_all_split(perm_fns)
         if not self.batched():
             return [e.critic_fit(perm_fns[i]) for i, e in enumerate(es)]
         n_its = [e.cfg["learning_iters"] for e in es]

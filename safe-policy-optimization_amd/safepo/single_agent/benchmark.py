@@ -9,7 +9,9 @@ through `--device-id`, and `--workers` defaults to one per GPU.  `--workers 0` o
 cppo_pid -- and ppo / pg -- on the persistent kernels' shapes); the other algorithms, and HumanoidVelocity, keep one subprocess
 per seed.  `--batch-second-order` (default off) lets cpo / pcpo / rcpo / trpo_lag / trpo / natural_pg join that grouping on
 the tasks whose observations fit the persistent CPO kernels (at most 24 seeds per subprocess), with `--batch-critic-fit True`
-on those commands: their critic fits share one persistent launch per iteration.  `--batch-focops-cup` (default off) does the
+on those commands: their critic fits share one persistent launch per iteration; `--batch-second-order-wide-obs` (default off,
+needs `--batch-second-order`) adds the Ant / Car / Doggo / Racecar navigation tasks (65-128 observations, up to 32 seeds per
+subprocess, `--batch-critic-fit True --batch-critic-fit-split True`).  `--batch-focops-cup` (default off) does the
 same for focops / cup with `--batch-update True` (up to 32 seeds per subprocess): their minibatch steps share one persistent launch
 per pass.
 """
@@ -22,7 +24,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from safepo.utils.config import KLPEN_BATCH_FIGURES
+from safepo.utils.config import CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -68,6 +70,11 @@ def parse_args(argv=None):
                         "critic-fit step of ALL seeds takes 9.9 / 11.2 / 14.2 us at 8 / 16 / 24 seeds against 9.8 us per seed one after "
                         "the other (60 / 8; profiles/seed_batch_critic/step_times.txt): the time per seed falls up to the cap, so the "
                         "largest K the sweep has seeds for.  Default off: these algorithms keep one subprocess per seed")
+    p.add_argument("--batch-second-order-wide-obs", action="store_true",
+                   help="with --batch-second-order: also group those scripts on the Ant / Car / Doggo / Racecar navigation tasks (65-128 "
+                        "observations; up to 32 seeds per subprocess, --batch-critic-fit True --batch-critic-fit-split True on those "
+                        "commands): their two-replica split critic fits share one persistent launch per iteration.  "
+                        + CRITIC_SPLIT_BATCH_FIGURES + "  Default off: those tasks keep one subprocess per seed")
     p.add_argument("--batch-focops-cup", action="store_true",
                    help="with --seeds-per-run: also group focops / cup (--batch-update True on those commands; HumanoidVelocity "
                         "excepted).  " + KLPEN_BATCH_FIGURES + "  Default off: these algorithms keep one subprocess per seed")
@@ -79,6 +86,7 @@ CRITIC_BATCHED_ALGOS = ("cpo", "pcpo", "rcpo", "trpo_lag", "trpo", "natural_pg")
 KLPEN_BATCHED_ALGOS = ("focops", "cup")                       # ... with --batch-update True (persistent-kernel shapes only)
 CRITIC_BATCH_MAX = 24                                         # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
+CRITIC_SPLIT_BATCH_MAX = 32                                   # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
 
 
 def _takes_seeds(algo: str, task: str) -> bool:
@@ -96,12 +104,24 @@ def _takes_klpen_batch(algo: str, task: str) -> bool:
 def _takes_critic_batch(algo: str, task: str) -> bool:
     """Can `--seeds ... --batch-critic-fit True` carry several seeds for this (algorithm, task)?  The full-batch CPO kernels of
     CPOEngine end at 64 observations: HumanoidVelocity and the Ant / Car / Doggo / Racecar navigation tasks run on WideCPOEngine."""
-    wide = "Humanoid" in task or ("Velocity" not in task and any(task.startswith(f"Safety{r}") for r in WIDE_OBS_NAV_ROBOTS))
+    wide = "Humanoid" in task or _is_wide_obs_nav(task)
     return algo in CRITIC_BATCHED_ALGOS and not wide
+
+
+def _is_wide_obs_nav(task: str) -> bool:
+    return "Velocity" not in task and any(task.startswith(f"Safety{r}") for r in WIDE_OBS_NAV_ROBOTS)
+
+
+def _takes_critic_split_batch(algo: str, task: str) -> bool:
+    """Can `--seeds ... --batch-critic-fit True --batch-critic-fit-split True` carry several seeds?  The Ant / Car / Doggo /
+    Racecar navigation tasks (65-128 observations: the split critic fit); not HumanoidVelocity (376: the feature-split kernel)."""
+    return algo in CRITIC_BATCHED_ALGOS and _is_wide_obs_nav(task)
 
 
 def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
     n_gpus = n_gpus or visible_gpus()
+    if getattr(args, "batch_second_order_wide_obs", False) and not getattr(args, "batch_second_order", False):
+        raise SystemExit("--batch-second-order-wide-obs widens --batch-second-order: give both")
     per_run = max(getattr(args, "seeds_per_run", 1), 1)
     if per_run > 32:
         raise SystemExit("--seeds-per-run: at most 32 seeds share a launch")
@@ -117,17 +137,22 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                 # one command for the whole group where the script takes --seeds, else one per seed as ever
                 critic = getattr(args, "batch_second_order", False) and _takes_critic_batch(algo, task)
                 klpen = getattr(args, "batch_focops_cup", False) and _takes_klpen_batch(algo, task)
+                split = (getattr(args, "batch_second_order", False) and getattr(args, "batch_second_order_wide_obs", False)
+                         and _takes_critic_split_batch(algo, task))
                 runs = [[s] for s in group]
                 if len(group) > 1 and (_takes_seeds(algo, task) or klpen):
                     runs = [group]
                 elif len(group) > 1 and critic:
                     runs = [group[i:i + CRITIC_BATCH_MAX] for i in range(0, len(group), CRITIC_BATCH_MAX)]
+                elif len(group) > 1 and split:
+                    runs = [group[i:i + CRITIC_SPLIT_BATCH_MAX] for i in range(0, len(group), CRITIC_SPLIT_BATCH_MAX)]
                 for run in runs:
                     batched = len(run) > 1
                     commands.append(" ".join([
                         shlex.quote(sys.executable), shlex.quote(os.path.join(script_dir, f"{algo}.py")), "--task", shlex.quote(task),
                         "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else [])
                         + (["--batch-critic-fit", "True"] if batched and critic else [])
+                        + (["--batch-critic-fit", "True", "--batch-critic-fit-split", "True"] if batched and split else [])
                         + (["--batch-update", "True"] if batched and klpen else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",

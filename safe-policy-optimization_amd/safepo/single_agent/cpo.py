@@ -922,6 +922,9 @@ def main(args, cfg_env=None, _update="cpo"):
     return {"timings": timings, "policy": policy, "engine": engine}
 
 
+CPO_MAX_OBS_GROUP = _abi.CPO_MAX_OBS      # up to here CPOEngine and the 24-run row-split group; above, the split form's 32
+
+
 class _SeedRun:
     """One run of a seed-batched process: what main() holds in local variables, per seed."""
 
@@ -933,13 +936,17 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
     (ReplicaRNG), in the stand-alone order, so each is the stand-alone run of its seed.  Rollout, GAE and the full-batch actor
     update -- kernels that fill the GPU already -- run seed by seed (`rollout(r)` -> next observation, `actor_update(r, epoch)`);
     the critic fits of all seeds run through CPOEngineGroup, one launch per iteration.  The Time/ columns hold the wall time of
-    the phase for ALL seeds of the process."""
+    the phase for ALL seeds of the process.  With `--batch-critic-fit-split True` as well, tasks with 65-128 observations (hidden
+    [64, 64]: WideCPOEngine, whose critic fit takes the two-replica split form) are taken too, up to 32 seeds: their split critic
+    fits share one launch per iteration (CPOEngineGroup(split_form=True))."""
     from safepo.common.engine_group import CPOEngineGroup, ReplicaRNG
     seeds = seed_list(args)
     if len(set(seeds)) != len(seeds):
         raise SystemExit(f"--seeds {seeds}: the same seed twice")
-    if len(seeds) > _abi.RS_CRITIC_MAX_REPLICAS:
-        raise SystemExit(f"--seeds: at most {_abi.RS_CRITIC_MAX_REPLICAS} seeds share the critic fit's launch, got {len(seeds)}")
+    split_form = bool(getattr(args, "batch_critic_fit_split", False))
+    seed_cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if split_form else _abi.RS_CRITIC_MAX_REPLICAS
+    if len(seeds) > seed_cap:
+        raise SystemExit(f"--seeds: at most {seed_cap} seeds share the critic fit's launch, got {len(seeds)}")
     if args.device == "cpu":
         raise RuntimeError("this build runs the CPO hot path on a ROCm GPU only (--device cuda); no CPU fallback")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -969,11 +976,23 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
             r.device_env = getattr(r.env, "is_device_env", False)
             r.policy = ActorVCritic(obs_dim=obs_space.shape[0], act_dim=act_space.shape[0],
                                     hidden_sizes=config["hidden_sizes"]).to(device)
-            if not r.policy.kernels_supported("cpo"):
-                raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "
-                                 f"64, act_dim <= 16); {args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network "
-                                 "kernels: one process per seed")
-            r.engine = CPOEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
+            D = obs_space.shape[0]
+            if split_form and list(config["hidden_sizes"]) == [64, 64] and CPO_MAX_OBS_GROUP < D <= _abi.MAX_OBS:
+                # 65-128 observations: the critics keep the persistent two-critic kernel whatever the actor's width (their layout
+                # is act-free) -- WideCPOEngine, whose critic fit takes the two-replica split form
+                r.engine = make_engine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
+            elif not r.policy.kernels_supported("cpo"):
+                limit = (f"obs_dim <= {_abi.MAX_OBS}, and act_dim <= 16 up to 64 observations" if split_form
+                         else "obs_dim <= 64, act_dim <= 16")
+                raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], {limit}); "
+                                 f"{args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network kernels: one process "
+                                 "per seed")
+            else:
+                if len(seeds) > _abi.RS_CRITIC_MAX_REPLICAS:
+                    raise SystemExit(f"--seeds: at most {_abi.RS_CRITIC_MAX_REPLICAS} seeds share the critic fit's launch up to "
+                                     f"{CPO_MAX_OBS_GROUP} observations ({_abi.CRITIC_SPLIT_MAX_REPLICAS} at 65-128 with "
+                                     f"--batch-critic-fit-split True), got {len(seeds)}")
+                r.engine = CPOEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
             if make_extra is not None:
                 make_extra(r)
             dict_args = dict(vars(args))
@@ -987,7 +1006,7 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
             obs, _ = r.env.reset()
             r.obs = _to_dev(obs, device)
         runs.append(r)
-    group = CPOEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs])
+    group = CPOEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs], split_form=split_form)
 
     timings, outs = [], []
     for epoch in range(epochs):

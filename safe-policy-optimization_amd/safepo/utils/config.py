@@ -73,6 +73,8 @@ def refuse_seed_batch(args, what: str, hint: str = "") -> None:
 def critic_seed_batch(args) -> bool:
     """The second-order scripts (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg): several seeds run in one process only with
     --batch-critic-fit True (their critic fits then share one launch per iteration); without it they are refused as ever."""
+    if getattr(args, "batch_critic_fit_split", False) and not getattr(args, "batch_critic_fit", False):
+        raise SystemExit("--batch-critic-fit-split True widens --batch-critic-fit True (65-128 observations, up to 32 seeds): give both")
     if len(seed_list(args)) <= 1:
         return False
     if not getattr(args, "batch_critic_fit", False):
@@ -86,6 +88,14 @@ CRITIC_BATCH_FIGURES = ("Measured at 60 / 8, 4096 x 128 rows, batch 128: one cri
                         "24 seeds against 9.8 us per seed one after the other (7.9 x / 13.9 x / 16.5 x the aggregate step rate; one seed alone: "
                         "9.90 against 9.76 us, which is why one seed stays `--seed`); cpo's second epoch with 8 seeds: Time/Update 0.56 s "
                         "against 3.35 s (profiles/seed_batch_critic/step_times.txt).")
+
+
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_critic_split/step_times.txt)
+CRITIC_SPLIT_BATCH_FIGURES = ("Measured at 72 / 2, 4096 x 128 rows, batch 128, one GPU: one split critic-fit step of ALL seeds takes 18.3 / 18.5 / "
+                              "19.4 us at 8 / 16 / 32 seeds against 15.7 us per seed one after the other (6.9 x / 13.6 x / 25.9 x the aggregate "
+                              "step rate; one seed alone: 17.75 against 15.74 us, which is why one seed stays `--seed`); cpo's second epoch with "
+                              "8 seeds at 72 observations: Time/Update 0.94 s against 5.34 s, one sample each "
+                              "(profiles/seed_batch_critic_split/step_times.txt).")
 
 
 # (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_klpen/step_times.txt)
@@ -109,6 +119,12 @@ def single_agent_args(argv=None):
                              "process, their critic fits sharing one persistent launch per iteration (up to 24 seeds, eight workgroups "
                              "each, run r on XCD r mod 8; hidden [64, 64], obs_dim <= 64), each seed the run its `--seed` would be.  "
                              + CRITIC_BATCH_FIGURES + "  Default False: several seeds are refused for these scripts")
+    parser.add_argument("--batch-critic-fit-split", type=_bool, default=False,
+                        help="with --batch-critic-fit True: also take tasks with 65-128 observations (hidden [64, 64]: the Ant / Car / "
+                             "Doggo / Racecar navigation tasks), whose critic fit runs the two-replica split form -- the seeds' split "
+                             "critic fits then share one persistent launch per iteration (spo_critic_fit_iter_split_multi: up to 32 "
+                             "seeds, four workgroups each, run r on XCD r mod 8), each seed the run its `--seed` would be.  "
+                             + CRITIC_SPLIT_BATCH_FIGURES + "  Default False: such tasks are refused with several seeds")
     parser.add_argument("--batch-update", type=_bool, default=False,
                         help="focops and cup with --seeds: run the seeds in one process, their minibatch steps sharing one persistent "
                              "launch per pass (spo_update_iter_ex_multi: up to 32 seeds, one workgroup per network each, run r on XCD "
