@@ -616,6 +616,43 @@ int spo_update_iter_ex_ks(float* theta, float* adam_m, float* adam_v, int64_t ad
                           const float* target_r, const float* target_c, const float* adv, const int32_t* perm, int64_t M,
                           const spo_ppo_cfg* cfg_host, int actor_loss, const float* old_mean, const float* old_std,
                           float kl_bound, float pg_coef, int actor_only, float* losses_out, void* sync_ws, void* stream);
+
+/* Seed-batched spo_update_iter_ex_ks (the six first-order scripts at HumanoidVelocity-class dims): S INDEPENDENT runs (own
+ * parameters, optimiser state and clocks, buffers, shuffle, old distribution, kl_bound, pg_coef, cfg scalars) take the minibatch
+ * steps of one learning iteration in ONE launch of the feature-split kernel, every run on workgroups of its own -- (3, or 1 with
+ * actor_only) x ceil(obs_dim / 64) -- of one XCD; run r sits on XCD label r mod 8, runs r and r + 8 share one.  Per run the
+ * semantics and the bits are spo_update_iter_ex_ks's (actor_loss == SPO_ACTOR_LOSS_CLIP with equal clocks:
+ * spo_ppo_lag_update_iter_ks's).  Every run has its own exchange slots, granules and placement census in a block the library owns
+ * (16 x 7 090 176 bytes + the argument table = 113 449 344 bytes per (device, stream), separate from the single launch's scratch;
+ * allocated at the first call together with a pinned host ring of argument tables, never under stream capture; freed by
+ * spo_update_scratch_release) and its own error word, the int at byte 64 of ITS sync_ws; nothing else of sync_ws is touched.  A
+ * run whose exchange times out leaves its parameters and optimiser state untouched and sets its error word; the other runs are
+ * unaffected.  A run with active == 0 is skipped: nothing of it is read or written.  Checked on the host before anything is
+ * enqueued: the replica range (spo_update_ks_multi_supported), equal obs_dim / act_dim / batch, the null pointers
+ * spo_update_iter_ex_ks checks, non-negative clocks, two runs sharing theta or sync_ws, a stream under capture (the argument
+ * table is copied from host memory at every call), ceil(M / batch) < 2^30.  All runs inactive: returns 0 with nothing enqueued.
+ * SPO_KS_SAFE is read as in the single launch; SPO_WIDE_KS is not: the caller decides whether to batch. */
+#define SPO_KS_MAX_REPLICAS 16
+int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss, int actor_only,
+                                void* stream);
+
+/* 1 where spo_ks_supported(obs_dim, act_dim, batch) and 1 <= n_replicas <= min(SPO_KS_MAX_REPLICAS, 8 * (8 / S)) with
+ * S = ceil(obs_dim / 64) and integer division: at most 24 working blocks per XCD label, each on one of that XCD's 32 CUs, so all
+ * workgroups of the launch are co-resident -- 16 runs up to 256 observations, 8 at 257 .. 512.  A run counts as 3 S blocks
+ * whatever actor_only is (one cap for both stages of CUP). */
+int spo_update_ks_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas);
+
+/* The launch's block -> (run, workgroup) mapping, the function the kernel itself uses (testable without a GPU): with
+ * wgs = (actor_only ? 1 : 3) * ceil(obs_dim / 64) workgroups per run the grid has 8 * wgs * ceil(n_replicas / 8) blocks; block b
+ * has XCD label b & 7 and serves run 8 * ((b >> 3) / wgs) + (b & 7) as workgroup (b >> 3) % wgs.  Returns 1 and fills replica /
+ * wg, or 0 for a block without work (run >= n_replicas, block outside the grid, or n_replicas outside the supported range). */
+int spo_update_ks_multi_block_map(int block, int obs_dim, int n_replicas, int actor_only, int* replica, int* wg);
+
+/* Measurement aid: {seed-batched launches enqueued, runs that took part in them, of those: runs whose placement census chose
+ * write-through exchange stores} since the last reset (out3_host, host array).  The third is counted by the kernel in a word per
+ * run; the call synchronises the device to read it. */
+int spo_debug_update_ks_multi_counters(unsigned long long* out3_host, int reset);
+
 /* One minibatch's gradient on the feature-split kernel (round 6: the data-parallel step at these dims): the RAW
  * data gradient (no L2 term, no value coefficient) of the three networks on rows idx[0 .. n), n <= 64, into flat_grad (theta's
  * layout, log_std included) and the three data losses into losses3 -- ppo_lag.py:306-324 up to loss.backward(), the part

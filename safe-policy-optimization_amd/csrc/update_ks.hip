@@ -26,11 +26,13 @@
 // summed slice by slice instead of in one chain (rounding-level difference; tests: 1e-5 on the first steps + the fp64 drift
 // envelope up to 8 192 steps at 524 288 rows x 376).  Two output tiles for the actor (act_dim <= 32).  One GPU.
 #include <cstdlib>
+#include <atomic>
 #include <cstring>
 #include <mutex>
 #include "common.h"
 #include "mlp_mfma.h"
 #include "adam.h"
+#include "update_rs.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -117,14 +119,19 @@ __device__ unsigned long long g_ks_prof[16];      // development builds: cycles 
 // three networks (no L2 term, no value coefficient: spo_wide_clip_adam adds them) goes to a.flat_grad in theta's layout and the
 // three data losses to a.losses; no norm exchange, no Adam, theta untouched.  The per-minibatch kernel of the data-parallel step at
 // these dims: kernel -> all-reduce of the flat gradient -> spo_wide_clip_adam on every rank.
-template <bool FAST, bool CFIT, int AMODE, bool GRAD = false>
-__device__ __forceinline__ void ks_body(const KsArgs& a, float* const lds) {
+// The workgroup index (among the launch's n_nets * S) is a parameter of ks_entry / ks_body: blockIdx.x >> 3 from the single
+// launches, the index rs_multi_map gave the block from the seed-batched ones (MULTI).  Without MULTI entry and body form blockIdx.x >> 3
+// again where they read it instead of keeping the parameter alive across the census: that keeps the four single kernels'
+// instruction text what it was (the value handed down alone cost critic_fit_ks_kernel 13 more spilled SGPRs, a spilled VGPR and
+// ~1 000 instructions; so did a callable passed by value).
+template <bool FAST, bool CFIT, int AMODE, bool GRAD = false, bool MULTI = false>
+__device__ __forceinline__ void ks_body(const KsArgs& a, float* const lds, const int wg_in) {
   using Col = KsCol<AMODE>;
 #ifdef SPO_KS_PROF
   unsigned long long pacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
 #endif
   using L = KsLds;
-  const int wg = (int)(blockIdx.x >> 3);
+  const int wg = MULTI ? wg_in : (int)(blockIdx.x >> 3);
   const int S = a.S, net = a.first_net + wg / S, ks = wg - (wg / S) * S;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), j = lane & 15, q = lane >> 4;
   const int D = a.cfg.obs_dim, A = a.cfg.act_dim, B = a.cfg.batch;
@@ -980,11 +987,13 @@ __device__ __forceinline__ void ks_body(const KsArgs& a, float* const lds) {
   }
 }
 
-template <bool CFIT, int AMODE, bool GRAD = false>
-__device__ __forceinline__ void ks_entry(const KsArgs& a) {
+// wg_in: this workgroup's index among the launch's n_nets * S (the single launches: blockIdx.x >> 3; the seed-batched ones, MULTI: rs_multi_map's)
+// wt_count: seed-batched launches only -- the run's word that counts its launches whose census chose write-through stores
+template <bool CFIT, int AMODE, bool GRAD = false, bool MULTI = false>
+__device__ __forceinline__ void ks_entry(const KsArgs& a, const int wg_in, unsigned* const wt_count = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* const red = lds + KsLds::RED;
-  const int wg = (int)(blockIdx.x >> 3), tid = threadIdx.x, S = a.S;
+  const int wg = MULTI ? wg_in : (int)(blockIdx.x >> 3), tid = threadIdx.x, S = a.S;
   // ---- placement census: do all workgroups of the launch share one XCD (one L2)?  Observed: block b runs on XCD b % 8, which is
   // what the grid of 8-block strides asks for -- but nothing promises it, so it is checked, once per launch, over words every
   // placement delivers (sc1 stores and loads).  Co-resident: stores of the exchange stay plain (the line stays in the shared L2,
@@ -1012,25 +1021,49 @@ __device__ __forceinline__ void ks_entry(const KsArgs& a) {
     fast = (red[250] == 0.f) && !a.force_safe;
     __syncthreads();
   }
-  if (fast) ks_body<true, CFIT, AMODE, GRAD>(a, lds);
-  else ks_body<false, CFIT, AMODE, GRAD>(a, lds);
+  if (wt_count && !fast && wg == 0 && tid == 0) __hip_atomic_fetch_add(wt_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (fast) ks_body<true, CFIT, AMODE, GRAD, MULTI>(a, lds, wg_in);
+  else ks_body<false, CFIT, AMODE, GRAD, MULTI>(a, lds, wg_in);
 }
 
 __global__ __launch_bounds__(256, 1) void ppo_update_ks_kernel(KsArgs a) {
   if (blockIdx.x & 7) return;                    // placement hint (update.hip): the working blocks land on one XCD and share its L2
-  ks_entry<false, 0>(a);
+  ks_entry<false, 0>(a, (int)(blockIdx.x >> 3));
 }
 __global__ __launch_bounds__(256, 1) void klpen_update_ks_kernel(KsArgs a) {
   if (blockIdx.x & 7) return;
-  ks_entry<false, 1>(a);
+  ks_entry<false, 1>(a, (int)(blockIdx.x >> 3));
 }
 __global__ __launch_bounds__(256, 1) void critic_fit_ks_kernel(KsArgs a) {
   if (blockIdx.x & 7) return;
-  ks_entry<true, 0>(a);
+  ks_entry<true, 0>(a, (int)(blockIdx.x >> 3));
 }
 __global__ __launch_bounds__(256, 1) void ppo_grad_ks_kernel(KsArgs a) {
   if (blockIdx.x & 7) return;
-  ks_entry<false, 0, true>(a);
+  ks_entry<false, 0, true>(a, (int)(blockIdx.x >> 3));
+}
+
+// Seed-batched launches (spo_update_iter_ex_ks_multi): S independent runs (own parameters, optimiser state and clocks, buffers,
+// shuffle, scalars, exchange slots, granules, census words, error word) take the minibatch steps of one learning iteration in ONE
+// launch, run r on its own n_nets * S workgroups of XCD label r & 7 (rs_multi_map, update_rs.h).  The step is ks_entry's,
+// unchanged: every run's a.zbuf / a.gran point into a block the library owns, so each run holds its own census and exchanges only
+// with itself.  One run's arguments as the kernel reads them from the device table:
+struct KsMultiEntry { KsArgs a; int active; };
+
+template <int AMODE>
+__device__ __forceinline__ void ks_multi_entry(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
+  int rep, wg;
+  if (!rs_multi_map((int)blockIdx.x, n_replicas, wgs, &rep, &wg)) return;
+  if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the run)
+  const KsArgs a = table[rep].a;                 // uniform address: scalar loads, once
+  // the run's write-through count sits behind its granules and census words (KS_G_BYTES of the run's 4 KB granule page)
+  ks_entry<false, AMODE, false, true>(a, wg, reinterpret_cast<unsigned*>(a.gran + 2 * 2 * 3 * KS_MAX_SLICES + 3 * KS_MAX_SLICES));
+}
+__global__ __launch_bounds__(256, 1) void ppo_update_ks_multi_kernel(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
+  ks_multi_entry<0>(table, n_replicas, wgs);
+}
+__global__ __launch_bounds__(256, 1) void klpen_update_ks_multi_kernel(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
+  ks_multi_entry<1>(table, n_replicas, wgs);
 }
 
 // Exchange scratch of the kernel: the partial pre-activation words and the norm granules, ordinary device memory (agent-scope
@@ -1074,16 +1107,108 @@ int ks_scratch(hipStream_t st, KsScratch* out, unsigned* tag_base, unsigned nste
   return 0;
 }
 
+// Per-run state of the seed-batched launches (spo_update_iter_ex_ks_multi), one block per (device, stream), separate from g_ks,
+// allocated at the first call (never under capture), zeroed once and kept: SPO_KS_MAX_REPLICAS strides of
+//   [KS_Z_BYTES exchange slots, zero row, dump row | 4 KB page: KS_G_BYTES granules + census words, then the run's write-through count]
+// then the argument table -- 16 x 7 090 176 bytes + the table = 113 449 344 bytes (108.2 MB).  The table leaves the host from pinned
+// memory: KSM_TAB_RING tables per entry, used in turn, each with an event recorded behind its copy (update.hip: exm_scratch).
+constexpr size_t KSM_G_PAGE = 4096;
+static_assert(KS_G_BYTES + sizeof(unsigned) <= KSM_G_PAGE && KS_Z_BYTES % 4096 == 0, "a run's granule page");
+constexpr size_t KSM_STRIDE = KS_Z_BYTES + KSM_G_PAGE;
+constexpr size_t KSM_T_OFF = (size_t)SPO_KS_MAX_REPLICAS * KSM_STRIDE;
+constexpr size_t KSM_BYTES = KSM_T_OFF + (((size_t)SPO_KS_MAX_REPLICAS * sizeof(KsMultiEntry) + 4095) & ~(size_t)4095);
+constexpr int KSM_TAB_RING = 4, KSM_SCRATCH_MAX = 16;
+struct KsmEntry { int dev; void* stream; char* base; KsMultiEntry* tab_host; hipEvent_t ev[KSM_TAB_RING]; unsigned calls; unsigned tag; };
+KsmEntry g_ksm[KSM_SCRATCH_MAX] = {};
+int g_ksm_n = 0;
+std::mutex g_ksm_mu;
+std::atomic<unsigned long long> g_ksm_counters[2];       // {launches enqueued, runs that took part}
+unsigned long long g_ksm_wt_released = 0;                // write-through counts of blocks that have been released (under g_ksm_mu)
+
+inline unsigned* ksm_wt_word(char* base, int r) { return reinterpret_cast<unsigned*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES + KS_G_BYTES); }
+
+// sums (and optionally clears) the write-through counts of one block; the caller holds g_ksm_mu and has synchronised the device
+int ksm_harvest(KsmEntry& e, unsigned long long* sum, bool clear) {
+  for (int r = 0; r < SPO_KS_MAX_REPLICAS; ++r) {
+    unsigned v = 0;
+    if (int rc = spo::hip_check(hipMemcpy(&v, ksm_wt_word(e.base, r), sizeof(v), hipMemcpyDeviceToHost), "hipMemcpy(ks multi count)")) return rc;
+    *sum += v;
+    if (clear && v)
+      if (int rc = spo::hip_check(hipMemset(ksm_wt_word(e.base, r), 0, sizeof(v)), "hipMemset(ks multi count)")) return rc;
+  }
+  return 0;
+}
+
+void ksm_free(KsmEntry& e) {
+  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched ks scratch)");
+  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(ks replica table)");
+  for (int i = 0; i < KSM_TAB_RING; ++i)
+    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(ks replica table)");
+  e = KsmEntry{};
+}
+
+// The caller holds g_ksm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot) and has
+// checked that the stream is not under capture.
+int ksm_scratch(hipStream_t st, unsigned nsteps, char** base, KsMultiEntry** tab_host, hipEvent_t* ev, unsigned* tag_base) {
+  const int dev = current_device_slot();
+  KsmEntry* e = nullptr;
+  for (int i = 0; i < g_ksm_n; ++i)
+    if (g_ksm[i].dev == dev && g_ksm[i].stream == (void*)st) e = &g_ksm[i];
+  if (!e) {
+    if (g_ksm_n == KSM_SCRATCH_MAX)
+      return spo::fail(-1, "update_iter_ex_ks_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                           "spo_update_scratch_release(stream) for streams that are gone", KSM_SCRATCH_MAX);
+    KsmEntry n{};
+    n.dev = dev; n.stream = (void*)st; n.tag = 16u;
+    void* p = nullptr;
+    if (int rc = spo::hip_check(hipMalloc(&p, KSM_BYTES), "hipMalloc(seed-batched ks scratch)")) return rc;
+    n.base = static_cast<char*>(p);
+    if (int rc = spo::hip_check(hipMemset(p, 0, KSM_BYTES), "hipMemset(seed-batched ks scratch)")) { ksm_free(n); return rc; }
+    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)")) { ksm_free(n); return rc; }
+    void* h = nullptr;
+    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)KSM_TAB_RING * SPO_KS_MAX_REPLICAS * sizeof(KsMultiEntry),
+                                              hipHostMallocDefault), "hipHostMalloc(ks replica table)")) { ksm_free(n); return rc; }
+    n.tab_host = static_cast<KsMultiEntry*>(h);
+    for (int i = 0; i < KSM_TAB_RING; ++i)
+      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(ks replica table)")) {
+        ksm_free(n); return rc;
+      }
+    g_ksm[g_ksm_n] = n;
+    e = &g_ksm[g_ksm_n++];
+  }
+  *base = e->base;
+  *tag_base = e->tag;
+  e->tag += nsteps + 2u;                           // (one tag range per launch serves all runs: their words are their own)
+  const unsigned slot = e->calls++ % KSM_TAB_RING;
+  *tab_host = e->tab_host + (size_t)slot * SPO_KS_MAX_REPLICAS;
+  *ev = e->ev[slot];
+  // (an event that was never recorded is complete)
+  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(ks replica table)");
+}
+
 }  // namespace
 
 // (called by spo_update_scratch_release, update.hip)
 int spo::ks_scratch_release(int dev, void* stream_or_null, int all) {
-  std::lock_guard<std::mutex> lk(g_ks_mu);
   int freed = 0;
-  for (int i = 0; i < g_ks_n;) {
-    if (g_ks[i].dev == dev && (all || g_ks[i].stream == stream_or_null)) {
-      (void)spo::hip_check(hipFree(g_ks[i].base), "hipFree(ks scratch)");
-      g_ks[i] = g_ks[--g_ks_n];
+  {
+    std::lock_guard<std::mutex> lk(g_ks_mu);
+    for (int i = 0; i < g_ks_n;) {
+      if (g_ks[i].dev == dev && (all || g_ks[i].stream == stream_or_null)) {
+        (void)spo::hip_check(hipFree(g_ks[i].base), "hipFree(ks scratch)");
+        g_ks[i] = g_ks[--g_ks_n];
+        ++freed;
+      } else ++i;
+    }
+  }
+  std::lock_guard<std::mutex> lk(g_ksm_mu);
+  for (int i = 0; i < g_ksm_n;) {
+    if (g_ksm[i].dev == dev && (all || g_ksm[i].stream == stream_or_null)) {
+      if (spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)") == 0)
+        (void)ksm_harvest(g_ksm[i], &g_ksm_wt_released, false);       // (the debug counter outlives the block)
+      ksm_free(g_ksm[i]);
+      g_ksm[i] = g_ksm[--g_ksm_n];
+      g_ksm[g_ksm_n] = KsmEntry{};
       ++freed;
     } else ++i;
   }
@@ -1240,5 +1365,145 @@ extern "C" int spo_critic_fit_iter_ks(float* theta, float* adam_m, float* adam_v
   a.perm = perm; a.losses = losses_out; a.stale_io = stale_sq_io; a.n_nets = 2; a.first_net = 0;
   if (int rc = ks_launch(a, cfg_host, adam_step_host, adam_step_host, M, sync_ws, (hipStream_t)stream, 1)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_ks");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- seed-batched spo_update_iter_ex_ks
+// At most 24 working blocks per XCD label (one CU each of the XCD's 32, as the seed-batched critic fit): 8 / S runs per label at
+// 3 S blocks a run -- counted with the critics whatever actor_only says, so both stages of a CUP group share one cap.
+extern "C" int spo_update_ks_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas) {
+  if (!spo_ks_supported(obs_dim, act_dim, batch)) return 0;
+  const int S = (obs_dim + 63) / 64;
+  const int cap = 8 * (8 / S) < SPO_KS_MAX_REPLICAS ? 8 * (8 / S) : SPO_KS_MAX_REPLICAS;
+  return (n_replicas >= 1 && n_replicas <= cap) ? 1 : 0;
+}
+
+extern "C" int spo_update_ks_multi_block_map(int block, int obs_dim, int n_replicas, int actor_only, int* replica, int* wg) {
+  if (!spo_update_ks_multi_supported(obs_dim, 1, 1, n_replicas)) return 0;
+  const int wgs = (actor_only ? 1 : 3) * ((obs_dim + 63) / 64);
+  if (block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
+  int r = 0, w = 0;
+  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
+  if (work && replica) *replica = r;
+  if (work && wg) *wg = w;
+  return work ? 1 : 0;
+}
+
+extern "C" int spo_debug_update_ks_multi_counters(unsigned long long* out3_host, int reset) {
+  SPO_REQUIRE(out3_host, "update_ks_multi_counters: null pointer");
+  if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(update_ks_multi_counters)")) return rc;
+  std::lock_guard<std::mutex> lk(g_ksm_mu);
+  const int dev = current_device_slot();
+  unsigned long long wt = g_ksm_wt_released;
+  for (int i = 0; i < g_ksm_n; ++i)
+    if (g_ksm[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm[i], &wt, reset != 0)) return rc;
+  if (reset) g_ksm_wt_released = 0;
+  for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_counters[i].exchange(0ull) : g_ksm_counters[i].load();
+  out3_host[2] = wt;
+  return 0;
+}
+
+extern "C" int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss,
+                                           int actor_only, void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "update_iter_ex_ks_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_KS_MAX_REPLICAS, "update_iter_ex_ks_multi: %d replicas outside [1, %d]",
+              n_replicas, SPO_KS_MAX_REPLICAS);
+  SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || actor_loss == SPO_ACTOR_LOSS_KL_PENALTY,
+              "update_iter_ex_ks_multi: unknown actor_loss %d", actor_loss);
+  SPO_REQUIRE(M > 0, "update_iter_ex_ks_multi: bad sizes");
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_ex_replica& p = reps_host[r];
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "update_iter_ex_ks_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
+                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+  }
+  SPO_REQUIRE(spo_ks_supported(c0.obs_dim, c0.act_dim, c0.batch),
+              "update_iter_ex_ks_multi: obs_dim %d / act_dim %d / batch %d outside [1,%d] / [1,%d] / [1,64]", c0.obs_dim, c0.act_dim,
+              c0.batch, 64 * KS_MAX_SLICES, KS_OUT);
+  const int S = (c0.obs_dim + 63) / 64;
+  SPO_REQUIRE(spo_update_ks_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, n_replicas),
+              "update_iter_ex_ks_multi: %d replicas at obs_dim %d: at most %d runs share a launch (24 workgroups of a run's %d per "
+              "XCD; spo_update_ks_multi_supported)", n_replicas, c0.obs_dim, 8 * (8 / S) < SPO_KS_MAX_REPLICAS ? 8 * (8 / S) : SPO_KS_MAX_REPLICAS, 3 * S);
+  const int64_t nsteps = (M + c0.batch - 1) / c0.batch;
+  SPO_REQUIRE(nsteps < (1ll << 30), "update_iter_ex_ks_multi: too many minibatch steps in one launch");
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_ex_replica& p = reps_host[r];
+    SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.act && p.logp_old && p.adv && p.sync_ws &&
+                    ((p.perm && p.losses_out) || !p.active), "update_iter_ex_ks_multi: null pointer in replica %d", r);
+    SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || (p.old_mean && p.old_std),
+                "update_iter_ex_ks_multi: old distribution is NULL in replica %d", r);
+    SPO_REQUIRE(actor_only || (p.target_r && p.target_c), "update_iter_ex_ks_multi: critic targets are NULL in replica %d", r);
+    SPO_REQUIRE(p.adam_step_critics >= 0 && p.adam_step_actor >= 0, "update_iter_ex_ks_multi: replica %d: negative adam_step", r);
+    for (int q = 0; q < r; ++q)
+      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
+                  "update_iter_ex_ks_multi: replicas %d and %d share theta or sync_ws", q, r);
+    n_active += p.active ? 1 : 0;
+  }
+  if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return spo::fail(-1, "update_iter_ex_ks_multi: the stream is under capture (the argument table is copied from host memory at "
+                           "every call: not a graph node)");
+  }
+  const int n_nets = actor_only ? 1 : 3, wgs = n_nets * S;
+  int force_safe;
+  { const char* e = getenv("SPO_KS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  std::lock_guard<std::mutex> lk(g_ksm_mu);                                // (until the table's copy and its event are enqueued)
+  char* base = nullptr;
+  KsMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  unsigned tag_base = 0;
+  if (int rc = ksm_scratch(st, (unsigned)nsteps, &base, &tab, &tab_ev, &tag_base)) return rc;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_update_ex_replica& p = reps_host[r];
+    KsArgs a{};                                                            // (as spo_update_iter_ex_ks and ks_launch fill it)
+    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
+    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
+    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
+    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * KSM_STRIDE);
+    a.gran = reinterpret_cast<unsigned long long*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step_critics);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step_critics);
+    a.pow_b1_actor = pow((double)p.cfg.beta1, (double)p.adam_step_actor);
+    a.pow_b2_actor = pow((double)p.cfg.beta2, (double)p.adam_step_actor);
+    a.tag_base = tag_base; a.S = S; a.n_nets = n_nets; a.first_net = actor_only ? 2 : 0;
+    a.old_mean = p.old_mean; a.old_std = p.old_std; a.kl_bound = p.kl_bound; a.pg_coef = p.pg_coef;
+    a.force_safe = force_safe;
+    tab[r].a = a;
+    tab[r].active = p.active ? 1 : 0;
+  }
+  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(base + KSM_T_OFF);
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(KsMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(ks replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(ks replica table)")) return rc;
+  // every partial slot of every active run starts as the sentinel (ks_launch); the run's row of zeros behind them stays zero
+  for (int r = 0; r < n_replicas; ++r)
+    if (reps_host[r].active)
+      if (int rc = spo::hip_check(hipMemsetAsync(base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
+        return rc;
+  const size_t sh = KsLds::SIZE * sizeof(float);
+  const bool klpen = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
+  static bool attr_done[SPO_MAX_DEVICES][2] = {};
+  const int dslot = current_device_slot();
+  if (!attr_done[dslot][klpen]) {
+    const void* fn = klpen ? reinterpret_cast<const void*>(&klpen_update_ks_multi_kernel)
+                           : reinterpret_cast<const void*>(&ppo_update_ks_multi_kernel);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_ks_multi)");
+    attr_done[dslot][klpen] = true;
+  }
+  const dim3 grid(spo::rs_multi_grid(n_replicas, wgs));
+  if (klpen) hipLaunchKernelGGL(klpen_update_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
+  else hipLaunchKernelGGL(ppo_update_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
+  SPO_LAUNCH_CHECK("spo_update_iter_ex_ks_multi");
+  g_ksm_counters[0] += 1ull;
+  g_ksm_counters[1] += (unsigned long long)n_active;
   return 0;
 }

@@ -102,6 +102,7 @@ RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS
 RS_CRITIC_MAX_REPLICAS = 24                        # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 UPDATE_EX_MAX_REPLICAS = 32                        # include/safepo_hip.h SPO_UPDATE_EX_MAX_REPLICAS
 CRITIC_SPLIT_MAX_REPLICAS = 32                     # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
+KS_MAX_REPLICAS = 16                               # include/safepo_hip.h SPO_KS_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
 ABI_VERSION = 2          # include/safepo_hip.h SPO_ABI_VERSION
@@ -160,6 +161,10 @@ PROTOTYPES = {
     "spo_ppo_lag_grad_ks": (c_int, [P] * 8 + [c_int, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex_ks": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,
                                    c_float, c_float, c_int, P, P, P]),
+    "spo_update_iter_ex_ks_multi": (c_int, [POINTER(UpdateExReplica), c_int, c_int64, c_int, c_int, P]),
+    "spo_update_ks_multi_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "spo_update_ks_multi_block_map": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_update_ks_multi_counters": (c_int, [P, c_int]),
     "spo_critic_fit_ks_supported": (c_int, [c_int, c_int]),
     "spo_critic_fit_iter_ks": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_scratch_release": (c_int, [P, c_int]),

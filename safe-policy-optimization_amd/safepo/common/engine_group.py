@@ -97,17 +97,30 @@ class _EngineGroup:
 
 class PPOLagEngineGroup(_EngineGroup):
     """S ordinary one-GPU PPOLagEngines of one shape (observations, actions, rows, minibatch size) on one device.
-    `rngs`: one ReplicaRNG per engine -- the default shuffle of run i is then drawn under rngs[i]."""
+    `rngs`: one ReplicaRNG per engine -- the default shuffle of run i is then drawn under rngs[i].
+    A group made entirely of one-GPU WidePPOLagEngines whose minibatch step is on the feature-split kernel
+    (_feature_split_kernel_ok: hidden [64, 64], up to 512 observations / 32 actions, HumanoidVelocity's 376 / 17) is taken too:
+    its learning iterations share one spo_update_iter_ex_ks_multi launch (csrc/update_ks.hip: run r on its own
+    3 x ceil(obs_dim / 64) co-XCD workgroups), each bit for bit its own spo_ppo_lag_update_iter_ks / spo_update_iter_ex_ks."""
 
     def __init__(self, engines, rngs=None):
-        from safepo.common.engine import PPOLagEngine
+        from safepo.common.engine import PPOLagEngine, WidePPOLagEngine
         engines = list(engines)
         if not engines:
             raise ValueError("PPOLagEngineGroup: no engines")
         e0 = engines[0]
+        # the feature-split form: every engine a WidePPOLagEngine on that kernel (mixed groups are refused below)
+        self._ks = all(type(e) is WidePPOLagEngine for e in engines)
         for i, e in enumerate(engines):
             if isinstance(e, PPOLagEngine):
-                if type(e) is not PPOLagEngine:
+                if self._ks:
+                    if e.comm.world_size != 1:
+                        raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
+                    if not e._feature_split_kernel_ok(e._cfg_struct()):
+                        raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a WidePPOLagEngine outside the feature-split kernel "
+                                            "(hidden [64, 64], obs_dim <= 512, act_dim <= 32, batch <= 64, SPO_WIDE_KS not 0); "
+                                            "only those wide engines can be grouped")
+                elif type(e) is not PPOLagEngine:
                     raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
                                         "PPOLagEngine (hidden [64, 64], obs_dim <= 128, act_dim <= 16) can be grouped")
                 if e.comm.world_size != 1:
@@ -133,10 +146,54 @@ class PPOLagEngineGroup(_EngineGroup):
         c0 = cfgs[0]
         if any(c.batch != c0.batch for c in cfgs):
             return False
+        if self._ks:
+            return self._ks_batched(cfgs)
         if os.environ.get("SPO_FORCE_DP", "0") == "1":
             return False
         return bool(self.lib.spo_update_rs_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))
                     and self.lib.spo_update_rs_multi_matches_single(c0.obs_dim, c0.act_dim, c0.batch))
+
+    def _ks_batched(self, cfgs) -> bool:
+        """A group of feature-split WidePPOLagEngines: one spo_update_iter_ex_ks_multi launch where every engine's own step is
+        (still: SPO_WIDE_KS is read at every call) on that kernel and the library takes this many runs of the shape
+        (spo_update_ks_multi_supported: 16 up to 256 observations, 8 up to 512)."""
+        c0 = cfgs[0]
+        return (all(e._feature_split_kernel_ok(c) for e, c in zip(self.engines, cfgs))
+                and bool(self.lib.spo_update_ks_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))))
+
+    def _ks_launch(self, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill):
+        """One spo_update_iter_ex_ks_multi launch for the active runs; the clocks advance as WidePPOLagEngine.learning_iter /
+        learning_iter_ex advance them."""
+        S, e0 = len(self.engines), self.engines[0]
+        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
+        reps = (_abi.UpdateExReplica * S)()
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            d = e.buffer.data
+            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
+            perm = perms[i] if active[i] else None
+            if perm is not None:
+                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+                losses[i] = (torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=e.dev) if nan_fill
+                             else torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev))
+            adv = _abi.require_gpu_tensor(advs[i], "adv", torch.float32)
+            r = reps[i]
+            r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
+            r.adam_step_critics, r.adam_step_actor = e.adam_step, e.adam_step + (e.adam_step_actor_extra if nan_fill else 0)
+            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(adv)
+            r.perm, r.old_mean, r.old_std = _abi.ptr(perm), _abi.ptr(e.mean_old), _abi.ptr(e.std_old)
+            r.kl_bound, r.pg_coef, r.losses_out = float(kl_bounds[i]), float(pg_coefs[i]), _abi.ptr(losses[i])
+            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
+        _abi.check(self.lib.spo_update_iter_ex_ks_multi(reps, S, e0.M, int(actor_loss), int(bool(actor_only)), _abi.stream_ptr()),
+                   "spo_update_iter_ex_ks_multi")
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                if actor_only:
+                    e.adam_step_actor_extra += n_mb
+                else:
+                    e.adam_step += n_mb
+        return losses
 
     def learning_iter_all(self, perms, active=None):
         """PPOLagEngine.learning_iter(perms[i]) for every run i with active[i] (default: all): one
@@ -149,6 +206,10 @@ class PPOLagEngineGroup(_EngineGroup):
         cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
         if not self.batched(cfgs):
             return [e.learning_iter(perms[i]) if active[i] else None for i, e in enumerate(self.engines)]
+        if self._ks:
+            # spo_ppo_lag_update_iter_ks is spo_update_iter_ex_ks with the clipped surrogate on adv_mix and equal clocks
+            return self._ks_launch(cfgs, perms, [e.buffer.adv_mix for e in self.engines], _abi.ACTOR_LOSS_CLIP,
+                                   [float("inf")] * S, [0.0] * S, False, active, nan_fill=False)
         e0 = self.engines[0]
         n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
         reps = (_abi.UpdateReplica * S)()
@@ -243,6 +304,8 @@ class PPOLagEngineGroup(_EngineGroup):
         c0 = cfgs[0]
         if any(c.batch != c0.batch for c in cfgs):
             return False
+        if self._ks:
+            return self._ks_batched(cfgs)
         return bool(self.lib.spo_update_ex_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss), len(self.engines))
                     and self.lib.spo_update_ex_multi_matches_single(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss)))
 
@@ -262,6 +325,8 @@ class PPOLagEngineGroup(_EngineGroup):
         if not self.batched_ex(actor_loss, cfgs):
             return [e.learning_iter_ex(perms[i], advs[i], actor_loss, kl_bounds[i], pg_coefs[i], actor_only) if active[i] else None
                     for i, e in enumerate(self.engines)]
+        if self._ks:
+            return self._ks_launch(cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill=True)
         e0 = self.engines[0]
         n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
         reps = (_abi.UpdateExReplica * S)()

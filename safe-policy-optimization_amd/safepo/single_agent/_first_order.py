@@ -16,6 +16,7 @@ import time
 import numpy as np
 import torch
 
+from safepo import _abi
 from safepo.common.engine import PPOLagEngine, WidePPOLagEngine
 from safepo.common.env import make_sa_mujoco_env
 from safepo.common.lagrange import Lagrange, PIDLagrangian
@@ -104,6 +105,9 @@ def _log_epoch(logger, args, out, variant, lagrange, epoch, next_lr, engine, env
 def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip: float | None = 0.2,
         variant: str = "ppo"):
     """variant: "ppo" (clipped surrogate family), "focops" (focops.py:279-367) or "cup" (cup.py:279-405)."""
+    if variant != "ppo" and getattr(args, "batch_wide_obs", False) and not getattr(args, "batch_update", False):
+        raise SystemExit("--batch-wide-obs True widens --batch-update True for focops and cup (hidden [64, 64], up to 512 observations "
+                         "/ 32 actions: HumanoidVelocity): give both")
     if len(seed_list(args)) > 1:
         if variant != "ppo" and not getattr(args, "batch_update", False):
             refuse_seed_batch(args, "focops and cup",
@@ -230,6 +234,13 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
     return {"timings": timings, "policy": policy, "engine": engine}
 
 
+def _ks_shape_ok(obs_dim: int, act_dim: int, config: dict, rows: int) -> bool:
+    """Would a one-GPU WidePPOLagEngine of this shape and config step on the feature-split kernel (its _feature_split_kernel_ok,
+    answered before an engine exists)?"""
+    batch = config.get("batch_size", max(rows // config.get("num_mini_batch", 1), 1))
+    return os.environ.get("SPO_WIDE_KS", "1") != "0" and bool(_abi.load().spo_ks_supported(int(obs_dim), int(act_dim), int(batch)))
+
+
 class _SeedRun:
     """One run of a seed-batched process: what run() holds in local variables, per seed."""
 
@@ -266,6 +277,10 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
     local_steps_per_epoch = steps_per_epoch // args.num_envs
     epochs = total_steps // steps_per_epoch
 
+    wide_obs = bool(getattr(args, "batch_wide_obs", False))
+    if wide_obs and list(config["hidden_sizes"]) == [64, 64] and len(seeds) > _abi.KS_MAX_REPLICAS:
+        raise SystemExit(f"--seeds: at most {_abi.KS_MAX_REPLICAS} seeds share a launch with --batch-wide-obs True (8 above 256 "
+                         f"observations), got {len(seeds)}")
     runs = []
     for seed, log_dir in zip(seeds, log_dirs):
         r = _SeedRun()
@@ -278,11 +293,24 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
                 r.eval_env, _, _ = make_sa_mujoco_env(num_envs=1, env_id=args.task, seed=None, device=device, **env_kwargs)
             r.policy = ActorVCritic(obs_dim=obs_space.shape[0], act_dim=act_space.shape[0],
                                     hidden_sizes=config["hidden_sizes"]).to(device)
-            if not r.policy.kernels_supported():
+            if r.policy.kernels_supported():
+                r.engine = PPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
+            elif wide_obs and list(config["hidden_sizes"]) == [64, 64] and _ks_shape_ok(obs_space.shape[0], act_space.shape[0], config,
+                                                                                         args.num_envs * local_steps_per_epoch):
+                # --batch-wide-obs True: the feature-split kernel's shapes (up to 512 observations / 32 actions, HumanoidVelocity's
+                # 376 / 17) -- WidePPOLagEngines, whose minibatch steps share one spo_update_iter_ex_ks_multi launch.  The seed cap
+                # depends on the observation count, which only the (first) environment tells: checked before anything is logged
+                D, A = obs_space.shape[0], act_space.shape[0]
+                lib = _abi.load()
+                if not lib.spo_update_ks_multi_supported(D, A, 1, len(seeds)):
+                    cap = max(n for n in range(1, _abi.KS_MAX_REPLICAS + 1) if lib.spo_update_ks_multi_supported(D, A, 1, n))
+                    raise SystemExit(f"--seeds: at most {cap} seeds share the feature-split kernel's launch at {D} observations "
+                                     f"(--batch-wide-obs True: {_abi.KS_MAX_REPLICAS} up to 256 observations, 8 up to 512), got {len(seeds)}")
+                r.engine = WidePPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
+            else:
                 raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "
                                  f"128, act_dim <= 16); {args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network "
                                  "kernels: one process per seed")
-            r.engine = PPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
             if multiplier == "adam":
                 upper = {"focops": FOCOPS_NU, "cup": CUP_NU}.get(variant)          # focops.py:136, cup.py:136
                 r.lagrange = Lagrange(cost_limit=args.cost_limit, lagrangian_multiplier_init=args.lagrangian_multiplier_init,

@@ -13,7 +13,9 @@ on those commands: their critic fits share one persistent launch per iteration; 
 needs `--batch-second-order`) adds the Ant / Car / Doggo / Racecar navigation tasks (65-128 observations, up to 32 seeds per
 subprocess, `--batch-critic-fit True --batch-critic-fit-split True`).  `--batch-focops-cup` (default off) does the
 same for focops / cup with `--batch-update True` (up to 32 seeds per subprocess): their minibatch steps share one persistent launch
-per pass.
+per pass.  `--batch-wide-obs` (default off) also groups HumanoidVelocity (376 / 17: the feature-split kernel) for ppo_lag / ppo /
+pg / cppo_pid -- and, with `--batch-focops-cup`, for focops / cup -- at most 8 seeds per subprocess, `--batch-wide-obs True` on
+those commands.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from safepo.utils.config import CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES
+from safepo.utils.config import CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -78,6 +80,11 @@ def parse_args(argv=None):
     p.add_argument("--batch-focops-cup", action="store_true",
                    help="with --seeds-per-run: also group focops / cup (--batch-update True on those commands; HumanoidVelocity "
                         "excepted).  " + KLPEN_BATCH_FIGURES + "  Default off: these algorithms keep one subprocess per seed")
+    p.add_argument("--batch-wide-obs", action="store_true",
+                   help="with --seeds-per-run: also group HumanoidVelocity (376 / 17: the feature-split kernel) for ppo_lag / ppo / pg "
+                        "/ cppo_pid, and with --batch-focops-cup for focops / cup, at most 8 seeds per subprocess "
+                        "(--batch-wide-obs True on those commands).  " + KS_BATCH_FIGURES + "  Default off: HumanoidVelocity keeps "
+                        "one subprocess per seed")
     return p.parse_args(argv)
 
 
@@ -87,17 +94,18 @@ KLPEN_BATCHED_ALGOS = ("focops", "cup")                       # ... with --batch
 CRITIC_BATCH_MAX = 24                                         # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
 CRITIC_SPLIT_BATCH_MAX = 32                                   # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
+KS_BATCH_MAX = 8                                              # spo_update_ks_multi_supported at 376 observations (S = 6: one run per XCD)
 
 
 def _takes_seeds(algo: str, task: str) -> bool:
-    """Can `--seeds` carry several seeds for this (algorithm, task)?  HumanoidVelocity (376 / 17) runs on the wide-network
-    kernels, which have no seed-batched form."""
+    """Can `--seeds` alone carry several seeds for this (algorithm, task)?  HumanoidVelocity (376 / 17) is outside the persistent
+    kernels' shapes: its seeds share a launch only with `--batch-wide-obs True` (_takes_wide_obs_batch)."""
     return algo in SEED_BATCHED_ALGOS and "Humanoid" not in task
 
 
 def _takes_klpen_batch(algo: str, task: str) -> bool:
     """Can `--seeds ... --batch-update True` carry several seeds for this (algorithm, task)?  As _takes_seeds: every task but
-    HumanoidVelocity runs on the persistent kernels (up to 128 observations)."""
+    HumanoidVelocity runs on the persistent kernels (up to 128 observations); that one needs `--batch-wide-obs True` as well."""
     return algo in KLPEN_BATCHED_ALGOS and "Humanoid" not in task
 
 
@@ -116,6 +124,12 @@ def _takes_critic_split_batch(algo: str, task: str) -> bool:
     """Can `--seeds ... --batch-critic-fit True --batch-critic-fit-split True` carry several seeds?  The Ant / Car / Doggo /
     Racecar navigation tasks (65-128 observations: the split critic fit); not HumanoidVelocity (376: the feature-split kernel)."""
     return algo in CRITIC_BATCHED_ALGOS and _is_wide_obs_nav(task)
+
+
+def _takes_wide_obs_batch(algo: str, task: str, klpen_too: bool) -> bool:
+    """Can `--seeds ... --batch-wide-obs True` carry several seeds?  HumanoidVelocity (376 / 17, hidden [64, 64]: the feature-split
+    kernel) for the PPO family, and for focops / cup where --batch-focops-cup adds `--batch-update True`."""
+    return "Humanoid" in task and (algo in SEED_BATCHED_ALGOS or (klpen_too and algo in KLPEN_BATCHED_ALGOS))
 
 
 def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
@@ -139,9 +153,13 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                 klpen = getattr(args, "batch_focops_cup", False) and _takes_klpen_batch(algo, task)
                 split = (getattr(args, "batch_second_order", False) and getattr(args, "batch_second_order_wide_obs", False)
                          and _takes_critic_split_batch(algo, task))
+                wide = (getattr(args, "batch_wide_obs", False)
+                        and _takes_wide_obs_batch(algo, task, getattr(args, "batch_focops_cup", False)))
                 runs = [[s] for s in group]
                 if len(group) > 1 and (_takes_seeds(algo, task) or klpen):
                     runs = [group]
+                elif len(group) > 1 and wide:
+                    runs = [group[i:i + KS_BATCH_MAX] for i in range(0, len(group), KS_BATCH_MAX)]
                 elif len(group) > 1 and critic:
                     runs = [group[i:i + CRITIC_BATCH_MAX] for i in range(0, len(group), CRITIC_BATCH_MAX)]
                 elif len(group) > 1 and split:
@@ -153,7 +171,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                         "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else [])
                         + (["--batch-critic-fit", "True"] if batched and critic else [])
                         + (["--batch-critic-fit", "True", "--batch-critic-fit-split", "True"] if batched and split else [])
-                        + (["--batch-update", "True"] if batched and klpen else []) + [
+                        + (["--batch-update", "True"] if batched and (klpen or (wide and algo in KLPEN_BATCHED_ALGOS)) else [])
+                        + (["--batch-wide-obs", "True"] if batched and wide else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
                         str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))

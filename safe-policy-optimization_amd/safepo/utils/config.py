@@ -105,6 +105,14 @@ KLPEN_BATCH_FIGURES = ("Measured at 4096 x 128 rows, batch 64: one FOCOPS step o
                        "`--seed` (profiles/seed_batch_klpen/step_times.txt).")
 
 
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_ks/step_times.txt)
+KS_BATCH_FIGURES = ("Measured at 376 / 17, 4096 x 128 rows, batch 64: one clipped-surrogate step of ALL seeds takes 16.4 / 16.5 / 16.6 us at 2 / 4 / 8 "
+                    "seeds against 16.2 us per seed one after the other (1.98 x / 3.93 x / 7.81 x the aggregate step rate; the FOCOPS step 18.0 / 18.1 / "
+                    "18.1 us against 17.8-17.9 per seed: 7.85 x at 8; CUP's second stage 7.81 x at 8); one seed alone: 16.49 against 16.23 us, which is "
+                    "why one seed stays `--seed`; 192 / 8 with 16 seeds, two per XCD: 17.64 us against 274.96 (15.6 x); ppo_lag's second epoch with 8 "
+                    "seeds at 376 / 17: Time/Update 3.06 s against 21.31 s, one sample each (profiles/seed_batch_ks/step_times.txt).")
+
+
 def single_agent_args(argv=None):
     """-> (args, cfg_env).  cfg_env is {} for non-Isaac tasks (reference config.py:172-191)."""
     parser = build_parser()
@@ -130,6 +138,13 @@ def single_agent_args(argv=None):
                              "launch per pass (spo_update_iter_ex_multi: up to 32 seeds, one workgroup per network each, run r on XCD "
                              "r mod 8; hidden [64, 64], obs_dim <= 128, act_dim <= 16), each seed the run its `--seed` would be.  "
                              + KLPEN_BATCH_FIGURES + "  Default False: several seeds are refused for these scripts")
+    parser.add_argument("--batch-wide-obs", type=_bool, default=False,
+                        help="the six first-order scripts with --seeds (focops and cup: with --batch-update True as well): also take "
+                             "shapes outside the persistent kernels but inside the feature-split kernel -- hidden [64, 64], up to 512 "
+                             "observations / 32 actions, minibatches of up to 64 rows: HumanoidVelocity's 376 / 17 -- whose minibatch "
+                             "steps then share one launch per pass (spo_update_iter_ex_ks_multi: up to 16 seeds up to 256 observations, "
+                             "8 up to 512; 3 x ceil(obs_dim / 64) workgroups each, run r on XCD r mod 8), each seed the run its `--seed` "
+                             "would be.  " + KS_BATCH_FIGURES + "  Default False: such tasks are refused with several seeds")
     args = parser.parse_args(argv)
     if args.task in isaac_gym_map:
         raise Exception("Please install isaacgym to run Isaac Gym tasks!")
