@@ -671,6 +671,41 @@ int spo_critic_fit_iter_ks(float* theta, float* adam_m, float* adam_v, int64_t a
                            const float* target_r, const float* target_c, const int32_t* perm, int64_t M,
                            const spo_ppo_cfg* cfg_host, float* stale_sq_io, float* losses_out, void* sync_ws, void* stream);
 
+/* Seed-batched spo_critic_fit_iter_ks (the six second-order scripts at HumanoidVelocity-class dims): one critic-fit iteration
+ * (ceil(M / batch) steps) for every active run of reps_host[n_replicas] (a HOST array of the spo_critic_fit_replica records
+ * spo_critic_fit_iter_multi takes) in ONE launch of the feature-split kernel, every run on its own 2 x ceil(obs_dim / 64)
+ * workgroups of one XCD; run r sits on XCD label r mod 8, runs r and r + 8 share one.  Per run the arithmetic is
+ * spo_critic_fit_iter_ks's, bit for bit (the two 64-column chunks of a 65-128-row minibatch, the stale actor-gradient norm in the
+ * joint clip, the placement census, SPO_KS_SAFE).  Every run has its own exchange slots, granules and census words -- in the block
+ * spo_update_iter_ex_ks_multi keeps per (device, stream), which both launches share: launches on one stream are ordered and each
+ * primes the slots of its active runs -- its own stale_sq_io and its own error word, the int at byte 64 of ITS sync_ws.  Unlike
+ * spo_critic_fit_iter_ks, which zeroes the first 64 bytes of sync_ws, this launch touches nothing else of sync_ws (the kernel reads
+ * none of it).  A run whose exchange times out leaves its parameters and optimiser state untouched and sets its error word; the
+ * other runs are unaffected.  A run with active == 0 is skipped: nothing of it is read or written (its perm / losses_out may be
+ * NULL).  Refused on the host before anything is enqueued, each with its own message: a null table, n_replicas outside
+ * [1, SPO_KS_MAX_REPLICAS] or the shape's cap (spo_critic_fit_ks_multi_supported), M <= 0, unequal obs_dim / act_dim / batch, a shape
+ * outside spo_critic_fit_ks_supported, act_dim < 1, null pointers of an active run, stale_sq_io NULL, a negative adam_step, two
+ * runs sharing theta, sync_ws or stale_sq_io, ceil(M / batch) >= 2^30, a stream under capture.  All runs inactive: returns 0 with
+ * nothing enqueued.  SPO_WIDE_KS is not read: the caller decides whether to batch. */
+int spo_critic_fit_iter_ks_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream);
+
+/* 1 where spo_critic_fit_ks_supported(obs_dim, batch) and 1 <= n_replicas <= min(SPO_KS_MAX_REPLICAS, 8 * (24 / (2 * S))) with
+ * S = ceil(obs_dim / 64) and integer division: at most 24 working blocks per XCD label, each on one of that XCD's 32 CUs, a run
+ * being 2 S blocks -- 16 runs up to 384 observations (HumanoidVelocity's 376 included), 8 at 385 .. 512. */
+int spo_critic_fit_ks_multi_supported(int obs_dim, int batch, int n_replicas);
+
+/* The launch's block -> (run, workgroup) mapping, the function the kernel itself uses (testable without a GPU): with
+ * wgs = 2 * ceil(obs_dim / 64) the grid has 8 * wgs * ceil(n_replicas / 8) blocks; block b has XCD label b & 7 and serves run
+ * 8 * ((b >> 3) / wgs) + (b & 7) as workgroup (b >> 3) % wgs.  Returns 1 and fills replica / wg (both optional), or 0 for a block
+ * without work (run >= n_replicas, block outside the grid, or n_replicas outside the supported range). */
+int spo_critic_fit_ks_multi_block_map(int block, int obs_dim, int n_replicas, int* replica, int* wg);
+
+/* Measurement aid: {spo_critic_fit_iter_ks_multi launches enqueued, runs that took part in them, of those: runs whose placement
+ * census chose write-through exchange stores} since the last reset (out3_host, host array).  The third is counted by the kernel
+ * in a word per run of its own, beside the one spo_debug_update_ks_multi_counters reads (which keeps counting the first-order
+ * launches only); the call synchronises the device to read it. */
+int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_host, int reset);
+
 /* Form of the in-kernel gradient exchange (which of the built all-reduce forms runs inside the persistent update
  * kernel).  spo_p2p_select_form pins one for the process (-1: back to the default policy: environment overrides, else the row-split
  * form at 2 / 4 / 8 ranks -- shapes outside the row-split kernel run the four-wave kernel -- recursive doubling at 2 / 4 ranks and

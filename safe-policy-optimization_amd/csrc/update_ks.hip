@@ -20,7 +20,9 @@
 // Three instantiations of one body: the clipped-surrogate step (ppo_update_ks_kernel: spo_ppo_lag_update_iter_ks), the KL-penalty
 // actor loss of FOCOPS / CUP with separate optimiser clocks and an actor-only launch (klpen_update_ks_kernel, AMODE 1:
 // spo_update_iter_ex_ks), and the second-order scripts' critic fit (critic_fit_ks_kernel, CFIT: two networks, minibatches of up
-// to 128 rows as two 64-column chunks, the actor's stale gradient norm in the joint clip: spo_critic_fit_iter_ks).
+// to 128 rows as two 64-column chunks, the actor's stale gradient norm in the joint clip: spo_critic_fit_iter_ks).  Each of the
+// three also has a seed-batched kernel (*_ks_multi_kernel: several independent runs in one launch, every run on workgroups of its
+// own; spo_update_iter_ex_ks_multi for the first two, spo_critic_fit_iter_ks_multi for the critic fit).
 //
 // The arithmetic per element is that of ppo_update_kernel (same MFMA chaining, loss, Adam); the first layer's dot products are
 // summed slice by slice instead of in one chain (rounding-level difference; tests: 1e-5 on the first steps + the fp64 drift
@@ -1043,27 +1045,32 @@ __global__ __launch_bounds__(256, 1) void ppo_grad_ks_kernel(KsArgs a) {
   ks_entry<false, 0, true>(a, (int)(blockIdx.x >> 3));
 }
 
-// Seed-batched launches (spo_update_iter_ex_ks_multi): S independent runs (own parameters, optimiser state and clocks, buffers,
+// Seed-batched launches (spo_update_iter_ex_ks_multi; the critic fit: spo_critic_fit_iter_ks_multi): S independent runs (own parameters, optimiser state and clocks, buffers,
 // shuffle, scalars, exchange slots, granules, census words, error word) take the minibatch steps of one learning iteration in ONE
 // launch, run r on its own n_nets * S workgroups of XCD label r & 7 (rs_multi_map, update_rs.h).  The step is ks_entry's,
 // unchanged: every run's a.zbuf / a.gran point into a block the library owns, so each run holds its own census and exchanges only
 // with itself.  One run's arguments as the kernel reads them from the device table:
 struct KsMultiEntry { KsArgs a; int active; };
 
-template <int AMODE>
+template <bool CFIT, int AMODE>
 __device__ __forceinline__ void ks_multi_entry(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
   int rep, wg;
   if (!rs_multi_map((int)blockIdx.x, n_replicas, wgs, &rep, &wg)) return;
   if (!table[rep].active) return;                // (uniform: before any barrier, before touching memory of the run)
   const KsArgs a = table[rep].a;                 // uniform address: scalar loads, once
-  // the run's write-through count sits behind its granules and census words (KS_G_BYTES of the run's 4 KB granule page)
-  ks_entry<false, AMODE, false, true>(a, wg, reinterpret_cast<unsigned*>(a.gran + 2 * 2 * 3 * KS_MAX_SLICES + 3 * KS_MAX_SLICES));
+  // the run's write-through counts sit behind its granules and census words (KS_G_BYTES of the run's 4 KB granule page): word 0
+  // counts the first-order launches, word 1 the critic fit's (spo_debug_critic_fit_ks_multi_counters)
+  ks_entry<CFIT, AMODE, false, true>(a, wg, reinterpret_cast<unsigned*>(a.gran + 2 * 2 * 3 * KS_MAX_SLICES + 3 * KS_MAX_SLICES) + (CFIT ? 1 : 0));
 }
 __global__ __launch_bounds__(256, 1) void ppo_update_ks_multi_kernel(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
-  ks_multi_entry<0>(table, n_replicas, wgs);
+  ks_multi_entry<false, 0>(table, n_replicas, wgs);
 }
 __global__ __launch_bounds__(256, 1) void klpen_update_ks_multi_kernel(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
-  ks_multi_entry<1>(table, n_replicas, wgs);
+  ks_multi_entry<false, 1>(table, n_replicas, wgs);
+}
+// spo_critic_fit_iter_ks_multi: the critic fit (CFIT) of every active run, run r on its own 2 * S workgroups (wgs) of XCD label r & 7
+__global__ __launch_bounds__(256, 1) void critic_fit_ks_multi_kernel(const KsMultiEntry* __restrict__ table, int n_replicas, int wgs) {
+  ks_multi_entry<true, 0>(table, n_replicas, wgs);
 }
 
 // Exchange scratch of the kernel: the partial pre-activation words and the norm granules, ordinary device memory (agent-scope
@@ -1109,11 +1116,14 @@ int ks_scratch(hipStream_t st, KsScratch* out, unsigned* tag_base, unsigned nste
 
 // Per-run state of the seed-batched launches (spo_update_iter_ex_ks_multi), one block per (device, stream), separate from g_ks,
 // allocated at the first call (never under capture), zeroed once and kept: SPO_KS_MAX_REPLICAS strides of
-//   [KS_Z_BYTES exchange slots, zero row, dump row | 4 KB page: KS_G_BYTES granules + census words, then the run's write-through count]
+//   [KS_Z_BYTES exchange slots, zero row, dump row | 4 KB page: KS_G_BYTES granules + census words, then the run's two write-through
+//    counts: the first-order launches', the critic fit's]
+// -- shared by spo_critic_fit_iter_ks_multi: launches on one stream are ordered, every launch primes the slots of its active runs, and
+// one tag counter per block serves both (a tag never repeats within a block) --
 // then the argument table -- 16 x 7 090 176 bytes + the table = 113 449 344 bytes (108.2 MB).  The table leaves the host from pinned
 // memory: KSM_TAB_RING tables per entry, used in turn, each with an event recorded behind its copy (update.hip: exm_scratch).
 constexpr size_t KSM_G_PAGE = 4096;
-static_assert(KS_G_BYTES + sizeof(unsigned) <= KSM_G_PAGE && KS_Z_BYTES % 4096 == 0, "a run's granule page");
+static_assert(KS_G_BYTES + 2 * sizeof(unsigned) <= KSM_G_PAGE && KS_Z_BYTES % 4096 == 0, "a run's granule page");
 constexpr size_t KSM_STRIDE = KS_Z_BYTES + KSM_G_PAGE;
 constexpr size_t KSM_T_OFF = (size_t)SPO_KS_MAX_REPLICAS * KSM_STRIDE;
 constexpr size_t KSM_BYTES = KSM_T_OFF + (((size_t)SPO_KS_MAX_REPLICAS * sizeof(KsMultiEntry) + 4095) & ~(size_t)4095);
@@ -1125,16 +1135,22 @@ std::mutex g_ksm_mu;
 std::atomic<unsigned long long> g_ksm_counters[2];       // {launches enqueued, runs that took part}
 unsigned long long g_ksm_wt_released = 0;                // write-through counts of blocks that have been released (under g_ksm_mu)
 
-inline unsigned* ksm_wt_word(char* base, int r) { return reinterpret_cast<unsigned*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES + KS_G_BYTES); }
+std::atomic<unsigned long long> g_ksm_cfit_counters[2];  // the same two of the critic fit's launches (spo_critic_fit_iter_ks_multi)
+unsigned long long g_ksm_cfit_wt_released = 0;
+
+// which: 0 = the first-order launches' count, 1 = the critic fit's (the word behind it)
+inline unsigned* ksm_wt_word(char* base, int r, int which = 0) {
+  return reinterpret_cast<unsigned*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES + KS_G_BYTES) + which;
+}
 
 // sums (and optionally clears) the write-through counts of one block; the caller holds g_ksm_mu and has synchronised the device
-int ksm_harvest(KsmEntry& e, unsigned long long* sum, bool clear) {
+int ksm_harvest(KsmEntry& e, unsigned long long* sum, bool clear, int which = 0) {
   for (int r = 0; r < SPO_KS_MAX_REPLICAS; ++r) {
     unsigned v = 0;
-    if (int rc = spo::hip_check(hipMemcpy(&v, ksm_wt_word(e.base, r), sizeof(v), hipMemcpyDeviceToHost), "hipMemcpy(ks multi count)")) return rc;
+    if (int rc = spo::hip_check(hipMemcpy(&v, ksm_wt_word(e.base, r, which), sizeof(v), hipMemcpyDeviceToHost), "hipMemcpy(ks multi count)")) return rc;
     *sum += v;
     if (clear && v)
-      if (int rc = spo::hip_check(hipMemset(ksm_wt_word(e.base, r), 0, sizeof(v)), "hipMemset(ks multi count)")) return rc;
+      if (int rc = spo::hip_check(hipMemset(ksm_wt_word(e.base, r, which), 0, sizeof(v)), "hipMemset(ks multi count)")) return rc;
   }
   return 0;
 }
@@ -1204,8 +1220,10 @@ int spo::ks_scratch_release(int dev, void* stream_or_null, int all) {
   std::lock_guard<std::mutex> lk(g_ksm_mu);
   for (int i = 0; i < g_ksm_n;) {
     if (g_ksm[i].dev == dev && (all || g_ksm[i].stream == stream_or_null)) {
-      if (spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)") == 0)
-        (void)ksm_harvest(g_ksm[i], &g_ksm_wt_released, false);       // (the debug counter outlives the block)
+      if (spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)") == 0) {
+        (void)ksm_harvest(g_ksm[i], &g_ksm_wt_released, false);       // (the debug counters outlive the block)
+        (void)ksm_harvest(g_ksm[i], &g_ksm_cfit_wt_released, false, 1);
+      }
       ksm_free(g_ksm[i]);
       g_ksm[i] = g_ksm[--g_ksm_n];
       g_ksm[g_ksm_n] = KsmEntry{};
@@ -1505,5 +1523,140 @@ extern "C" int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_hos
   SPO_LAUNCH_CHECK("spo_update_iter_ex_ks_multi");
   g_ksm_counters[0] += 1ull;
   g_ksm_counters[1] += (unsigned long long)n_active;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- seed-batched spo_critic_fit_iter_ks
+// At most 24 working blocks per XCD label, as above; a run is 2 S blocks (two critics x S slices), so 24 / (2 S) runs per label:
+// 16 runs up to 384 observations (S <= 6: two per label), 8 at 385 .. 512.
+static int cfit_ks_multi_cap(int S) {
+  const int cap = 8 * (24 / (2 * S));
+  return cap < SPO_KS_MAX_REPLICAS ? cap : SPO_KS_MAX_REPLICAS;
+}
+
+extern "C" int spo_critic_fit_ks_multi_supported(int obs_dim, int batch, int n_replicas) {
+  if (!spo_critic_fit_ks_supported(obs_dim, batch)) return 0;
+  return (n_replicas >= 1 && n_replicas <= cfit_ks_multi_cap((obs_dim + 63) / 64)) ? 1 : 0;
+}
+
+extern "C" int spo_critic_fit_ks_multi_block_map(int block, int obs_dim, int n_replicas, int* replica, int* wg) {
+  if (!spo_critic_fit_ks_multi_supported(obs_dim, 1, n_replicas)) return 0;
+  const int wgs = 2 * ((obs_dim + 63) / 64);
+  if (block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
+  int r = 0, w = 0;
+  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
+  if (work && replica) *replica = r;
+  if (work && wg) *wg = w;
+  return work ? 1 : 0;
+}
+
+extern "C" int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_host, int reset) {
+  SPO_REQUIRE(out3_host, "critic_fit_ks_multi_counters: null pointer");
+  if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(critic_fit_ks_multi_counters)")) return rc;
+  std::lock_guard<std::mutex> lk(g_ksm_mu);
+  const int dev = current_device_slot();
+  unsigned long long wt = g_ksm_cfit_wt_released;
+  for (int i = 0; i < g_ksm_n; ++i)
+    if (g_ksm[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm[i], &wt, reset != 0, 1)) return rc;
+  if (reset) g_ksm_cfit_wt_released = 0;
+  for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_cfit_counters[i].exchange(0ull) : g_ksm_cfit_counters[i].load();
+  out3_host[2] = wt;
+  return 0;
+}
+
+extern "C" int spo_critic_fit_iter_ks_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream) {
+  // ---- everything that can be refused is refused here, before any HIP call
+  SPO_REQUIRE(reps_host, "critic_fit_iter_ks_multi: null replica table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_KS_MAX_REPLICAS, "critic_fit_iter_ks_multi: %d replicas outside [1, %d]",
+              n_replicas, SPO_KS_MAX_REPLICAS);
+  SPO_REQUIRE(M > 0, "critic_fit_iter_ks_multi: bad sizes (M = %lld)", (long long)M);
+  const spo_ppo_cfg& c0 = reps_host[0].cfg;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_replica& p = reps_host[r];
+    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
+                "critic_fit_iter_ks_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
+                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+  }
+  SPO_REQUIRE(spo_critic_fit_ks_supported(c0.obs_dim, c0.batch),
+              "critic_fit_iter_ks_multi: obs_dim %d / batch %d outside [1,%d] / [1,128]", c0.obs_dim, c0.batch, 64 * KS_MAX_SLICES);
+  SPO_REQUIRE(c0.act_dim >= 1, "critic_fit_iter_ks_multi: act_dim %d (the flat parameter layout needs the actor's size)", c0.act_dim);
+  const int S = (c0.obs_dim + 63) / 64;
+  SPO_REQUIRE(spo_critic_fit_ks_multi_supported(c0.obs_dim, c0.batch, n_replicas),
+              "critic_fit_iter_ks_multi: %d replicas at obs_dim %d: at most %d runs share a launch (24 workgroups of a run's %d per "
+              "XCD; spo_critic_fit_ks_multi_supported)", n_replicas, c0.obs_dim, cfit_ks_multi_cap(S), 2 * S);
+  const int64_t nsteps = (M + c0.batch - 1) / c0.batch;
+  SPO_REQUIRE(nsteps < (1ll << 30), "critic_fit_iter_ks_multi: too many minibatch steps in one launch");
+  int n_active = 0;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_replica& p = reps_host[r];
+    SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.target_r && p.target_c && p.sync_ws &&
+                    ((p.perm && p.losses_out) || !p.active), "critic_fit_iter_ks_multi: null pointer in replica %d", r);
+    SPO_REQUIRE(p.stale_sq_io, "critic_fit_iter_ks_multi: stale_sq_io is NULL in replica %d", r);
+    SPO_REQUIRE(p.adam_step >= 0, "critic_fit_iter_ks_multi: replica %d: negative adam_step", r);
+    for (int q = 0; q < r; ++q)
+      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws && reps_host[q].stale_sq_io != p.stale_sq_io,
+                  "critic_fit_iter_ks_multi: replicas %d and %d share theta, sync_ws or stale_sq_io", q, r);
+    n_active += p.active ? 1 : 0;
+  }
+  if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
+  hipStream_t st = (hipStream_t)stream;
+  {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return spo::fail(-1, "critic_fit_iter_ks_multi: the stream is under capture (the argument table is copied from host memory at "
+                           "every call: not a graph node)");
+  }
+  const int wgs = 2 * S;
+  int force_safe;
+  { const char* e = getenv("SPO_KS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  std::lock_guard<std::mutex> lk(g_ksm_mu);                                // (until the table's copy and its event are enqueued)
+  char* base = nullptr;
+  KsMultiEntry* tab = nullptr;
+  hipEvent_t tab_ev = nullptr;
+  unsigned tag_base = 0;
+  if (int rc = ksm_scratch(st, (unsigned)nsteps, &base, &tab, &tab_ev, &tag_base)) return rc;
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_critic_fit_replica& p = reps_host[r];
+    KsArgs a{};                                                            // (as spo_critic_fit_iter_ks and ks_launch fill it)
+    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
+    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c;
+    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out; a.stale_io = p.stale_sq_io;
+    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * KSM_STRIDE);
+    a.gran = reinterpret_cast<unsigned long long*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
+    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
+    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
+    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
+    a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
+    a.tag_base = tag_base; a.S = S; a.n_nets = 2; a.first_net = 0;
+    a.force_safe = force_safe;
+    tab[r].a = a;
+    tab[r].active = p.active ? 1 : 0;
+  }
+  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(base + KSM_T_OFF);
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(KsMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(ks replica table)")) return rc;
+  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(ks replica table)")) return rc;
+  // every partial slot of every active run starts as the sentinel (ks_launch); the run's row of zeros behind them stays zero.
+  // (sync_ws: only the error word at byte 64 is the kernel's; its first 64 bytes are NOT zeroed here, unlike ks_launch -- nothing
+  // of the feature-split kernels reads them, and an inactive run's sync_ws must stay untouched)
+  for (int r = 0; r < n_replicas; ++r)
+    if (reps_host[r].active)
+      if (int rc = spo::hip_check(hipMemsetAsync(base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
+        return rc;
+  const size_t sh = KsLds::SIZE * sizeof(float);
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  const int dslot = current_device_slot();
+  if (!attr_done[dslot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&critic_fit_ks_multi_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(critic_fit_ks_multi)");
+    attr_done[dslot] = true;
+  }
+  const dim3 grid(spo::rs_multi_grid(n_replicas, wgs));
+  hipLaunchKernelGGL(critic_fit_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
+  SPO_LAUNCH_CHECK("spo_critic_fit_iter_ks_multi");
+  g_ksm_cfit_counters[0] += 1ull;
+  g_ksm_cfit_counters[1] += (unsigned long long)n_active;
   return 0;
 }

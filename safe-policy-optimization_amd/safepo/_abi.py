@@ -167,6 +167,10 @@ PROTOTYPES = {
     "spo_debug_update_ks_multi_counters": (c_int, [P, c_int]),
     "spo_critic_fit_ks_supported": (c_int, [c_int, c_int]),
     "spo_critic_fit_iter_ks": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
+    "spo_critic_fit_iter_ks_multi": (c_int, [POINTER(CriticFitReplica), c_int, c_int64, P]),
+    "spo_critic_fit_ks_multi_supported": (c_int, [c_int, c_int, c_int]),
+    "spo_critic_fit_ks_multi_block_map": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "spo_debug_critic_fit_ks_multi_counters": (c_int, [P, c_int]),
     "spo_update_scratch_release": (c_int, [P, c_int]),
     "spo_debug_update_counters": (c_int, [P, c_int]),
     "spo_debug_crosslane_selftest": (c_int, [P, P, P]),

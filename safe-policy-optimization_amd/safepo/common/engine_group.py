@@ -459,27 +459,43 @@ class CPOEngineGroup(_EngineGroup):
     GPU and stay one run after the other.  `rngs`: one ReplicaRNG per engine -- run i's default shuffle is drawn under rngs[i].
     `split_form=True` also admits WideCPOEngines whose critics are on the persistent kernel at 65-128 observations (up to 32):
     their two-replica split critic fits share one launch per iteration (spo_critic_fit_iter_split_multi, csrc/update.hip: run r
-    on its own four co-XCD workgroups), each bit for bit its own spo_critic_fit_iter_split; see batched_split()."""
+    on its own four co-XCD workgroups), each bit for bit its own spo_critic_fit_iter_split; see batched_split().
+    `ks_form=True` also admits WideCPOEngines at 129-512 observations with hidden [64, 64] (HumanoidVelocity's 376 / 17), whose
+    critic fit runs on the feature-split kernel: their critic fits share one launch per iteration
+    (spo_critic_fit_iter_ks_multi, csrc/update_ks.hip: run r on its own 2 x ceil(obs_dim / 64) workgroups of XCD label r mod 8;
+    up to 16 runs up to 384 observations, 8 up to 512), each bit for bit its own spo_critic_fit_iter_ks; see batched_ks()."""
 
-    def __init__(self, engines, rngs=None, split_form=False):
+    KS_MIN_OBS, KS_MAX_OBS = _abi.MAX_OBS + 1, 512      # above the persistent two-critic kernel, inside the feature-split kernel
+
+    def __init__(self, engines, rngs=None, split_form=False, ks_form=False):
         from safepo.single_agent.cpo import CPOEngine, WideCPOEngine
         engines = list(engines)
         if not engines:
             raise ValueError("CPOEngineGroup: no engines")
-        self.split_form = bool(split_form)
+        self.split_form, self.ks_form = bool(split_form), bool(ks_form)
 
         def takes_split(e):
             return (self.split_form and type(e) is WideCPOEngine and getattr(e, "_critics_on_persistent_kernel", False)
                     and 65 <= e.D <= _abi.MAX_OBS)
 
-        # the split form's launch holds up to 32 runs (four workgroups each) at 65-128 observations; everything else 24
-        cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if takes_split(engines[0]) else _abi.RS_CRITIC_MAX_REPLICAS
+        def takes_ks(e):
+            return (self.ks_form and type(e) is WideCPOEngine and not getattr(e, "_critics_on_persistent_kernel", False)
+                    and self.KS_MIN_OBS <= e.D <= self.KS_MAX_OBS and list(e.policy.hidden_sizes) == [64, 64])
+
+        self._takes_ks = takes_ks
+        # the split form's launch holds up to 32 runs (four workgroups each) at 65-128 observations; the feature-split form what
+        # 24 workgroups per XCD leave of its 2 x ceil(obs_dim / 64) a run (spo_critic_fit_ks_multi_supported); everything else 24
+        if takes_ks(engines[0]):
+            lib = _abi.load()
+            cap = max(n for n in range(1, _abi.KS_MAX_REPLICAS + 1) if lib.spo_critic_fit_ks_multi_supported(engines[0].D, 1, n))
+        else:
+            cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if takes_split(engines[0]) else _abi.RS_CRITIC_MAX_REPLICAS
         if len(engines) > cap:
             raise _abi.SpoError(f"CPOEngineGroup: {len(engines)} engines; at most {cap} critic fits share a launch")
         e0 = engines[0]
         for i, e in enumerate(engines):
             if isinstance(e, CPOEngine):
-                if takes_split(e):
+                if takes_split(e) or takes_ks(e):
                     pass
                 elif type(e) is not CPOEngine:
                     raise _abi.SpoError(f"CPOEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
@@ -645,11 +661,96 @@ class CPOEngineGroup(_EngineGroup):
             outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
         return outs
 
+    # ------------------------------------------------------------------ the feature-split form (129-512 observations)
+    def batched_ks(self) -> bool:
+        """Does critic_fit_all run the feature-split critic fits of all runs as one launch per iteration
+        (spo_critic_fit_iter_ks_multi)?  Only in a group built with ks_form=True, where every engine's own critic_fit would
+        take the feature-split kernel too (_feature_split_critic_fit_ok: hidden [64, 64], one GPU, not SPO_WIDE_KS=0), all
+        runs share the minibatch size and the library has the form for this shape and run count
+        (spo_critic_fit_ks_multi_supported)."""
+        if not (self.ks_form and self._native):
+            return False
+        es = self.engines
+        if not all(self._takes_ks(e) for e in es):
+            return False
+        cfgs = [e._cfg_struct() for e in es]
+        if any(c.batch != cfgs[0].batch for c in cfgs):
+            return False
+        if not all(e._feature_split_critic_fit_ok(c) for e, c in zip(es, cfgs)):
+            return False
+        return bool(self.lib.spo_critic_fit_ks_multi_supported(es[0].D, cfgs[0].batch, len(es)))
+
+    def fit_iter_ks_all(self, perms, active=None):
+        """One iteration of WideCPOEngine.critic_fit's feature-split loop for every run i with active[i] in ONE launch;
+        adam_step advances per run.  Returns the losses [n_mb, 3] per run (columns 0, 1 are written; None for a run that sat
+        out)."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        if len(perms) != S or len(active) != S:
+            raise ValueError("fit_iter_ks_all: one perm and one active flag per engine")
+        cfgs = [e._cfg_struct() for e in self.engines]
+        e0 = self.engines[0]
+        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
+        reps = (_abi.CriticFitReplica * S)()
+        losses = [None] * S
+        for i, e in enumerate(self.engines):
+            d = e.buffer.data
+            perm = perms[i] if active[i] else None
+            if perm is not None:
+                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
+                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            r = reps[i]
+            r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
+            r.obs, r.target_r, r.target_c = _abi.ptr(d["obs"]), _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"])
+            r.perm, r.losses_out, r.stale_sq_io = _abi.ptr(perm), _abi.ptr(losses[i]), _abi.ptr(e.stale_sq)
+            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
+        _abi.check(self.lib.spo_critic_fit_iter_ks_multi(reps, S, e0.M, _abi.stream_ptr()), "spo_critic_fit_iter_ks_multi")
+        for i, e in enumerate(self.engines):
+            if active[i]:
+                e.adam_step += n_mb
+        return losses
+
+    def _critic_fit_all_ks(self, perm_fns):
+        """critic_fit_all where batched_ks(): the feature-split loop of WideCPOEngine.critic_fit for every run, one launch per
+        iteration; after the loop every run's error word (one host read for all) and the rescale of its stale actor-gradient
+        vector to the norm the kernel carried.  An exchange error is not degraded to another form: every run's critics,
+        moments, stale norm and adam_step are restored to the start of this critic fit (the stale vector has not been touched
+        yet) and the error raised, naming the run."""
+        es, S = self.engines, len(self.engines)
+        backups = [(e.policy.theta.clone(), e.adam_m.clone(), e.adam_v.clone(), e.stale_sq.clone(), e.adam_step) for e in es]
+        n_its = [e.cfg["learning_iters"] for e in es]
+        all_losses = [[] for _ in range(S)]
+        for it in range(max(n_its)):
+            active = [it < n for n in n_its]
+            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
+            losses = self.fit_iter_ks_all(perms, active)
+            for i in range(S):
+                if active[i]:
+                    all_losses[i].append(losses[i][:, :2])
+        codes = [int(c) & 0xFFFFFFFF for c in torch.stack([e.sync_ws[8].to(torch.int64) for e in es]).cpu().tolist()]
+        bad = [i for i in range(S) if codes[i]]
+        if bad:
+            for e, b in zip(es, backups):
+                e.sync_ws[8] = 0
+                e.policy.theta.copy_(b[0]); e.adam_m.copy_(b[1]); e.adam_v.copy_(b[2]); e.stale_sq.copy_(b[3])
+                e.adam_step = b[4]
+            i = bad[0]
+            raise _abi.SpoError(f"replica {i} of {S}: feature-split critic fit: exchange error {codes[i]} (the inter-workgroup "
+                                "exchange of the seed-batched launch timed out); every run's critics, moments and stale norm are "
+                                "restored to the start of this critic fit")
+        outs = []
+        for e, b, ls in zip(es, backups, all_losses):
+            e.flat_grad[e.ls_off:].mul_(torch.sqrt(e.stale_sq / b[3].clamp_min(1e-38)))
+            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
+            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
+        return outs
+
     def critic_fit_all(self, perm_fns=None):
         """CPOEngine.critic_fit for every run: learning_iters iterations each (a run with fewer sits out the later launches),
         every iteration's shuffle drawn per run -- under its ReplicaRNG by default -- before that iteration's launch, as the
         stand-alone loop draws it.  Where batched_split() (a split_form group at 65-128 observations): the same loop on the
-        two-replica split form.  Where neither: each engine's own critic_fit, one after the other -- the same results.
+        two-replica split form.  Where batched_ks() (a ks_form group at 129-512 observations): the same loop on the
+        feature-split kernel.  Where none of them: each engine's own critic_fit, one after the other -- the same results.
         Returns the list of critic_fit()'s dicts."""
         es, S = self.engines, len(self.engines)
 
@@ -665,6 +766,8 @@ class CPOEngineGroup(_EngineGroup):
         perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
         if self.batched_split():
             return self._critic_fit_all_split(perm_fns)
+        if self.batched_ks():
+            return self._critic_fit_all_ks(perm_fns)
         if not self.batched():
             return [e.critic_fit(perm_fns[i]) for i, e in enumerate(es)]
         n_its = [e.cfg["learning_iters"] for e in es]

@@ -26,7 +26,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from safepo.utils.config import CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES
+from safepo.utils.config import CRITIC_KS_BATCH_FIGURES, CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -77,6 +77,11 @@ def parse_args(argv=None):
                         "observations; up to 32 seeds per subprocess, --batch-critic-fit True --batch-critic-fit-split True on those "
                         "commands): their two-replica split critic fits share one persistent launch per iteration.  "
                         + CRITIC_SPLIT_BATCH_FIGURES + "  Default off: those tasks keep one subprocess per seed")
+    p.add_argument("--batch-second-order-feature-split", action="store_true",
+                   help="with --batch-second-order: also group those scripts on HumanoidVelocity (376 / 17: the critic fit on the "
+                        "feature-split kernel; at most 8 seeds per subprocess, --batch-critic-fit True "
+                        "--batch-critic-fit-feature-split True on those commands): their critic fits share one launch per "
+                        "iteration.  " + CRITIC_KS_BATCH_FIGURES + "  Default off: HumanoidVelocity keeps one subprocess per seed")
     p.add_argument("--batch-focops-cup", action="store_true",
                    help="with --seeds-per-run: also group focops / cup (--batch-update True on those commands; HumanoidVelocity "
                         "excepted).  " + KLPEN_BATCH_FIGURES + "  Default off: these algorithms keep one subprocess per seed")
@@ -94,6 +99,7 @@ KLPEN_BATCHED_ALGOS = ("focops", "cup")                       # ... with --batch
 CRITIC_BATCH_MAX = 24                                         # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
 CRITIC_SPLIT_BATCH_MAX = 32                                   # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
+CRITIC_KS_BATCH_MAX = 8                                       # seeds per subprocess at 376 observations: one run per XCD label
 KS_BATCH_MAX = 8                                              # spo_update_ks_multi_supported at 376 observations (S = 6: one run per XCD)
 
 
@@ -126,6 +132,12 @@ def _takes_critic_split_batch(algo: str, task: str) -> bool:
     return algo in CRITIC_BATCHED_ALGOS and _is_wide_obs_nav(task)
 
 
+def _takes_critic_ks_batch(algo: str, task: str) -> bool:
+    """Can `--seeds ... --batch-critic-fit True --batch-critic-fit-feature-split True` carry several seeds?  HumanoidVelocity
+    (376 / 17, hidden [64, 64]: the critic fit on the feature-split kernel) for the six second-order scripts."""
+    return algo in CRITIC_BATCHED_ALGOS and "Humanoid" in task
+
+
 def _takes_wide_obs_batch(algo: str, task: str, klpen_too: bool) -> bool:
     """Can `--seeds ... --batch-wide-obs True` carry several seeds?  HumanoidVelocity (376 / 17, hidden [64, 64]: the feature-split
     kernel) for the PPO family, and for focops / cup where --batch-focops-cup adds `--batch-update True`."""
@@ -136,6 +148,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
     n_gpus = n_gpus or visible_gpus()
     if getattr(args, "batch_second_order_wide_obs", False) and not getattr(args, "batch_second_order", False):
         raise SystemExit("--batch-second-order-wide-obs widens --batch-second-order: give both")
+    if getattr(args, "batch_second_order_feature_split", False) and not getattr(args, "batch_second_order", False):
+        raise SystemExit("--batch-second-order-feature-split widens --batch-second-order: give both")
     per_run = max(getattr(args, "seeds_per_run", 1), 1)
     if per_run > 32:
         raise SystemExit("--seeds-per-run: at most 32 seeds share a launch")
@@ -153,6 +167,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                 klpen = getattr(args, "batch_focops_cup", False) and _takes_klpen_batch(algo, task)
                 split = (getattr(args, "batch_second_order", False) and getattr(args, "batch_second_order_wide_obs", False)
                          and _takes_critic_split_batch(algo, task))
+                critic_ks = (getattr(args, "batch_second_order", False) and getattr(args, "batch_second_order_feature_split", False)
+                             and _takes_critic_ks_batch(algo, task))
                 wide = (getattr(args, "batch_wide_obs", False)
                         and _takes_wide_obs_batch(algo, task, getattr(args, "batch_focops_cup", False)))
                 runs = [[s] for s in group]
@@ -164,6 +180,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                     runs = [group[i:i + CRITIC_BATCH_MAX] for i in range(0, len(group), CRITIC_BATCH_MAX)]
                 elif len(group) > 1 and split:
                     runs = [group[i:i + CRITIC_SPLIT_BATCH_MAX] for i in range(0, len(group), CRITIC_SPLIT_BATCH_MAX)]
+                elif len(group) > 1 and critic_ks:
+                    runs = [group[i:i + CRITIC_KS_BATCH_MAX] for i in range(0, len(group), CRITIC_KS_BATCH_MAX)]
                 for run in runs:
                     batched = len(run) > 1
                     commands.append(" ".join([
@@ -171,6 +189,7 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                         "--seed", str(run[0])] + (["--seeds"] + [str(s) for s in run] if batched else [])
                         + (["--batch-critic-fit", "True"] if batched and critic else [])
                         + (["--batch-critic-fit", "True", "--batch-critic-fit-split", "True"] if batched and split else [])
+                        + (["--batch-critic-fit", "True", "--batch-critic-fit-feature-split", "True"] if batched and critic_ks else [])
                         + (["--batch-update", "True"] if batched and (klpen or (wide and algo in KLPEN_BATCHED_ALGOS)) else [])
                         + (["--batch-wide-obs", "True"] if batched and wide else []) + [
                         "--write-terminal", "False", "--experiment",

@@ -938,7 +938,10 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
     the critic fits of all seeds run through CPOEngineGroup, one launch per iteration.  The Time/ columns hold the wall time of
     the phase for ALL seeds of the process.  With `--batch-critic-fit-split True` as well, tasks with 65-128 observations (hidden
     [64, 64]: WideCPOEngine, whose critic fit takes the two-replica split form) are taken too, up to 32 seeds: their split critic
-    fits share one launch per iteration (CPOEngineGroup(split_form=True))."""
+    fits share one launch per iteration (CPOEngineGroup(split_form=True)).  With `--batch-critic-fit-feature-split True`, tasks
+    with 129-512 observations and up to 32 actions (hidden [64, 64]: HumanoidVelocity's 376 / 17 -- WideCPOEngine with the actor
+    on the streamed full-batch kernels and the critic fit on the feature-split kernel) are taken, up to 16 seeds up to 384
+    observations and 8 up to 512: their critic fits share one launch per iteration (CPOEngineGroup(ks_form=True))."""
     from safepo.common.engine_group import CPOEngineGroup, ReplicaRNG
     seeds = seed_list(args)
     if len(set(seeds)) != len(seeds):
@@ -947,6 +950,10 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
     seed_cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if split_form else _abi.RS_CRITIC_MAX_REPLICAS
     if len(seeds) > seed_cap:
         raise SystemExit(f"--seeds: at most {seed_cap} seeds share the critic fit's launch, got {len(seeds)}")
+    ks_form = bool(getattr(args, "batch_critic_fit_feature_split", False))
+    if ks_form and len(seeds) > _abi.KS_MAX_REPLICAS:
+        raise SystemExit(f"--seeds: at most {_abi.KS_MAX_REPLICAS} seeds share a launch with --batch-critic-fit-feature-split True (8 "
+                         f"above 384 observations), got {len(seeds)}")
     if args.device == "cpu":
         raise RuntimeError("this build runs the CPO hot path on a ROCm GPU only (--device cuda); no CPU fallback")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -981,6 +988,18 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
                 # 65-128 observations: the critics keep the persistent two-critic kernel whatever the actor's width (their layout
                 # is act-free) -- WideCPOEngine, whose critic fit takes the two-replica split form
                 r.engine = make_engine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
+            elif (ks_form and list(config["hidden_sizes"]) == [64, 64]
+                  and _abi.load().spo_cpo512_supported(D, act_space.shape[0])):
+                # 129-512 observations, up to 32 actions (HumanoidVelocity's 376 / 17): WideCPOEngine, whose critic fit runs on the
+                # feature-split kernel.  The seed cap depends on the observation count, which only the (first) environment tells:
+                # checked before anything is logged
+                lib = _abi.load()
+                if not lib.spo_critic_fit_ks_multi_supported(D, 1, len(seeds)):
+                    cap = max(n for n in range(1, _abi.KS_MAX_REPLICAS + 1) if lib.spo_critic_fit_ks_multi_supported(D, 1, n))
+                    raise SystemExit(f"--seeds: at most {cap} seeds share the feature-split critic fit's launch at {D} observations "
+                                     f"(--batch-critic-fit-feature-split True: {_abi.KS_MAX_REPLICAS} up to 384 observations, 8 up "
+                                     f"to 512), got {len(seeds)}")
+                r.engine = make_engine(r.policy, args.num_envs, local_steps_per_epoch, config, device)
             elif not r.policy.kernels_supported("cpo"):
                 limit = (f"obs_dim <= {_abi.MAX_OBS}, and act_dim <= 16 up to 64 observations" if split_form
                          else "obs_dim <= 64, act_dim <= 16")
@@ -1006,7 +1025,7 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
             obs, _ = r.env.reset()
             r.obs = _to_dev(obs, device)
         runs.append(r)
-    group = CPOEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs], split_form=split_form)
+    group = CPOEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs], split_form=split_form, ks_form=ks_form)
 
     timings, outs = [], []
     for epoch in range(epochs):

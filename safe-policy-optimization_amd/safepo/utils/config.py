@@ -75,6 +75,9 @@ def critic_seed_batch(args) -> bool:
     --batch-critic-fit True (their critic fits then share one launch per iteration); without it they are refused as ever."""
     if getattr(args, "batch_critic_fit_split", False) and not getattr(args, "batch_critic_fit", False):
         raise SystemExit("--batch-critic-fit-split True widens --batch-critic-fit True (65-128 observations, up to 32 seeds): give both")
+    if getattr(args, "batch_critic_fit_feature_split", False) and not getattr(args, "batch_critic_fit", False):
+        raise SystemExit("--batch-critic-fit-feature-split True widens --batch-critic-fit True (129-512 observations, up to 16 seeds): "
+                         "give both")
     if len(seed_list(args)) <= 1:
         return False
     if not getattr(args, "batch_critic_fit", False):
@@ -96,6 +99,15 @@ CRITIC_SPLIT_BATCH_FIGURES = ("Measured at 72 / 2, 4096 x 128 rows, batch 128, o
                               "step rate; one seed alone: 17.75 against 15.74 us, which is why one seed stays `--seed`); cpo's second epoch with "
                               "8 seeds at 72 observations: Time/Update 0.94 s against 5.34 s, one sample each "
                               "(profiles/seed_batch_critic_split/step_times.txt).")
+
+
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_critic_ks/step_times.txt)
+CRITIC_KS_BATCH_FIGURES = ("Measured at 376 / 17, 4096 x 128 rows, batch 128: one critic-fit step of ALL seeds takes 26.5 / 26.5 / 26.5 / 26.8 us at 2 / 4 / "
+                           "8 / 16 seeds against 25.9 us per seed one after the other (1.95 x / 3.92 x / 7.81 x / 15.48 x the aggregate step rate; 16 "
+                           "seeds, two per XCD, lose nothing measurable); one seed alone: 26.58 against 25.90 us, which is why one seed stays "
+                           "`--seed`; 512 / 32 with 8 seeds: 26.66 us against 207.54 (7.79 x); the critic fit is 0.96 of a stand-alone run's "
+                           "Time/Update at this shape; cpo's second epoch with 8 seeds at 376 / 17: Time/Update 1.45 s against 8.85 s, one "
+                           "sample each (profiles/seed_batch_critic_ks/step_times.txt).")
 
 
 # (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_klpen/step_times.txt)
@@ -133,6 +145,13 @@ def single_agent_args(argv=None):
                              "critic fits then share one persistent launch per iteration (spo_critic_fit_iter_split_multi: up to 32 "
                              "seeds, four workgroups each, run r on XCD r mod 8), each seed the run its `--seed` would be.  "
                              + CRITIC_SPLIT_BATCH_FIGURES + "  Default False: such tasks are refused with several seeds")
+    parser.add_argument("--batch-critic-fit-feature-split", type=_bool, default=False,
+                        help="with --batch-critic-fit True: also take tasks with 129-512 observations and up to 32 actions (hidden "
+                             "[64, 64]: HumanoidVelocity's 376 / 17), whose critic fit runs on the feature-split kernel -- the seeds' "
+                             "critic fits then share one launch per iteration (spo_critic_fit_iter_ks_multi: up to 16 seeds up to 384 "
+                             "observations, 8 up to 512; 2 x ceil(obs_dim / 64) workgroups each, run r on XCD r mod 8), each seed the "
+                             "run its `--seed` would be.  " + CRITIC_KS_BATCH_FIGURES
+                             + "  Default False: such tasks are refused with several seeds")
     parser.add_argument("--batch-update", type=_bool, default=False,
                         help="focops and cup with --seeds: run the seeds in one process, their minibatch steps sharing one persistent "
                              "launch per pass (spo_update_iter_ex_multi: up to 32 seeds, one workgroup per network each, run r on XCD "
