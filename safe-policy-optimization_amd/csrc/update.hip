@@ -24,6 +24,7 @@
 #include "adam.h"
 #include "../../include/safepo_hip.h"
 #include "update_rs.h"
+#include "replica_batch.h"
 
 namespace {
 using namespace spo;
@@ -3024,8 +3025,7 @@ int h_scratch_for(hipStream_t st, float** backup, unsigned long long** slots, in
   if (g_hs_n == H_SCRATCH_MAX)
     return spo::fail(-1, "update kernel: more than %d (device, stream) pairs hold update scratch in this process; call "
                          "spo_update_scratch_release(stream) for streams that are gone", H_SCRATCH_MAX);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+  if (spo::stream_is_capturing(st))
     return spo::fail(-1, "update kernel: first launch on a stream under capture (the scratch block is allocated on first use: "
                          "launch once outside the capture)");
   void* p = nullptr;
@@ -3058,72 +3058,17 @@ int split_local_release(int dev, void* stream_or_null, int all) {
 // (never under capture) and kept: [run] clip-norm granules [2][4] on a 128-byte line of their own -- contiguous, so ONE
 // hipMemsetAsync zeroes the first n_replicas of them per launch (the tags restart at 1) -- then the argument table.  The table
 // leaves the host from pinned memory: EXM_TAB_RING tables per entry, used in turn, each with an event recorded behind its copy --
-// a table is rewritten only once the copy that read it last has completed.
+// a table is rewritten only once the copy that read it last has completed (the pool's ring, replica_batch.h).
 constexpr size_t EXM_G_STRIDE = 128;
 constexpr size_t EXM_T_OFF = (size_t)SPO_UPDATE_EX_MAX_REPLICAS * EXM_G_STRIDE;
 constexpr size_t EXM_BYTES = EXM_T_OFF + (size_t)SPO_UPDATE_EX_MAX_REPLICAS * sizeof(UpdMultiEntry);
-constexpr int EXM_TAB_RING = 4, EXM_SCRATCH_MAX = 16;
-struct ExmEntry { int dev; void* stream; char* base; UpdMultiEntry* tab_host; hipEvent_t ev[EXM_TAB_RING]; unsigned calls; };
-ExmEntry g_exm[EXM_SCRATCH_MAX] = {};
-int g_exm_n = 0;
+constexpr int EXM_SCRATCH_MAX = 16;
 std::mutex g_exm_mu;
+spo::ReplicaPool<UpdMultiEntry, SPO_UPDATE_EX_MAX_REPLICAS, EXM_SCRATCH_MAX> g_exm{
+    EXM_BYTES, false, "update_iter_ex_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                      "spo_update_scratch_release(stream) for streams that are gone",
+    "seed-batched update scratch", "replica table", nullptr};
 std::atomic<unsigned long long> g_exm_counters[2];       // {launches enqueued, runs that took part}
-
-void exm_free(ExmEntry& e) {
-  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched update scratch)");
-  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(replica table)");
-  for (int i = 0; i < EXM_TAB_RING; ++i)
-    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(replica table)");
-  e = ExmEntry{};
-}
-
-// The caller holds g_exm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot).
-int exm_scratch(hipStream_t st, char** base, UpdMultiEntry** tab_host, hipEvent_t* ev) {
-  const int dev = current_device_slot();
-  ExmEntry* e = nullptr;
-  for (int i = 0; i < g_exm_n; ++i)
-    if (g_exm[i].dev == dev && g_exm[i].stream == (void*)st) e = &g_exm[i];
-  if (!e) {
-    if (g_exm_n == EXM_SCRATCH_MAX)
-      return spo::fail(-1, "update_iter_ex_multi: more than %d (device, stream) pairs hold scratch in this process; call "
-                           "spo_update_scratch_release(stream) for streams that are gone", EXM_SCRATCH_MAX);
-    ExmEntry n{};
-    n.dev = dev; n.stream = (void*)st;
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, EXM_BYTES), "hipMalloc(seed-batched update scratch)")) return rc;
-    n.base = static_cast<char*>(p);
-    void* h = nullptr;
-    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)EXM_TAB_RING * SPO_UPDATE_EX_MAX_REPLICAS * sizeof(UpdMultiEntry),
-                                              hipHostMallocDefault), "hipHostMalloc(replica table)")) { exm_free(n); return rc; }
-    n.tab_host = static_cast<UpdMultiEntry*>(h);
-    for (int i = 0; i < EXM_TAB_RING; ++i)
-      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(replica table)")) {
-        exm_free(n); return rc;
-      }
-    g_exm[g_exm_n] = n;
-    e = &g_exm[g_exm_n++];
-  }
-  *base = e->base;
-  const unsigned slot = e->calls++ % EXM_TAB_RING;
-  *tab_host = e->tab_host + (size_t)slot * SPO_UPDATE_EX_MAX_REPLICAS;
-  *ev = e->ev[slot];
-  // (an event that was never recorded is complete)
-  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
-}
-
-int exm_release(int dev, void* stream_or_null, int all) {
-  std::lock_guard<std::mutex> lk(g_exm_mu);
-  int freed = 0;
-  for (int i = 0; i < g_exm_n;) {
-    if (g_exm[i].dev == dev && (all || g_exm[i].stream == stream_or_null)) {
-      exm_free(g_exm[i]);
-      g_exm[i] = g_exm[--g_exm_n];
-      g_exm[g_exm_n] = ExmEntry{};
-      ++freed;
-    } else ++i;
-  }
-  return freed;
-}
 
 // Per-run state of the seed-batched split critic fit (spo_critic_fit_iter_split_multi), one block per (device, stream) beside
 // g_split_local, allocated on first use (never under capture), grown to the largest S seen and kept:
@@ -3142,103 +3087,63 @@ constexpr size_t SPLITM_RUN_BYTES = 2 * SPLITM_REGION_BYTES + 2 * SPLITM_G_BYTES
 constexpr size_t SPLITM_CENSUS_BYTES = 256;
 static_assert(SPLITM_REGION_BYTES <= XR_REGION_BYTES && SPLITM_REGION_BYTES % 4096 == 0, "a prefix of an exchange region");
 static_assert((SPLITM_COUNT_WORD + 1) * 8 <= (int)SPLITM_CENSUS_BYTES && SPLITM_COUNT_WORD >= 16 + 2 * 2, "census words 0-3, 16-19 + counter");
-constexpr int SPLITM_TAB_RING = 4, SPLITM_SCRATCH_MAX = 8;
-struct SplitMultiState {
-  int dev; void* stream; char* base; int cap;
+constexpr int SPLITM_SCRATCH_MAX = 8;
+// On the pool's ring (replica_batch.h) with a device block of its own making: the pool allocates none (bytes 0), splitm_grow below
+// sizes it for `cap` runs; every run keeps a census tag of its own.
+struct SplitMultiExtra {
+  int cap = 0;
   unsigned tag[SPO_CRITIC_SPLIT_MAX_REPLICAS];
-  UpdSplitMultiEntry* tab_host; hipEvent_t ev[SPLITM_TAB_RING]; unsigned calls;
+  SplitMultiExtra() { for (unsigned& t : tag) t = 1u; }
   size_t census_off() const { return (size_t)cap * SPLITM_RUN_BYTES; }
   size_t table_off() const { return census_off() + (size_t)cap * SPLITM_CENSUS_BYTES; }
   size_t bytes() const { return table_off() + (size_t)cap * sizeof(UpdSplitMultiEntry); }
 };
-SplitMultiState g_splitm[SPLITM_SCRATCH_MAX] = {};
-int g_splitm_n = 0;
+using SplitMultiPool = spo::ReplicaPool<UpdSplitMultiEntry, SPO_CRITIC_SPLIT_MAX_REPLICAS, SPLITM_SCRATCH_MAX, SplitMultiExtra>;
+using SplitMultiState = SplitMultiPool::Block;
 std::mutex g_splitm_mu;
 std::atomic<unsigned long long> g_splitm_counters[3];    // {launches enqueued, runs that took part, shared-L2 runs of blocks that are gone}
 
 // sum of the runs' shared-L2 counters of one block (synchronises the device); reset: zeroes them
 int splitm_read_l2(SplitMultiState& e, unsigned long long* sum, bool reset) {
   *sum = 0;
-  if (!e.base || e.cap == 0) return 0;
+  if (!e.base || e.x.cap == 0) return 0;
   if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(split counters)")) return rc;
-  char* const w = e.base + e.census_off() + (size_t)SPLITM_COUNT_WORD * 8;
+  char* const w = e.base + e.x.census_off() + (size_t)SPLITM_COUNT_WORD * 8;
   unsigned long long host[SPO_CRITIC_SPLIT_MAX_REPLICAS];
-  if (int rc = spo::hip_check(hipMemcpy2D(host, 8, w, SPLITM_CENSUS_BYTES, 8, (size_t)e.cap, hipMemcpyDeviceToHost),
+  if (int rc = spo::hip_check(hipMemcpy2D(host, 8, w, SPLITM_CENSUS_BYTES, 8, (size_t)e.x.cap, hipMemcpyDeviceToHost),
                               "hipMemcpy2D(split counters)")) return rc;
-  for (int r = 0; r < e.cap; ++r) *sum += host[r];
-  if (reset) return spo::hip_check(hipMemset2D(w, SPLITM_CENSUS_BYTES, 0, 8, (size_t)e.cap), "hipMemset2D(split counters)");
+  for (int r = 0; r < e.x.cap; ++r) *sum += host[r];
+  if (reset) return spo::hip_check(hipMemset2D(w, SPLITM_CENSUS_BYTES, 0, 8, (size_t)e.x.cap), "hipMemset2D(split counters)");
   return 0;
 }
 
-void splitm_free(SplitMultiState& e) {
-  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched split scratch)");
-  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(split replica table)");
-  for (int i = 0; i < SPLITM_TAB_RING; ++i)
-    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(split replica table)");
-  e = SplitMultiState{};
+// a block that is about to be freed: its runs' shared-L2 counts move to the host
+void splitm_before_free(SplitMultiState& e) {
+  unsigned long long carry = 0;
+  if (splitm_read_l2(e, &carry, false) == 0) g_splitm_counters[2] += carry;
 }
 
-// The caller holds g_splitm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot) and
-// has checked that the stream is not under capture.
-int splitm_scratch(hipStream_t st, int n_replicas, SplitMultiState** out, UpdSplitMultiEntry** tab_host, hipEvent_t* ev) {
-  const int dev = current_device_slot();
-  SplitMultiState* e = nullptr;
-  for (int i = 0; i < g_splitm_n; ++i)
-    if (g_splitm[i].dev == dev && g_splitm[i].stream == (void*)st) e = &g_splitm[i];
-  if (!e) {
-    if (g_splitm_n == SPLITM_SCRATCH_MAX)
-      return spo::fail(-1, "critic_fit_iter_split_multi: more than %d (device, stream) pairs hold scratch in this process; call "
-                           "spo_update_scratch_release(stream) for streams that are gone", SPLITM_SCRATCH_MAX);
-    SplitMultiState n{};
-    n.dev = dev; n.stream = (void*)st;
-    void* h = nullptr;
-    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)SPLITM_TAB_RING * SPO_CRITIC_SPLIT_MAX_REPLICAS * sizeof(UpdSplitMultiEntry),
-                                              hipHostMallocDefault), "hipHostMalloc(split replica table)")) return rc;
-    n.tab_host = static_cast<UpdSplitMultiEntry*>(h);
-    for (int i = 0; i < SPLITM_TAB_RING; ++i)
-      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(split replica table)")) {
-        splitm_free(n); return rc;
-      }
-    for (unsigned& t : n.tag) t = 1u;
-    g_splitm[g_splitm_n] = n;
-    e = &g_splitm[g_splitm_n++];
-  }
-  if (n_replicas > e->cap) {
-    // grow: the old block may still be in use by launches on the stream -- hipFree waits for the device; the runs' shared-L2
-    // counts move to the host, their census tags carry on (the new words are zero, a tag is never 0)
-    unsigned long long carry = 0;
-    if (int rc = splitm_read_l2(*e, &carry, false)) return rc;
-    g_splitm_counters[2] += carry;
-    if (e->base) { if (int rc = spo::hip_check(hipFree(e->base), "hipFree(seed-batched split scratch)")) return rc; }
-    e->base = nullptr; e->cap = 0;
-    SplitMultiState sized = *e;
-    sized.cap = n_replicas;
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, sized.bytes()), "hipMalloc(seed-batched split scratch)")) return rc;
-    if (int rc = spo::hip_check(hipMemset(p, 0, sized.bytes()), "hipMemset(seed-batched split scratch)")) { (void)hipFree(p); return rc; }
-    e->base = static_cast<char*>(p); e->cap = n_replicas;
-  }
-  *out = e;
-  const unsigned slot = e->calls++ % SPLITM_TAB_RING;
-  *tab_host = e->tab_host + (size_t)slot * SPO_CRITIC_SPLIT_MAX_REPLICAS;
-  *ev = e->ev[slot];
-  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(split replica table)");    // (never recorded: complete)
-}
+SplitMultiPool g_splitm{0, false, "critic_fit_iter_split_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                                  "spo_update_scratch_release(stream) for streams that are gone",
+                        "seed-batched split scratch", "split replica table", splitm_before_free};
 
-int splitm_release(int dev, void* stream_or_null, int all) {
-  std::lock_guard<std::mutex> lk(g_splitm_mu);
-  int freed = 0;
-  for (int i = 0; i < g_splitm_n;) {
-    if (g_splitm[i].dev == dev && (all || g_splitm[i].stream == stream_or_null)) {
-      unsigned long long carry = 0;
-      if (splitm_read_l2(g_splitm[i], &carry, false) == 0) g_splitm_counters[2] += carry;
-      splitm_free(g_splitm[i]);
-      g_splitm[i] = g_splitm[--g_splitm_n];
-      g_splitm[g_splitm_n] = SplitMultiState{};
-      ++freed;
-    } else ++i;
-  }
-  return freed;
+// Grows the block to n_replicas runs (the caller holds g_splitm_mu; the stream is not under capture).  The old block may still be
+// in use by launches on the stream -- hipFree waits for the device; the runs' shared-L2 counts move to the host, their census tags
+// carry on (the new words are zero, a tag is never 0).
+int splitm_grow(SplitMultiState& e, int n_replicas) {
+  if (n_replicas <= e.x.cap) return 0;
+  unsigned long long carry = 0;
+  if (int rc = splitm_read_l2(e, &carry, false)) return rc;
+  g_splitm_counters[2] += carry;
+  if (e.base) { if (int rc = spo::hip_check(hipFree(e.base), "hipFree(seed-batched split scratch)")) return rc; }
+  e.base = nullptr; e.x.cap = 0;
+  SplitMultiExtra sized = e.x;
+  sized.cap = n_replicas;
+  void* p = nullptr;
+  if (int rc = spo::hip_check(hipMalloc(&p, sized.bytes()), "hipMalloc(seed-batched split scratch)")) return rc;
+  if (int rc = spo::hip_check(hipMemset(p, 0, sized.bytes()), "hipMemset(seed-batched split scratch)")) { (void)hipFree(p); return rc; }
+  e.base = static_cast<char*>(p); e.x.cap = n_replicas;
+  return 0;
 }
 
 }  // namespace
@@ -3261,8 +3166,8 @@ extern "C" int spo_update_scratch_release(void* stream_or_null, int all) {
   freed += spo::ks_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_multi_scratch_release(dev, stream_or_null, all);
-  freed += exm_release(dev, stream_or_null, all);
-  freed += splitm_release(dev, stream_or_null, all);
+  { std::lock_guard<std::mutex> lk2(g_exm_mu); freed += g_exm.release(dev, stream_or_null, all); }
+  { std::lock_guard<std::mutex> lk2(g_splitm_mu); freed += g_splitm.release(dev, stream_or_null, all); }
   return freed;
 }
 namespace {
@@ -3356,18 +3261,9 @@ int launch_update(const UpdArgs& a, int blocks, hipStream_t st) {
 
 template <int K, int AMODE>
 int launch_update_multi_k(const UpdMultiEntry* table_dev, int n_replicas, int wgs, hipStream_t st) {
-  const size_t sh = UpdLds<K>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_multi_kernel<K, AMODE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_multi)");
-    attr_done[dslot] = true;
-  }
-  hipLaunchKernelGGL((ppo_update_multi_kernel<K, AMODE>), dim3(rs_multi_grid(n_replicas, wgs)), dim3(256), sh, st, table_dev, n_replicas,
-                     wgs);
-  return 0;
+  return launch_dyn_lds(&ppo_update_multi_kernel<K, AMODE>, attr_done, "hipFuncSetAttribute(update_multi)",
+                        dim3(rs_multi_grid(n_replicas, wgs)), dim3(256), UpdLds<K>::SIZE * sizeof(float), st, table_dev, n_replicas, wgs);
 }
 
 template <int AMODE>
@@ -3486,17 +3382,10 @@ extern "C" int spo_update_iter_ex(float* theta, float* adam_m, float* adam_v, in
   hipStream_t st = (hipStream_t)stream;
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
   UpdArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.M = M; a.cfg = *cfg_host; a.losses = losses_out;
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_critics_host, adam_step_actor_host, obs, act, logp_old, target_r, target_c, adv,
+                   perm, M, *cfg_host, actor_only ? 1 : 3, actor_only ? 2 : 0, nullptr, losses_out, sync_ws, old_mean, old_std, kl_bound,
+                   pg_coef);
   a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_critics_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_critics_host);
-  a.pow_b1_actor = pow((double)cfg_host->beta1, (double)adam_step_actor_host);
-  a.pow_b2_actor = pow((double)cfg_host->beta2, (double)adam_step_actor_host);
-  a.first_net = actor_only ? 2 : 0; a.n_nets = actor_only ? 1 : 3; a.stale_sq = 0.f; a.stale_io = nullptr;
-  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef;
   if (actor_loss == SPO_ACTOR_LOSS_KL_PENALTY) {
     if (int rc = launch_update<true, 1>(a, a.n_nets, st)) return rc;
   } else {
@@ -3521,13 +3410,7 @@ extern "C" int spo_update_ex_multi_matches_single(int obs_dim, int act_dim, int 
 }
 
 extern "C" int spo_update_ex_multi_block_map(int block, int n_replicas, int actor_only, int* replica, int* wg) {
-  const int wgs = actor_only ? 1 : 3;
-  if (n_replicas < 1 || n_replicas > SPO_UPDATE_EX_MAX_REPLICAS || block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
-  int r = 0, w = 0;
-  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
-  if (work && replica) *replica = r;
-  if (work && wg) *wg = w;
-  return work ? 1 : 0;
+  return spo::block_map_query(block, n_replicas, SPO_UPDATE_EX_MAX_REPLICAS, actor_only ? 1 : 3, replica, wg);
 }
 
 extern "C" int spo_debug_update_ex_multi_counters(unsigned long long* out2_host, int reset) {
@@ -3539,9 +3422,8 @@ extern "C" int spo_debug_update_ex_multi_counters(unsigned long long* out2_host,
 extern "C" int spo_update_iter_ex_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss,
                                         int actor_only, void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "update_iter_ex_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_UPDATE_EX_MAX_REPLICAS, "update_iter_ex_multi: %d replicas outside [1, %d]",
-              n_replicas, SPO_UPDATE_EX_MAX_REPLICAS);
+  constexpr const char* NAME = "update_iter_ex_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_UPDATE_EX_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || actor_loss == SPO_ACTOR_LOSS_KL_PENALTY,
               "update_iter_ex_multi: unknown actor_loss %d", actor_loss);
   SPO_REQUIRE(M > 0, "update_iter_ex_multi: bad sizes");
@@ -3553,57 +3435,39 @@ extern "C" int spo_update_iter_ex_multi(const spo_update_ex_replica* reps_host, 
   int n_active = 0;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_update_ex_replica& p = reps_host[r];
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "update_iter_ex_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
-                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
     SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.act && p.logp_old && p.adv && p.sync_ws &&
                     ((p.perm && p.losses_out) || !p.active), "update_iter_ex_multi: null pointer in replica %d", r);
     SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || (p.old_mean && p.old_std),
                 "update_iter_ex_multi: old distribution is NULL in replica %d", r);
     SPO_REQUIRE(actor_only || (p.target_r && p.target_c), "update_iter_ex_multi: critic targets are NULL in replica %d", r);
     SPO_REQUIRE(p.adam_step_critics >= 0 && p.adam_step_actor >= 0, "update_iter_ex_multi: replica %d: negative adam_step", r);
-    for (int q = 0; q < r; ++q)
-      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
-                  "update_iter_ex_multi: replicas %d and %d share theta or sync_ws", q, r);
+    if (int rc = spo::distinct(NAME, reps_host, r)) return rc;
     n_active += p.active ? 1 : 0;
   }
   if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
   hipStream_t st = (hipStream_t)stream;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return spo::fail(-1, "update_iter_ex_multi: the stream is under capture (the argument table is copied from host memory at "
-                           "every call: not a graph node)");
-  }
+  if (spo::stream_is_capturing(st))
+    return spo::fail(-1, "update_iter_ex_multi: the stream is under capture (the argument table is copied from host memory at "
+                         "every call: not a graph node)");
   const int wgs = actor_only ? 1 : 3;
   std::lock_guard<std::mutex> lk(g_exm_mu);                                // (until the table's copy and its event are enqueued)
-  char* base = nullptr;
-  UpdMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  if (int rc = exm_scratch(st, &base, &tab, &tab_ev)) return rc;
+  decltype(g_exm)::Slot sl{};
+  if (int rc = g_exm.acquire(st, 0, &sl)) return rc;                       // (no tags to hand out: the granules restart at 1)
   for (int r = 0; r < n_replicas; ++r) {
     const spo_update_ex_replica& p = reps_host[r];
-    UpdArgs a{};                                                           // (as spo_update_iter_ex fills it)
-    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
-    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
-    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
-    a.slots = reinterpret_cast<unsigned long long*>(base + (size_t)r * EXM_G_STRIDE);      // the run's own granules
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step_critics);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step_critics);
-    a.pow_b1_actor = pow((double)p.cfg.beta1, (double)p.adam_step_actor);
-    a.pow_b2_actor = pow((double)p.cfg.beta2, (double)p.adam_step_actor);
-    a.first_net = actor_only ? 2 : 0; a.n_nets = wgs; a.stale_sq = 0.f; a.stale_io = nullptr;
-    a.old_mean = p.old_mean; a.old_std = p.old_std; a.kl_bound = p.kl_bound; a.pg_coef = p.pg_coef;
-    tab[r].a = a;
-    tab[r].active = p.active ? 1 : 0;
+    UpdArgs a{};
+    spo::fill_run_ex(a, p.theta, p.adam_m, p.adam_v, p.adam_step_critics, p.adam_step_actor, p.obs, p.act, p.logp_old, p.target_r,
+                     p.target_c, p.adv, p.perm, M, p.cfg, wgs, actor_only ? 2 : 0, nullptr, p.losses_out, p.sync_ws, p.old_mean, p.old_std,
+                     p.kl_bound, p.pg_coef);
+    a.slots = reinterpret_cast<unsigned long long*>(sl.base + (size_t)r * EXM_G_STRIDE);   // the run's own granules
+    sl.tab_host[r].a = a;
+    sl.tab_host[r].active = p.active ? 1 : 0;
   }
-  UpdMultiEntry* const table_dev = reinterpret_cast<UpdMultiEntry*>(base + EXM_T_OFF);
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(UpdMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  UpdMultiEntry* const table_dev = reinterpret_cast<UpdMultiEntry*>(sl.base + EXM_T_OFF);
+  if (int rc = spo::upload_table(table_dev, sl.tab_host, n_replicas, sl.ev, st, "replica table")) return rc;
   // the tags restart at 1 with every launch: every run's granules start as zero
-  if (int rc = spo::hip_check(hipMemsetAsync(base, 0, (size_t)n_replicas * EXM_G_STRIDE, st), "hipMemsetAsync(granules)")) return rc;
+  if (int rc = spo::hip_check(hipMemsetAsync(sl.base, 0, (size_t)n_replicas * EXM_G_STRIDE, st), "hipMemsetAsync(granules)")) return rc;
   int rc = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY ? launch_update_multi<1>(c0.obs_dim, table_dev, n_replicas, wgs, st)
                                                    : launch_update_multi<0>(c0.obs_dim, table_dev, n_replicas, wgs, st);
   if (rc) return rc;
@@ -3880,8 +3744,7 @@ static int split_local_for(hipStream_t st, UpdArgs& a, UpdArgs& b) {
     if (g_split_local[i].dev == dev && g_split_local[i].stream == (void*)st) sl = &g_split_local[i];
   if (!sl) {
     if (g_split_local_n == SPLIT_LOCAL_MAX) return 0;               // (table full: the uncached regions, as before round 5)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;        // (allocation + memset would invalidate a capture)
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (spo::stream_is_capturing(st))                               // (allocation + memset would invalidate a capture)
       return spo::fail(-1, "split critic fit: first launch on a stream under capture (the cached exchange regions are allocated on "
                            "first use: launch once outside the capture)");
     void* p = nullptr;
@@ -3918,15 +3781,9 @@ extern "C" int spo_critic_fit_iter_split(float* theta0, float* adam_m0, float* a
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws1, 0, 64, st), "hipMemsetAsync(sync_ws1)")) return rc;
   UpdArgs a{};
   if (int rc = fill_xr(a, 0, 2, regions2, step0)) return rc;
-  a.theta = theta0; a.adam_m = adam_m0; a.adam_v = adam_v0;
-  a.obs = obs; a.tgt_r = target_r; a.tgt_c = target_c; a.perm = perm0; a.M = M_half; a.cfg = *cfg_host;
-  a.losses = losses0;
+  spo::fill_run_ex(a, theta0, adam_m0, adam_v0, adam_step_host, adam_step_host, obs, nullptr, nullptr, target_r, target_c, nullptr, perm0,
+                   M_half, *cfg_host, 2, 0, stale_sq_io0, losses0, sync_ws0);
   a.slots = reinterpret_cast<unsigned long long*>(sync_ws0);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws0) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-  a.first_net = 0; a.n_nets = 2; a.stale_sq = 0.f; a.stale_io = stale_sq_io0;
   UpdArgs b = a;                       // rank 1: same data and configuration, its own replica / rows / outputs
   b.xr_rank = 1;
   b.theta = theta1; b.adam_m = adam_m1; b.adam_v = adam_v1; b.perm = perm1; b.losses = losses1;
@@ -3991,21 +3848,20 @@ extern "C" int spo_critic_fit_split_multi_supported(int obs_dim, int batch, int 
 }
 
 extern "C" int spo_critic_fit_split_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
-  if (!replica || !wg || n_replicas < 1 || n_replicas > SPO_CRITIC_SPLIT_MAX_REPLICAS || block < 0 ||
-      block >= spo::rs_multi_grid(n_replicas, SPLITM_WGS)) return 0;
-  return spo::rs_multi_map(block, n_replicas, SPLITM_WGS, replica, wg) ? 1 : 0;
+  if (!replica || !wg) return 0;
+  return spo::block_map_query(block, n_replicas, SPO_CRITIC_SPLIT_MAX_REPLICAS, SPLITM_WGS, replica, wg);
 }
 
 extern "C" int spo_debug_critic_fit_split_multi_counters(unsigned long long* out3_host, int reset) {
   SPO_REQUIRE(out3_host, "critic_fit_split_multi_counters: null pointer");
   for (int i = 0; i < 3; ++i) out3_host[i] = reset ? g_splitm_counters[i].exchange(0ull) : g_splitm_counters[i].load();
   std::lock_guard<std::mutex> lk(g_splitm_mu);
-  if (g_splitm_n == 0) return 0;                                           // (no block: no device access)
+  if (g_splitm.n == 0) return 0;                                           // (no block: no device access)
   const int dev = current_device_slot();
-  for (int i = 0; i < g_splitm_n; ++i) {
-    if (g_splitm[i].dev != dev) continue;
+  for (int i = 0; i < g_splitm.n; ++i) {
+    if (g_splitm.e[i].dev != dev) continue;
     unsigned long long l2 = 0;
-    if (int rc = splitm_read_l2(g_splitm[i], &l2, reset != 0)) return rc;
+    if (int rc = splitm_read_l2(g_splitm.e[i], &l2, reset != 0)) return rc;
     out3_host[2] += l2;
   }
   return 0;
@@ -4014,18 +3870,13 @@ extern "C" int spo_debug_critic_fit_split_multi_counters(unsigned long long* out
 extern "C" int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replica* reps_host, int n_replicas, int64_t M_half,
                                                void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "critic_fit_iter_split_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_CRITIC_SPLIT_MAX_REPLICAS, "critic_fit_iter_split_multi: %d replicas outside [1, %d]",
-              n_replicas, SPO_CRITIC_SPLIT_MAX_REPLICAS);
+  constexpr const char* NAME = "critic_fit_iter_split_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_CRITIC_SPLIT_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(M_half > 0, "critic_fit_iter_split_multi: bad sizes");
   const spo_ppo_cfg& c0 = reps_host[0].cfg;
   int n_active = 0;
-  for (int r = 0; r < n_replicas; ++r) {
-    const spo_critic_fit_split_replica& p = reps_host[r];
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "critic_fit_iter_split_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
-                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
-  }
+  for (int r = 0; r < n_replicas; ++r)
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
   if (int rc = check_cfg(&c0)) return rc;
   SPO_REQUIRE(spo_critic_fit_split_multi_supported(c0.obs_dim, c0.batch, n_replicas),
               "critic_fit_iter_split_multi: no seed-batched split form for obs_dim %d, batch %d per half "
@@ -4058,40 +3909,32 @@ extern "C" int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replic
   }
   if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
   hipStream_t st = (hipStream_t)stream;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return spo::fail(-1, "critic_fit_iter_split_multi: the stream is under capture (the argument table is copied from host memory "
-                           "at every call and the scratch block may grow: not a graph node)");
-  }
+  if (spo::stream_is_capturing(st))
+    return spo::fail(-1, "critic_fit_iter_split_multi: the stream is under capture (the argument table is copied from host memory "
+                         "at every call and the scratch block may grow: not a graph node)");
   static const bool l2_off = [] { const char* e = getenv("SPO_CPO_SPLIT_L2"); return e && !strcmp(e, "0"); }();
   std::lock_guard<std::mutex> lk(g_splitm_mu);                             // (until the table's copy and its event are enqueued)
-  SplitMultiState* sm = nullptr;
-  UpdSplitMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  if (int rc = splitm_scratch(st, n_replicas, &sm, &tab, &tab_ev)) return rc;
-  char* const base = sm->base;
+  SplitMultiPool::Slot sl{};
+  if (int rc = g_splitm.acquire(st, 0, &sl)) return rc;                    // (the census tags are per run: SplitMultiExtra)
+  if (int rc = splitm_grow(*sl.block, n_replicas)) return rc;
+  SplitMultiExtra& sm = sl.block->x;
+  char* const base = sl.block->base;
+  UpdSplitMultiEntry* const tab = sl.tab_host;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_critic_fit_split_replica& p = reps_host[r];
     tab[r] = UpdSplitMultiEntry{};
     if (!p.active) continue;                                               // (active == 0: the kernel reads nothing else of the entry)
     char* const run = base + (size_t)r * SPLITM_RUN_BYTES;
-    UpdArgs a{};                                                           // (as spo_critic_fit_iter_split fills the pair)
+    UpdArgs a{};
     if (int rc = fill_xr(a, 0, 2, p.regions2, p.step0)) return rc;
-    a.theta = p.theta0; a.adam_m = p.adam_m0; a.adam_v = p.adam_v0;
-    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.perm = p.perm0; a.M = M_half; a.cfg = p.cfg;
-    a.losses = p.losses0;
+    spo::fill_run_ex(a, p.theta0, p.adam_m0, p.adam_v0, p.adam_step, p.adam_step, p.obs, nullptr, nullptr, p.target_r, p.target_c, nullptr,
+                     p.perm0, M_half, p.cfg, 2, 0, p.stale_sq_io0, p.losses0, p.sync_ws0);
     a.slots = reinterpret_cast<unsigned long long*>(run + 2 * SPLITM_REGION_BYTES);        // the run's own granules
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws0) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
-    a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-    a.first_net = 0; a.n_nets = 2; a.stale_sq = 0.f; a.stale_io = p.stale_sq_io0;
     if (!l2_off) {                                                         // (SPO_CPO_SPLIT_L2=0: every run on the uncached body)
       a.xr_region[2] = run; a.xr_region[3] = run + SPLITM_REGION_BYTES;
-      a.xr_census = reinterpret_cast<unsigned long long*>(base + sm->census_off() + (size_t)r * SPLITM_CENSUS_BYTES);
-      a.xr_census_tag = sm->tag[r];
-      sm->tag[r] = sm->tag[r] + 1u ? sm->tag[r] + 1u : 1u;                 // (never 0: fresh census words are zero)
+      a.xr_census = reinterpret_cast<unsigned long long*>(base + sm.census_off() + (size_t)r * SPLITM_CENSUS_BYTES);
+      a.xr_census_tag = sm.tag[r];
+      sm.tag[r] = sm.tag[r] + 1u ? sm.tag[r] + 1u : 1u;                    // (never 0: fresh census words are zero)
     }
     UpdArgs b = a;                     // second replica: same data and configuration, its own parameters / rows / outputs
     b.xr_rank = 1;
@@ -4101,26 +3944,15 @@ extern "C" int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replic
     b.stale_io = p.stale_sq_io1;
     tab[r].a0 = a; tab[r].a1 = b; tab[r].active = 1;
   }
-  UpdSplitMultiEntry* const table_dev = reinterpret_cast<UpdSplitMultiEntry*>(base + sm->table_off());
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(UpdSplitMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(split replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(split replica table)")) return rc;
+  UpdSplitMultiEntry* const table_dev = reinterpret_cast<UpdSplitMultiEntry*>(base + sm.table_off());
+  if (int rc = spo::upload_table(table_dev, tab, n_replicas, sl.ev, st, "split replica table")) return rc;
   // one clear for the S runs of the launch: cached regions (tags restart with every engine) and granules (tags restart at 1)
   if (int rc = spo::hip_check(hipMemsetAsync(base, 0, (size_t)n_replicas * SPLITM_RUN_BYTES, st), "hipMemsetAsync(split exchange)"))
     return rc;
-  {
-    const size_t sh = UpdLds<128>::SIZE * sizeof(float);
-    static bool attr_done[SPO_MAX_DEVICES] = {};
-    const int dslot = current_device_slot();
-    if (!attr_done[dslot]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_split_multi_kernel<128>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update split multi)");
-      attr_done[dslot] = true;
-    }
-    hipLaunchKernelGGL((ppo_update_split_multi_kernel<128>), dim3(spo::rs_multi_grid(n_replicas, SPLITM_WGS)), dim3(256), sh, st,
-                       table_dev, n_replicas);
-  }
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  if (int rc = spo::launch_dyn_lds(&ppo_update_split_multi_kernel<128>, attr_done, "hipFuncSetAttribute(update split multi)",
+                                   dim3(spo::rs_multi_grid(n_replicas, SPLITM_WGS)), dim3(256), UpdLds<128>::SIZE * sizeof(float), st,
+                                   table_dev, n_replicas)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_split_multi");
   g_splitm_counters[0] += 1ull;
   g_splitm_counters[1] += (unsigned long long)n_active;

@@ -35,6 +35,7 @@
 #include "mlp_mfma.h"
 #include "adam.h"
 #include "update_rs.h"
+#include "replica_batch.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -1095,8 +1096,7 @@ int ks_scratch(hipStream_t st, KsScratch* out, unsigned* tag_base, unsigned nste
     if (g_ks_n == KS_SCRATCH_MAX)
       return spo::fail(-1, "feature-split update kernel: more than %d (device, stream) pairs hold exchange scratch in this process; "
                            "call spo_update_scratch_release(stream) for streams that are gone", KS_SCRATCH_MAX);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (spo::stream_is_capturing(st))
       return spo::fail(-1, "feature-split update kernel: first launch on a stream under capture (the scratch block is allocated on "
                            "first use: launch once outside the capture)");
     void* p = nullptr;
@@ -1127,10 +1127,8 @@ static_assert(KS_G_BYTES + 2 * sizeof(unsigned) <= KSM_G_PAGE && KS_Z_BYTES % 40
 constexpr size_t KSM_STRIDE = KS_Z_BYTES + KSM_G_PAGE;
 constexpr size_t KSM_T_OFF = (size_t)SPO_KS_MAX_REPLICAS * KSM_STRIDE;
 constexpr size_t KSM_BYTES = KSM_T_OFF + (((size_t)SPO_KS_MAX_REPLICAS * sizeof(KsMultiEntry) + 4095) & ~(size_t)4095);
-constexpr int KSM_TAB_RING = 4, KSM_SCRATCH_MAX = 16;
-struct KsmEntry { int dev; void* stream; char* base; KsMultiEntry* tab_host; hipEvent_t ev[KSM_TAB_RING]; unsigned calls; unsigned tag; };
-KsmEntry g_ksm[KSM_SCRATCH_MAX] = {};
-int g_ksm_n = 0;
+constexpr int KSM_SCRATCH_MAX = 16;
+using KsmPool = spo::ReplicaPool<KsMultiEntry, SPO_KS_MAX_REPLICAS, KSM_SCRATCH_MAX>;
 std::mutex g_ksm_mu;
 std::atomic<unsigned long long> g_ksm_counters[2];       // {launches enqueued, runs that took part}
 unsigned long long g_ksm_wt_released = 0;                // write-through counts of blocks that have been released (under g_ksm_mu)
@@ -1144,7 +1142,7 @@ inline unsigned* ksm_wt_word(char* base, int r, int which = 0) {
 }
 
 // sums (and optionally clears) the write-through counts of one block; the caller holds g_ksm_mu and has synchronised the device
-int ksm_harvest(KsmEntry& e, unsigned long long* sum, bool clear, int which = 0) {
+int ksm_harvest(KsmPool::Block& e, unsigned long long* sum, bool clear, int which = 0) {
   for (int r = 0; r < SPO_KS_MAX_REPLICAS; ++r) {
     unsigned v = 0;
     if (int rc = spo::hip_check(hipMemcpy(&v, ksm_wt_word(e.base, r, which), sizeof(v), hipMemcpyDeviceToHost), "hipMemcpy(ks multi count)")) return rc;
@@ -1155,52 +1153,17 @@ int ksm_harvest(KsmEntry& e, unsigned long long* sum, bool clear, int which = 0)
   return 0;
 }
 
-void ksm_free(KsmEntry& e) {
-  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(seed-batched ks scratch)");
-  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(ks replica table)");
-  for (int i = 0; i < KSM_TAB_RING; ++i)
-    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(ks replica table)");
-  e = KsmEntry{};
+// a block that is about to be freed: the debug counters outlive it
+void ksm_before_free(KsmPool::Block& e) {
+  if (spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)")) return;
+  (void)ksm_harvest(e, &g_ksm_wt_released, false);
+  (void)ksm_harvest(e, &g_ksm_cfit_wt_released, false, 1);
 }
 
-// The caller holds g_ksm_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot) and has
-// checked that the stream is not under capture.
-int ksm_scratch(hipStream_t st, unsigned nsteps, char** base, KsMultiEntry** tab_host, hipEvent_t* ev, unsigned* tag_base) {
-  const int dev = current_device_slot();
-  KsmEntry* e = nullptr;
-  for (int i = 0; i < g_ksm_n; ++i)
-    if (g_ksm[i].dev == dev && g_ksm[i].stream == (void*)st) e = &g_ksm[i];
-  if (!e) {
-    if (g_ksm_n == KSM_SCRATCH_MAX)
-      return spo::fail(-1, "update_iter_ex_ks_multi: more than %d (device, stream) pairs hold scratch in this process; call "
-                           "spo_update_scratch_release(stream) for streams that are gone", KSM_SCRATCH_MAX);
-    KsmEntry n{};
-    n.dev = dev; n.stream = (void*)st; n.tag = 16u;
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, KSM_BYTES), "hipMalloc(seed-batched ks scratch)")) return rc;
-    n.base = static_cast<char*>(p);
-    if (int rc = spo::hip_check(hipMemset(p, 0, KSM_BYTES), "hipMemset(seed-batched ks scratch)")) { ksm_free(n); return rc; }
-    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)")) { ksm_free(n); return rc; }
-    void* h = nullptr;
-    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)KSM_TAB_RING * SPO_KS_MAX_REPLICAS * sizeof(KsMultiEntry),
-                                              hipHostMallocDefault), "hipHostMalloc(ks replica table)")) { ksm_free(n); return rc; }
-    n.tab_host = static_cast<KsMultiEntry*>(h);
-    for (int i = 0; i < KSM_TAB_RING; ++i)
-      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(ks replica table)")) {
-        ksm_free(n); return rc;
-      }
-    g_ksm[g_ksm_n] = n;
-    e = &g_ksm[g_ksm_n++];
-  }
-  *base = e->base;
-  *tag_base = e->tag;
-  e->tag += nsteps + 2u;                           // (one tag range per launch serves all runs: their words are their own)
-  const unsigned slot = e->calls++ % KSM_TAB_RING;
-  *tab_host = e->tab_host + (size_t)slot * SPO_KS_MAX_REPLICAS;
-  *ev = e->ev[slot];
-  // (an event that was never recorded is complete)
-  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(ks replica table)");
-}
+// one tag range per launch serves all runs of it: their words are their own
+KsmPool g_ksm{KSM_BYTES, true, "update_iter_ex_ks_multi: more than %d (device, stream) pairs hold scratch in this process; call "
+                               "spo_update_scratch_release(stream) for streams that are gone",
+              "seed-batched ks scratch", "ks replica table", ksm_before_free};
 
 }  // namespace
 
@@ -1218,19 +1181,7 @@ int spo::ks_scratch_release(int dev, void* stream_or_null, int all) {
     }
   }
   std::lock_guard<std::mutex> lk(g_ksm_mu);
-  for (int i = 0; i < g_ksm_n;) {
-    if (g_ksm[i].dev == dev && (all || g_ksm[i].stream == stream_or_null)) {
-      if (spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(seed-batched ks scratch)") == 0) {
-        (void)ksm_harvest(g_ksm[i], &g_ksm_wt_released, false);       // (the debug counters outlive the block)
-        (void)ksm_harvest(g_ksm[i], &g_ksm_cfit_wt_released, false, 1);
-      }
-      ksm_free(g_ksm[i]);
-      g_ksm[i] = g_ksm[--g_ksm_n];
-      g_ksm[g_ksm_n] = KsmEntry{};
-      ++freed;
-    } else ++i;
-  }
-  return freed;
+  return freed + g_ksm.release(dev, stream_or_null, all);
 }
 
 #ifdef SPO_KS_PROF
@@ -1243,19 +1194,12 @@ extern "C" int spo_ks_supported(int obs_dim, int act_dim, int batch) {
   return (obs_dim >= 1 && obs_dim <= 64 * KS_MAX_SLICES && act_dim >= 1 && act_dim <= KS_OUT && batch >= 1 && batch <= 64) ? 1 : 0;
 }
 
-// kind: 0 = clipped-surrogate step, 1 = critic fit, 2 = KL-penalty actor loss, 3 = one minibatch's gradient only; the caller sets n_nets / first_net
-static int ks_launch(KsArgs& a, const spo_ppo_cfg* cfg_host, int64_t adam_step_host, int64_t adam_step_actor_host, int64_t M,
-                     void* sync_ws, hipStream_t st, int kind) {
+// a: filled by fill_run_ex.  kind: 0 = clipped-surrogate step, 1 = critic fit, 2 = KL-penalty actor loss, 3 = one minibatch's gradient only
+static int ks_launch(KsArgs& a, void* sync_ws, hipStream_t st, int kind) {
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  a.cfg = *cfg_host; a.M = M;
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = pow((double)cfg_host->beta1, (double)adam_step_actor_host);
-  a.pow_b2_actor = pow((double)cfg_host->beta2, (double)adam_step_actor_host);
-  a.S = (cfg_host->obs_dim + 63) / 64;
-  { const char* e = getenv("SPO_KS_SAFE"); a.force_safe = (e && *e && *e != '0') ? 1 : 0; }
-  const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
+  a.S = (a.cfg.obs_dim + 63) / 64;
+  a.force_safe = spo::env_flag("SPO_KS_SAFE");
+  const int64_t nsteps = (a.M + a.cfg.batch - 1) / a.cfg.batch;
   SPO_REQUIRE(nsteps < (1ll << 30), "update_iter_ks: too many minibatch steps in one launch");
   KsScratch sc;
   bool* primed = nullptr;
@@ -1300,10 +1244,9 @@ extern "C" int spo_ppo_lag_update_iter_ks(float* theta, float* adam_m, float* ad
               "update_iter_ks: null pointer");
   SPO_REQUIRE(M > 0 && adam_step_host >= 0, "update_iter_ks: bad sizes");
   KsArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.losses = losses_out; a.n_nets = 3; a.first_net = 0;
-  if (int rc = ks_launch(a, cfg_host, adam_step_host, adam_step_host, M, sync_ws, (hipStream_t)stream, 0)) return rc;
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_host, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
+                   *cfg_host, 3, 0, nullptr, losses_out, sync_ws);
+  if (int rc = ks_launch(a, sync_ws, (hipStream_t)stream, 0)) return rc;
   SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_ks");
   return 0;
 }
@@ -1322,12 +1265,12 @@ extern "C" int spo_ppo_lag_grad_ks(const float* theta, const float* obs, const f
   SPO_REQUIRE(theta && obs && act && logp_old && target_r && target_c && adv && idx && flat_grad && losses3 && sync_ws,
               "ppo_lag_grad_ks: null pointer");
   KsArgs a{};
-  a.theta = const_cast<float*>(theta); a.adam_m = const_cast<float*>(theta); a.adam_v = const_cast<float*>(theta);   // (moments: loaded, never used or stored)
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = idx; a.losses = losses3; a.n_nets = 3; a.first_net = 0; a.flat_grad = flat_grad;
   spo_ppo_cfg c = *cfg_host;
   c.batch = n;                                        // one minibatch of exactly the rows given
-  if (int rc = ks_launch(a, &c, 0, 0, n, sync_ws, (hipStream_t)stream, 3)) return rc;
+  float* const th = const_cast<float*>(theta);        // (also as the moments: loaded, never used or stored)
+  spo::fill_run_ex(a, th, th, th, 0, 0, obs, act, logp_old, target_r, target_c, adv, idx, n, c, 3, 0, nullptr, losses3, sync_ws);
+  a.flat_grad = flat_grad;
+  if (int rc = ks_launch(a, sync_ws, (hipStream_t)stream, 3)) return rc;
   SPO_LAUNCH_CHECK("spo_ppo_lag_grad_ks");
   return 0;
 }
@@ -1349,13 +1292,10 @@ extern "C" int spo_update_iter_ex_ks(float* theta, float* adam_m, float* adam_v,
   SPO_REQUIRE(actor_only || (target_r && target_c), "update_iter_ex_ks: critic targets are NULL");
   SPO_REQUIRE(M > 0 && adam_step_critics_host >= 0 && adam_step_actor_host >= 0, "update_iter_ex_ks: bad sizes");
   KsArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.losses = losses_out;
-  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef;
-  a.n_nets = actor_only ? 1 : 3; a.first_net = actor_only ? 2 : 0;
-  if (int rc = ks_launch(a, cfg_host, adam_step_critics_host, adam_step_actor_host, M, sync_ws, (hipStream_t)stream,
-                         actor_loss == SPO_ACTOR_LOSS_KL_PENALTY ? 2 : 0)) return rc;
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_critics_host, adam_step_actor_host, obs, act, logp_old, target_r, target_c, adv,
+                   perm, M, *cfg_host, actor_only ? 1 : 3, actor_only ? 2 : 0, nullptr, losses_out, sync_ws, old_mean, old_std, kl_bound,
+                   pg_coef);
+  if (int rc = ks_launch(a, sync_ws, (hipStream_t)stream, actor_loss == SPO_ACTOR_LOSS_KL_PENALTY ? 2 : 0)) return rc;
   SPO_LAUNCH_CHECK("spo_update_iter_ex_ks");
   return 0;
 }
@@ -1378,10 +1318,9 @@ extern "C" int spo_critic_fit_iter_ks(float* theta, float* adam_m, float* adam_v
               "critic_fit_iter_ks: null pointer");
   SPO_REQUIRE(M > 0 && adam_step_host >= 0, "critic_fit_iter_ks: bad sizes");
   KsArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.tgt_r = target_r; a.tgt_c = target_c;
-  a.perm = perm; a.losses = losses_out; a.stale_io = stale_sq_io; a.n_nets = 2; a.first_net = 0;
-  if (int rc = ks_launch(a, cfg_host, adam_step_host, adam_step_host, M, sync_ws, (hipStream_t)stream, 1)) return rc;
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_host, adam_step_host, obs, nullptr, nullptr, target_r, target_c, nullptr, perm, M,
+                   *cfg_host, 2, 0, stale_sq_io, losses_out, sync_ws);
+  if (int rc = ks_launch(a, sync_ws, (hipStream_t)stream, 1)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_ks");
   return 0;
 }
@@ -1398,13 +1337,7 @@ extern "C" int spo_update_ks_multi_supported(int obs_dim, int act_dim, int batch
 
 extern "C" int spo_update_ks_multi_block_map(int block, int obs_dim, int n_replicas, int actor_only, int* replica, int* wg) {
   if (!spo_update_ks_multi_supported(obs_dim, 1, 1, n_replicas)) return 0;
-  const int wgs = (actor_only ? 1 : 3) * ((obs_dim + 63) / 64);
-  if (block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
-  int r = 0, w = 0;
-  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
-  if (work && replica) *replica = r;
-  if (work && wg) *wg = w;
-  return work ? 1 : 0;
+  return spo::block_map_query(block, n_replicas, SPO_KS_MAX_REPLICAS, (actor_only ? 1 : 3) * ((obs_dim + 63) / 64), replica, wg);
 }
 
 extern "C" int spo_debug_update_ks_multi_counters(unsigned long long* out3_host, int reset) {
@@ -1413,9 +1346,9 @@ extern "C" int spo_debug_update_ks_multi_counters(unsigned long long* out3_host,
   std::lock_guard<std::mutex> lk(g_ksm_mu);
   const int dev = current_device_slot();
   unsigned long long wt = g_ksm_wt_released;
-  for (int i = 0; i < g_ksm_n; ++i)
-    if (g_ksm[i].dev == dev)
-      if (int rc = ksm_harvest(g_ksm[i], &wt, reset != 0)) return rc;
+  for (int i = 0; i < g_ksm.n; ++i)
+    if (g_ksm.e[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm.e[i], &wt, reset != 0)) return rc;
   if (reset) g_ksm_wt_released = 0;
   for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_counters[i].exchange(0ull) : g_ksm_counters[i].load();
   out3_host[2] = wt;
@@ -1425,19 +1358,14 @@ extern "C" int spo_debug_update_ks_multi_counters(unsigned long long* out3_host,
 extern "C" int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_host, int n_replicas, int64_t M, int actor_loss,
                                            int actor_only, void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "update_iter_ex_ks_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_KS_MAX_REPLICAS, "update_iter_ex_ks_multi: %d replicas outside [1, %d]",
-              n_replicas, SPO_KS_MAX_REPLICAS);
+  constexpr const char* NAME = "update_iter_ex_ks_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_KS_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || actor_loss == SPO_ACTOR_LOSS_KL_PENALTY,
               "update_iter_ex_ks_multi: unknown actor_loss %d", actor_loss);
   SPO_REQUIRE(M > 0, "update_iter_ex_ks_multi: bad sizes");
   const spo_ppo_cfg& c0 = reps_host[0].cfg;
-  for (int r = 0; r < n_replicas; ++r) {
-    const spo_update_ex_replica& p = reps_host[r];
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "update_iter_ex_ks_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
-                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
-  }
+  for (int r = 0; r < n_replicas; ++r)
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
   SPO_REQUIRE(spo_ks_supported(c0.obs_dim, c0.act_dim, c0.batch),
               "update_iter_ex_ks_multi: obs_dim %d / act_dim %d / batch %d outside [1,%d] / [1,%d] / [1,64]", c0.obs_dim, c0.act_dim,
               c0.batch, 64 * KS_MAX_SLICES, KS_OUT);
@@ -1456,70 +1384,44 @@ extern "C" int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_hos
                 "update_iter_ex_ks_multi: old distribution is NULL in replica %d", r);
     SPO_REQUIRE(actor_only || (p.target_r && p.target_c), "update_iter_ex_ks_multi: critic targets are NULL in replica %d", r);
     SPO_REQUIRE(p.adam_step_critics >= 0 && p.adam_step_actor >= 0, "update_iter_ex_ks_multi: replica %d: negative adam_step", r);
-    for (int q = 0; q < r; ++q)
-      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
-                  "update_iter_ex_ks_multi: replicas %d and %d share theta or sync_ws", q, r);
+    if (int rc = spo::distinct(NAME, reps_host, r)) return rc;
     n_active += p.active ? 1 : 0;
   }
   if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
   hipStream_t st = (hipStream_t)stream;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return spo::fail(-1, "update_iter_ex_ks_multi: the stream is under capture (the argument table is copied from host memory at "
-                           "every call: not a graph node)");
-  }
+  if (spo::stream_is_capturing(st))
+    return spo::fail(-1, "update_iter_ex_ks_multi: the stream is under capture (the argument table is copied from host memory at "
+                         "every call: not a graph node)");
   const int n_nets = actor_only ? 1 : 3, wgs = n_nets * S;
-  int force_safe;
-  { const char* e = getenv("SPO_KS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  const int force_safe = spo::env_flag("SPO_KS_SAFE");
   std::lock_guard<std::mutex> lk(g_ksm_mu);                                // (until the table's copy and its event are enqueued)
-  char* base = nullptr;
-  KsMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  unsigned tag_base = 0;
-  if (int rc = ksm_scratch(st, (unsigned)nsteps, &base, &tab, &tab_ev, &tag_base)) return rc;
+  KsmPool::Slot sl{};
+  if (int rc = g_ksm.acquire(st, (unsigned)nsteps, &sl)) return rc;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_update_ex_replica& p = reps_host[r];
-    KsArgs a{};                                                            // (as spo_update_iter_ex_ks and ks_launch fill it)
-    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
-    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
-    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
-    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * KSM_STRIDE);
-    a.gran = reinterpret_cast<unsigned long long*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step_critics);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step_critics);
-    a.pow_b1_actor = pow((double)p.cfg.beta1, (double)p.adam_step_actor);
-    a.pow_b2_actor = pow((double)p.cfg.beta2, (double)p.adam_step_actor);
-    a.tag_base = tag_base; a.S = S; a.n_nets = n_nets; a.first_net = actor_only ? 2 : 0;
-    a.old_mean = p.old_mean; a.old_std = p.old_std; a.kl_bound = p.kl_bound; a.pg_coef = p.pg_coef;
+    KsArgs a{};
+    spo::fill_run_ex(a, p.theta, p.adam_m, p.adam_v, p.adam_step_critics, p.adam_step_actor, p.obs, p.act, p.logp_old, p.target_r,
+                     p.target_c, p.adv, p.perm, M, p.cfg, n_nets, actor_only ? 2 : 0, nullptr, p.losses_out, p.sync_ws, p.old_mean,
+                     p.old_std, p.kl_bound, p.pg_coef);
+    a.zbuf = reinterpret_cast<float*>(sl.base + (size_t)r * KSM_STRIDE);
+    a.gran = reinterpret_cast<unsigned long long*>(sl.base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
+    a.tag_base = sl.tag_base; a.S = S;
     a.force_safe = force_safe;
-    tab[r].a = a;
-    tab[r].active = p.active ? 1 : 0;
+    sl.tab_host[r].a = a;
+    sl.tab_host[r].active = p.active ? 1 : 0;
   }
-  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(base + KSM_T_OFF);
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(KsMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(ks replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(ks replica table)")) return rc;
+  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(sl.base + KSM_T_OFF);
+  if (int rc = spo::upload_table(table_dev, sl.tab_host, n_replicas, sl.ev, st, "ks replica table")) return rc;
   // every partial slot of every active run starts as the sentinel (ks_launch); the run's row of zeros behind them stays zero
   for (int r = 0; r < n_replicas; ++r)
     if (reps_host[r].active)
-      if (int rc = spo::hip_check(hipMemsetAsync(base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
+      if (int rc = spo::hip_check(hipMemsetAsync(sl.base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
         return rc;
-  const size_t sh = KsLds::SIZE * sizeof(float);
   const bool klpen = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
-  static bool attr_done[SPO_MAX_DEVICES][2] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot][klpen]) {
-    const void* fn = klpen ? reinterpret_cast<const void*>(&klpen_update_ks_multi_kernel)
-                           : reinterpret_cast<const void*>(&ppo_update_ks_multi_kernel);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_ks_multi)");
-    attr_done[dslot][klpen] = true;
-  }
-  const dim3 grid(spo::rs_multi_grid(n_replicas, wgs));
-  if (klpen) hipLaunchKernelGGL(klpen_update_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
-  else hipLaunchKernelGGL(ppo_update_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
+  static bool attr_done[2][SPO_MAX_DEVICES] = {};
+  if (int rc = spo::launch_dyn_lds(klpen ? &klpen_update_ks_multi_kernel : &ppo_update_ks_multi_kernel, attr_done[klpen],
+                                   "hipFuncSetAttribute(update_ks_multi)", dim3(spo::rs_multi_grid(n_replicas, wgs)), dim3(256),
+                                   KsLds::SIZE * sizeof(float), st, table_dev, n_replicas, wgs)) return rc;
   SPO_LAUNCH_CHECK("spo_update_iter_ex_ks_multi");
   g_ksm_counters[0] += 1ull;
   g_ksm_counters[1] += (unsigned long long)n_active;
@@ -1541,13 +1443,7 @@ extern "C" int spo_critic_fit_ks_multi_supported(int obs_dim, int batch, int n_r
 
 extern "C" int spo_critic_fit_ks_multi_block_map(int block, int obs_dim, int n_replicas, int* replica, int* wg) {
   if (!spo_critic_fit_ks_multi_supported(obs_dim, 1, n_replicas)) return 0;
-  const int wgs = 2 * ((obs_dim + 63) / 64);
-  if (block < 0 || block >= spo::rs_multi_grid(n_replicas, wgs)) return 0;
-  int r = 0, w = 0;
-  const bool work = spo::rs_multi_map(block, n_replicas, wgs, &r, &w);
-  if (work && replica) *replica = r;
-  if (work && wg) *wg = w;
-  return work ? 1 : 0;
+  return spo::block_map_query(block, n_replicas, SPO_KS_MAX_REPLICAS, 2 * ((obs_dim + 63) / 64), replica, wg);
 }
 
 extern "C" int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_host, int reset) {
@@ -1556,9 +1452,9 @@ extern "C" int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_h
   std::lock_guard<std::mutex> lk(g_ksm_mu);
   const int dev = current_device_slot();
   unsigned long long wt = g_ksm_cfit_wt_released;
-  for (int i = 0; i < g_ksm_n; ++i)
-    if (g_ksm[i].dev == dev)
-      if (int rc = ksm_harvest(g_ksm[i], &wt, reset != 0, 1)) return rc;
+  for (int i = 0; i < g_ksm.n; ++i)
+    if (g_ksm.e[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm.e[i], &wt, reset != 0, 1)) return rc;
   if (reset) g_ksm_cfit_wt_released = 0;
   for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_cfit_counters[i].exchange(0ull) : g_ksm_cfit_counters[i].load();
   out3_host[2] = wt;
@@ -1567,17 +1463,12 @@ extern "C" int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_h
 
 extern "C" int spo_critic_fit_iter_ks_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "critic_fit_iter_ks_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_KS_MAX_REPLICAS, "critic_fit_iter_ks_multi: %d replicas outside [1, %d]",
-              n_replicas, SPO_KS_MAX_REPLICAS);
+  constexpr const char* NAME = "critic_fit_iter_ks_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_KS_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(M > 0, "critic_fit_iter_ks_multi: bad sizes (M = %lld)", (long long)M);
   const spo_ppo_cfg& c0 = reps_host[0].cfg;
-  for (int r = 0; r < n_replicas; ++r) {
-    const spo_critic_fit_replica& p = reps_host[r];
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "critic_fit_iter_ks_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
-                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
-  }
+  for (int r = 0; r < n_replicas; ++r)
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
   SPO_REQUIRE(spo_critic_fit_ks_supported(c0.obs_dim, c0.batch),
               "critic_fit_iter_ks_multi: obs_dim %d / batch %d outside [1,%d] / [1,128]", c0.obs_dim, c0.batch, 64 * KS_MAX_SLICES);
   SPO_REQUIRE(c0.act_dim >= 1, "critic_fit_iter_ks_multi: act_dim %d (the flat parameter layout needs the actor's size)", c0.act_dim);
@@ -1594,67 +1485,44 @@ extern "C" int spo_critic_fit_iter_ks_multi(const spo_critic_fit_replica* reps_h
                     ((p.perm && p.losses_out) || !p.active), "critic_fit_iter_ks_multi: null pointer in replica %d", r);
     SPO_REQUIRE(p.stale_sq_io, "critic_fit_iter_ks_multi: stale_sq_io is NULL in replica %d", r);
     SPO_REQUIRE(p.adam_step >= 0, "critic_fit_iter_ks_multi: replica %d: negative adam_step", r);
-    for (int q = 0; q < r; ++q)
-      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws && reps_host[q].stale_sq_io != p.stale_sq_io,
-                  "critic_fit_iter_ks_multi: replicas %d and %d share theta, sync_ws or stale_sq_io", q, r);
+    if (int rc = spo::distinct(NAME, reps_host, r)) return rc;
     n_active += p.active ? 1 : 0;
   }
   if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
   hipStream_t st = (hipStream_t)stream;
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return spo::fail(-1, "critic_fit_iter_ks_multi: the stream is under capture (the argument table is copied from host memory at "
-                           "every call: not a graph node)");
-  }
+  if (spo::stream_is_capturing(st))
+    return spo::fail(-1, "critic_fit_iter_ks_multi: the stream is under capture (the argument table is copied from host memory at "
+                         "every call: not a graph node)");
   const int wgs = 2 * S;
-  int force_safe;
-  { const char* e = getenv("SPO_KS_SAFE"); force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  const int force_safe = spo::env_flag("SPO_KS_SAFE");
   std::lock_guard<std::mutex> lk(g_ksm_mu);                                // (until the table's copy and its event are enqueued)
-  char* base = nullptr;
-  KsMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  unsigned tag_base = 0;
-  if (int rc = ksm_scratch(st, (unsigned)nsteps, &base, &tab, &tab_ev, &tag_base)) return rc;
+  KsmPool::Slot sl{};
+  if (int rc = g_ksm.acquire(st, (unsigned)nsteps, &sl)) return rc;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_critic_fit_replica& p = reps_host[r];
-    KsArgs a{};                                                            // (as spo_critic_fit_iter_ks and ks_launch fill it)
-    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
-    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c;
-    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out; a.stale_io = p.stale_sq_io;
-    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * KSM_STRIDE);
-    a.gran = reinterpret_cast<unsigned long long*>(base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
-    a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-    a.tag_base = tag_base; a.S = S; a.n_nets = 2; a.first_net = 0;
+    KsArgs a{};
+    spo::fill_run_ex(a, p.theta, p.adam_m, p.adam_v, p.adam_step, p.adam_step, p.obs, nullptr, nullptr, p.target_r, p.target_c, nullptr,
+                     p.perm, M, p.cfg, 2, 0, p.stale_sq_io, p.losses_out, p.sync_ws);
+    a.zbuf = reinterpret_cast<float*>(sl.base + (size_t)r * KSM_STRIDE);
+    a.gran = reinterpret_cast<unsigned long long*>(sl.base + (size_t)r * KSM_STRIDE + KS_Z_BYTES);
+    a.tag_base = sl.tag_base; a.S = S;
     a.force_safe = force_safe;
-    tab[r].a = a;
-    tab[r].active = p.active ? 1 : 0;
+    sl.tab_host[r].a = a;
+    sl.tab_host[r].active = p.active ? 1 : 0;
   }
-  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(base + KSM_T_OFF);
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(KsMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(ks replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(ks replica table)")) return rc;
+  KsMultiEntry* const table_dev = reinterpret_cast<KsMultiEntry*>(sl.base + KSM_T_OFF);
+  if (int rc = spo::upload_table(table_dev, sl.tab_host, n_replicas, sl.ev, st, "ks replica table")) return rc;
   // every partial slot of every active run starts as the sentinel (ks_launch); the run's row of zeros behind them stays zero.
   // (sync_ws: only the error word at byte 64 is the kernel's; its first 64 bytes are NOT zeroed here, unlike ks_launch -- nothing
   // of the feature-split kernels reads them, and an inactive run's sync_ws must stay untouched)
   for (int r = 0; r < n_replicas; ++r)
     if (reps_host[r].active)
-      if (int rc = spo::hip_check(hipMemsetAsync(base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
+      if (int rc = spo::hip_check(hipMemsetAsync(sl.base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
         return rc;
-  const size_t sh = KsLds::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&critic_fit_ks_multi_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(critic_fit_ks_multi)");
-    attr_done[dslot] = true;
-  }
-  const dim3 grid(spo::rs_multi_grid(n_replicas, wgs));
-  hipLaunchKernelGGL(critic_fit_ks_multi_kernel, grid, dim3(256), sh, st, table_dev, n_replicas, wgs);
+  if (int rc = spo::launch_dyn_lds(&critic_fit_ks_multi_kernel, attr_done, "hipFuncSetAttribute(critic_fit_ks_multi)",
+                                   dim3(spo::rs_multi_grid(n_replicas, wgs)), dim3(256), KsLds::SIZE * sizeof(float), st, table_dev,
+                                   n_replicas, wgs)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_ks_multi");
   g_ksm_cfit_counters[0] += 1ull;
   g_ksm_cfit_counters[1] += (unsigned long long)n_active;

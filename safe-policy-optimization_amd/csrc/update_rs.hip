@@ -40,6 +40,7 @@
 #include "adam.h"
 #include "../../include/safepo_hip.h"
 #include "update_rs.h"
+#include "replica_batch.h"
 
 namespace {
 using namespace spo;
@@ -1697,8 +1698,7 @@ int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* t
     if (g_rs_n == RS_SCRATCH_MAX)
       return spo::fail(-1, "row-split update kernel: more than %d (device, stream) pairs hold exchange scratch in this process; "
                            "call spo_update_scratch_release(stream) for streams that are gone", RS_SCRATCH_MAX);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (spo::stream_is_capturing(st))
       return spo::fail(-1, "row-split update kernel: first launch on a stream under capture (the scratch block is allocated on "
                            "first use: launch once outside the capture)");
     void* p = nullptr;
@@ -1727,8 +1727,7 @@ int rs_stage_block(hipStream_t st, size_t bytes, char** out) {
     if (g_rs[i].dev == dev && g_rs[i].stream == (void*)st) e = &g_rs[i];
   if (!e) return spo::fail(-1, "row-split update kernel: no scratch entry for this stream");
   if (e->stage_bytes < bytes) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+    if (spo::stream_is_capturing(st)) return 0;
     if (e->stage) {
       (void)spo::hip_check(hipFree(e->stage), "hipFree(rs stage)");
       e->stage = nullptr; e->stage_bytes = 0;
@@ -1898,14 +1897,10 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
                           float* losses_out, void* sync_ws, unsigned long long* prof, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   RsArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.M = M; a.cfg = *cfg_host; a.losses = losses_out;
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.n_nets = n_nets; a.first_net = 0; a.stale_io = stale_sq_io; a.prof = prof;
-  { const char* e = getenv("SPO_RS_SAFE"); a.force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  spo::fill_run(a, theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M, *cfg_host, n_nets, 0,
+                stale_sq_io, losses_out, sync_ws);
+  a.prof = prof;
+  a.force_safe = spo::env_flag("SPO_RS_SAFE");
   a.clip_thr_sq = rs_clip_threshold(cfg_host->max_grad_norm);
   const bool l1p = rs_l1_pipe();
   const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
@@ -1978,14 +1973,10 @@ int spo::rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t
   SPO_REQUIRE(cfg_host->batch <= 64, "update_rs (data-parallel): batch %d > 64", cfg_host->batch);
   hipStream_t st = (hipStream_t)stream;
   RsArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.M = M; a.cfg = *cfg_host; a.losses = losses_out;
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.n_nets = 3; a.first_net = 0; a.stale_io = nullptr; a.prof = nullptr; a.prof_wg = -1;
-  { const char* e = getenv("SPO_RS_SAFE"); a.force_safe = (e && *e && *e != '0') ? 1 : 0; }
+  spo::fill_run(a, theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M, *cfg_host, 3, 0, nullptr,
+                losses_out, sync_ws);
+  a.prof = nullptr; a.prof_wg = -1;
+  a.force_safe = spo::env_flag("SPO_RS_SAFE");
   a.clip_thr_sq = -1.f;                                                    // (the data-parallel forms have no fast path)
   for (int r = 0; r < 8; ++r) a.xr_region[r] = r < world ? regions[r] : nullptr;
   a.xr_rank = rank; a.xr_step0 = step0; a.rsx_off = rsx_off;
@@ -2017,100 +2008,29 @@ struct RsmLayout {
 };
 constexpr RsmLayout RSM_PPO{rs_z_bytes(2), SPO_RS_MAX_REPLICAS};                 // ~49 MB
 constexpr RsmLayout RSM_CRITIC{rs_z_bytes(4), SPO_RS_CRITIC_MAX_REPLICAS};       // 24 x 6 MiB of slots + 30 KB: ~151 MB
-// The argument table leaves the host from pinned memory: RSM_TAB_RING tables per entry, used in turn, each with an event recorded
-// behind its copy -- a table is rewritten only once the copy that read it last has completed, so a launch makes the host wait
-// only when RSM_TAB_RING launches are already queued behind one another.
-constexpr int RSM_TAB_RING = 4;
-struct RsmEntry { int dev; void* stream; char* base; unsigned tag; RsMultiEntry* tab_host; hipEvent_t ev[RSM_TAB_RING]; unsigned calls; };
-struct RsmPool { RsmLayout lay; RsmEntry e[RS_SCRATCH_MAX]; int n; };
-RsmPool g_rsm{RSM_PPO, {}, 0};
-RsmPool g_rsm_critic{RSM_CRITIC, {}, 0};
+// The argument table leaves the host through the pool's pinned ring (replica_batch.h).  Both pools are used under g_rs_mu.
+constexpr const char* RSM_FULL = "replica-batched update: more than %d (device, stream) pairs hold exchange scratch in this process; "
+                                 "call spo_update_scratch_release(stream) for streams that are gone";
+spo::ReplicaPool<RsMultiEntry, SPO_RS_MAX_REPLICAS, RS_SCRATCH_MAX> g_rsm{
+    RSM_PPO.bytes(), true, RSM_FULL, "replica-batched rs scratch", "replica table", nullptr};
+spo::ReplicaPool<RsMultiEntry, SPO_RS_CRITIC_MAX_REPLICAS, RS_SCRATCH_MAX> g_rsm_critic{
+    RSM_CRITIC.bytes(), true, RSM_FULL, "replica-batched rs scratch", "replica table", nullptr};
 
-void rsm_free(RsmEntry& e) {
-  if (e.base) (void)spo::hip_check(hipFree(e.base), "hipFree(replica-batched rs scratch)");
-  if (e.tab_host) (void)spo::hip_check(hipHostFree(e.tab_host), "hipHostFree(replica table)");
-  for (int i = 0; i < RSM_TAB_RING; ++i)
-    if (e.ev[i]) (void)spo::hip_check(hipEventDestroy(e.ev[i]), "hipEventDestroy(replica table)");
-  e = RsmEntry{};
-}
-
-// The caller holds g_rs_mu (and keeps it until its table copy is enqueued: *tab_host / *ev are this call's ring slot).
-int rsm_scratch(RsmPool& pool, hipStream_t st, char** base, unsigned* tag_base, unsigned nsteps, RsMultiEntry** tab_host, hipEvent_t* ev) {
-  const int dev = current_device_slot();
-  const size_t bytes = pool.lay.bytes();
-  RsmEntry* e = nullptr;
-  for (int i = 0; i < pool.n; ++i)
-    if (pool.e[i].dev == dev && pool.e[i].stream == (void*)st) e = &pool.e[i];
-  if (!e) {
-    if (pool.n == RS_SCRATCH_MAX)
-      return spo::fail(-1, "replica-batched update: more than %d (device, stream) pairs hold exchange scratch in this process; "
-                           "call spo_update_scratch_release(stream) for streams that are gone", RS_SCRATCH_MAX);
-    RsmEntry n{};
-    n.dev = dev; n.stream = (void*)st; n.tag = 16u;
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, bytes), "hipMalloc(replica-batched rs scratch)")) return rc;
-    n.base = static_cast<char*>(p);
-    if (int rc = spo::hip_check(hipMemset(p, 0, bytes), "hipMemset(replica-batched rs scratch)")) { rsm_free(n); return rc; }
-    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(replica-batched rs scratch)")) { rsm_free(n); return rc; }
-    void* h = nullptr;
-    if (int rc = spo::hip_check(hipHostMalloc(&h, (size_t)RSM_TAB_RING * pool.lay.max_reps * sizeof(RsMultiEntry), hipHostMallocDefault),
-                                "hipHostMalloc(replica table)")) { rsm_free(n); return rc; }
-    n.tab_host = static_cast<RsMultiEntry*>(h);
-    for (int i = 0; i < RSM_TAB_RING; ++i)
-      if (int rc = spo::hip_check(hipEventCreateWithFlags(&n.ev[i], hipEventDisableTiming), "hipEventCreate(replica table)")) {
-        rsm_free(n); return rc;
-      }
-    pool.e[pool.n] = n;
-    e = &pool.e[pool.n++];
-  }
-  *base = e->base;
-  *tag_base = e->tag;
-  e->tag += nsteps + 2u;
-  const unsigned slot = e->calls++ % RSM_TAB_RING;
-  *tab_host = e->tab_host + (size_t)slot * pool.lay.max_reps;
-  *ev = e->ev[slot];
-  // (an event that was never recorded is complete)
-  return spo::hip_check(hipEventSynchronize(*ev), "hipEventSynchronize(replica table)");
-}
-
-int rsm_release(RsmPool& pool, int dev, void* stream_or_null, int all) {
-  int freed = 0;
-  for (int i = 0; i < pool.n;) {
-    if (pool.e[i].dev == dev && (all || pool.e[i].stream == stream_or_null)) {
-      rsm_free(pool.e[i]);
-      pool.e[i] = pool.e[--pool.n];
-      pool.e[pool.n] = RsmEntry{};
-      ++freed;
-    } else ++i;
-  }
-  return freed;
-}
-
-// Launch helper of both replica-batched kernels (WGS workgroups per replica).
-template <typename K>
-int rs_multi_launch(K kernel, bool* attr_done, size_t sh, int wgs, const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs_multi)");
-    attr_done[dslot] = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(rs_multi_grid(n_replicas, wgs)), dim3(512), sh, st, table_dev, n_replicas);
-  return 0;
-}
-
+// Launch of both replica-batched kernels (wgs workgroups per replica).
 template <int KIN, bool L1P>
 int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  return rs_multi_launch(&ppo_update_rs_multi_kernel<KIN, L1P, 2, 3>, attr_done, RsLds<KIN, 2>::SIZE * sizeof(float), RS_MULTI_WG, table_dev,
-                         n_replicas, st);
+  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, L1P, 2, 3>, attr_done, "hipFuncSetAttribute(update_rs_multi)",
+                             dim3(rs_multi_grid(n_replicas, RS_MULTI_WG)), dim3(512), RsLds<KIN, 2>::SIZE * sizeof(float), st, table_dev,
+                             n_replicas);
 }
 
 template <int KIN>
 int rs_critic_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  return rs_multi_launch(&ppo_update_rs_multi_kernel<KIN, false, 4, 2>, attr_done, RsLds<KIN, 2>::SIZE * sizeof(float), RS_CRITIC_MULTI_WG, table_dev,
-                         n_replicas, st);
+  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, false, 4, 2>, attr_done, "hipFuncSetAttribute(update_rs_multi)",
+                             dim3(rs_multi_grid(n_replicas, RS_CRITIC_MULTI_WG)), dim3(512), RsLds<KIN, 2>::SIZE * sizeof(float), st,
+                             table_dev, n_replicas);
 }
 
 int rs_counters_rw(const void* symbol, unsigned long long* out2_host, int reset) {
@@ -2122,26 +2042,11 @@ int rs_counters_rw(const void* symbol, unsigned long long* out2_host, int reset)
   return 0;
 }
 
-int rs_block_map_query(int block, int n_replicas, int max_reps, int wgs, int* replica, int* wg) {
-  if (n_replicas < 1 || n_replicas > max_reps || block < 0 || block >= rs_multi_grid(n_replicas, wgs)) return 0;
-  int r = 0, w = 0;
-  const bool work = rs_multi_map(block, n_replicas, wgs, &r, &w);
-  if (work && replica) *replica = r;
-  if (work && wg) *wg = w;
-  return work ? 1 : 0;
-}
-
-int rs_force_safe() { const char* e = getenv("SPO_RS_SAFE"); return (e && *e && *e != '0') ? 1 : 0; }
-
-bool stream_is_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-}
 }  // namespace
 
 int spo::rs_multi_scratch_release(int dev, void* stream_or_null, int all) {
   std::lock_guard<std::mutex> lk(g_rs_mu);
-  return rsm_release(g_rsm, dev, stream_or_null, all) + rsm_release(g_rsm_critic, dev, stream_or_null, all);
+  return g_rsm.release(dev, stream_or_null, all) + g_rsm_critic.release(dev, stream_or_null, all);
 }
 
 extern "C" int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch, int n_replicas) {
@@ -2150,11 +2055,11 @@ extern "C" int spo_update_rs_multi_supported(int obs_dim, int act_dim, int batch
 }
 
 extern "C" int spo_rs_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
-  return rs_block_map_query(block, n_replicas, SPO_RS_MAX_REPLICAS, RS_MULTI_WG, replica, wg);
+  return spo::block_map_query(block, n_replicas, SPO_RS_MAX_REPLICAS, RS_MULTI_WG, replica, wg);
 }
 
 extern "C" int spo_rs_critic_multi_block_map(int block, int n_replicas, int* replica, int* wg) {
-  return rs_block_map_query(block, n_replicas, SPO_RS_CRITIC_MAX_REPLICAS, RS_CRITIC_MULTI_WG, replica, wg);
+  return spo::block_map_query(block, n_replicas, SPO_RS_CRITIC_MAX_REPLICAS, RS_CRITIC_MULTI_WG, replica, wg);
 }
 
 extern "C" int spo_debug_clip_threshold(float max_grad_norm, float* thr_sq_out_host) {
@@ -2176,9 +2081,8 @@ extern "C" int spo_debug_rs_critic_multi_counters(unsigned long long* out2_host,
 
 extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host, int n_replicas, int64_t M, void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "update_iter_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_RS_MAX_REPLICAS, "update_iter_multi: %d replicas outside [1, %d]", n_replicas,
-              SPO_RS_MAX_REPLICAS);
+  constexpr const char* NAME = "update_iter_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_RS_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(M > 0, "update_iter_multi: bad sizes");
   const spo_ppo_cfg& c0 = reps_host[0].cfg;
   SPO_REQUIRE(spo_update_rs_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, n_replicas),
@@ -2191,50 +2095,37 @@ extern "C" int spo_ppo_lag_update_iter_multi(const spo_update_replica* reps_host
     SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.act && p.logp_old && p.target_r && p.target_c && p.adv && p.sync_ws &&
                     ((p.perm && p.losses_out) || !p.active), "update_iter_multi: null pointer in replica %d", r);
     SPO_REQUIRE(p.adam_step >= 0, "update_iter_multi: replica %d: negative adam_step", r);
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "update_iter_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r, p.cfg.obs_dim,
-                p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
-    for (int q = 0; q < r; ++q)
-      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws,
-                  "update_iter_multi: replicas %d and %d share theta or sync_ws", q, r);
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
+    if (int rc = spo::distinct(NAME, reps_host, r)) return rc;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st))
+  if (spo::stream_is_capturing(st))
     return spo::fail(-1, "update_iter_multi: the stream is under capture (the argument table is copied from host memory at "
                          "every call: not a graph node)");
-  const int force_safe = rs_force_safe();
+  const int force_safe = spo::env_flag("SPO_RS_SAFE");
   std::lock_guard<std::mutex> lk(g_rs_mu);                                 // (until the table's copy and its event are enqueued)
-  char* base = nullptr;
-  unsigned tag_base = 0;
-  RsMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  if (int rc = rsm_scratch(g_rsm, st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
+  decltype(g_rsm)::Slot sl{};
+  if (int rc = g_rsm.acquire(st, (unsigned)nsteps, &sl)) return rc;
   int n_active = 0;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_update_replica& p = reps_host[r];
     RsArgs a{};
-    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
-    a.obs = p.obs; a.act = p.act; a.logp_old = p.logp_old; a.tgt_r = p.target_r; a.tgt_c = p.target_c; a.adv = p.adv;
-    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
-    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_PPO.z_bytes);
-    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_PPO.g_off() + (size_t)r * RSM_G_STRIDE);
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
-    a.tag_base = tag_base;
-    a.n_nets = 3; a.first_net = 0; a.stale_io = nullptr; a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
+    spo::fill_run(a, p.theta, p.adam_m, p.adam_v, p.adam_step, p.obs, p.act, p.logp_old, p.target_r, p.target_c, p.adv, p.perm, M, p.cfg,
+                  3, 0, nullptr, p.losses_out, p.sync_ws);
+    a.zbuf = reinterpret_cast<float*>(sl.base + (size_t)r * RSM_PPO.z_bytes);
+    a.gran = reinterpret_cast<unsigned long long*>(sl.base + RSM_PPO.g_off() + (size_t)r * RSM_G_STRIDE);
+    a.tag_base = sl.tag_base;
+    a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
     a.clip_thr_sq = rs_clip_threshold(p.cfg.max_grad_norm);
-    tab[r].a = a;
-    tab[r].active = p.active ? 1 : 0;
-    n_active += tab[r].active;
+    sl.tab_host[r].a = a;
+    sl.tab_host[r].active = p.active ? 1 : 0;
+    n_active += sl.tab_host[r].active;
   }
   if (n_active == 0) return 0;
-  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_PPO.t_off());
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(RsMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(sl.base + RSM_PPO.t_off());
+  if (int rc = spo::upload_table(table_dev, sl.tab_host, n_replicas, sl.ev, st, "replica table")) return rc;
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
-  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_PPO.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
+  if (int rc = spo::hip_check(hipMemsetAsync(sl.base, 0xFF, (size_t)n_replicas * RSM_PPO.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : c0.obs_dim <= 64 ? 64 : 128;
   const bool l1p = rs_l1_pipe();                                           // (the form the single launch takes: batched == stand-alone bits)
   int rc = kin == 16 ? rs_multi_launch_k<16, false>(table_dev, n_replicas, st)
@@ -2254,9 +2145,8 @@ extern "C" int spo_critic_fit_multi_supported(int obs_dim, int act_dim, int batc
 
 extern "C" int spo_critic_fit_iter_multi(const spo_critic_fit_replica* reps_host, int n_replicas, int64_t M, void* stream) {
   // ---- everything that can be refused is refused here, before any HIP call
-  SPO_REQUIRE(reps_host, "critic_fit_iter_multi: null replica table");
-  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_RS_CRITIC_MAX_REPLICAS, "critic_fit_iter_multi: %d replicas outside [1, %d]",
-              n_replicas, SPO_RS_CRITIC_MAX_REPLICAS);
+  constexpr const char* NAME = "critic_fit_iter_multi";
+  if (int rc = spo::table_head(NAME, reps_host, n_replicas, SPO_RS_CRITIC_MAX_REPLICAS)) return rc;
   SPO_REQUIRE(M > 0, "critic_fit_iter_multi: bad sizes");
   const spo_ppo_cfg& c0 = reps_host[0].cfg;
   SPO_REQUIRE(spo_critic_fit_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, n_replicas),
@@ -2264,58 +2154,45 @@ extern "C" int spo_critic_fit_iter_multi(const spo_critic_fit_replica* reps_host
               c0.obs_dim, c0.act_dim, c0.batch);
   const int64_t nsteps = (M + c0.batch - 1) / c0.batch;
   SPO_REQUIRE(nsteps < (1ll << 30), "critic_fit_iter_multi: too many minibatch steps in one launch");
+  int n_active = 0;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_critic_fit_replica& p = reps_host[r];
     SPO_REQUIRE(p.theta && p.adam_m && p.adam_v && p.obs && p.target_r && p.target_c && p.stale_sq_io && p.sync_ws &&
                     ((p.perm && p.losses_out) || !p.active), "critic_fit_iter_multi: null pointer in replica %d", r);
     SPO_REQUIRE(p.adam_step >= 0, "critic_fit_iter_multi: replica %d: negative adam_step", r);
-    SPO_REQUIRE(p.cfg.obs_dim == c0.obs_dim && p.cfg.act_dim == c0.act_dim && p.cfg.batch == c0.batch,
-                "critic_fit_iter_multi: replica %d has obs_dim / act_dim / batch %d / %d / %d, replica 0 has %d / %d / %d", r,
-                p.cfg.obs_dim, p.cfg.act_dim, p.cfg.batch, c0.obs_dim, c0.act_dim, c0.batch);
-    for (int q = 0; q < r; ++q)
-      SPO_REQUIRE(reps_host[q].theta != p.theta && reps_host[q].sync_ws != p.sync_ws && reps_host[q].stale_sq_io != p.stale_sq_io,
-                  "critic_fit_iter_multi: replicas %d and %d share theta, sync_ws or stale_sq_io", q, r);
+    if (int rc = spo::same_shape(NAME, reps_host, r)) return rc;
+    if (int rc = spo::distinct(NAME, reps_host, r)) return rc;
+    n_active += p.active ? 1 : 0;
   }
-  int n_active = 0;
-  for (int r = 0; r < n_replicas; ++r) n_active += reps_host[r].active ? 1 : 0;
   if (n_active == 0) return 0;                                             // (nothing to enqueue: no HIP call at all)
   hipStream_t st = (hipStream_t)stream;
-  if (stream_is_capturing(st))
+  if (spo::stream_is_capturing(st))
     return spo::fail(-1, "critic_fit_iter_multi: the stream is under capture (the argument table is copied from host memory at "
                          "every call: not a graph node)");
-  const int force_safe = rs_force_safe();
+  const int force_safe = spo::env_flag("SPO_RS_SAFE");
   std::lock_guard<std::mutex> lk(g_rs_mu);                                 // (until the table's copy and its event are enqueued)
-  char* base = nullptr;
-  unsigned tag_base = 0;
-  RsMultiEntry* tab = nullptr;
-  hipEvent_t tab_ev = nullptr;
-  if (int rc = rsm_scratch(g_rsm_critic, st, &base, &tag_base, (unsigned)nsteps, &tab, &tab_ev)) return rc;
+  decltype(g_rsm_critic)::Slot sl{};
+  if (int rc = g_rsm_critic.acquire(st, (unsigned)nsteps, &sl)) return rc;
   for (int r = 0; r < n_replicas; ++r) {
     const spo_critic_fit_replica& p = reps_host[r];
-    RsArgs a{};                                                            // (as rs_update_launch fills it for spo_critic_fit_iter)
-    a.theta = p.theta; a.adam_m = p.adam_m; a.adam_v = p.adam_v;
-    a.obs = p.obs; a.tgt_r = p.target_r; a.tgt_c = p.target_c;
-    a.perm = p.perm; a.M = M; a.cfg = p.cfg; a.losses = p.losses_out;
-    a.zbuf = reinterpret_cast<float*>(base + (size_t)r * RSM_CRITIC.z_bytes);
-    a.gran = reinterpret_cast<unsigned long long*>(base + RSM_CRITIC.g_off() + (size_t)r * RSM_G_STRIDE);
-    a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(p.sync_ws) + 64);
-    a.pow_b1 = pow((double)p.cfg.beta1, (double)p.adam_step);
-    a.pow_b2 = pow((double)p.cfg.beta2, (double)p.adam_step);
-    a.tag_base = tag_base;
-    a.n_nets = 2; a.first_net = 0; a.stale_io = p.stale_sq_io; a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
+    RsArgs a{};
+    spo::fill_run(a, p.theta, p.adam_m, p.adam_v, p.adam_step, p.obs, nullptr, nullptr, p.target_r, p.target_c, nullptr, p.perm, M, p.cfg,
+                  2, 0, p.stale_sq_io, p.losses_out, p.sync_ws);
+    a.zbuf = reinterpret_cast<float*>(sl.base + (size_t)r * RSM_CRITIC.z_bytes);
+    a.gran = reinterpret_cast<unsigned long long*>(sl.base + RSM_CRITIC.g_off() + (size_t)r * RSM_G_STRIDE);
+    a.tag_base = sl.tag_base;
+    a.force_safe = force_safe; a.prof = nullptr; a.prof_wg = -1;
     a.clip_thr_sq = rs_clip_threshold(p.cfg.max_grad_norm);
-    tab[r].a = a;
-    tab[r].active = p.active ? 1 : 0;
+    sl.tab_host[r].a = a;
+    sl.tab_host[r].active = p.active ? 1 : 0;
     // what spo_critic_fit_iter does to sync_ws at every call
     if (p.active)
       if (int rc = spo::hip_check(hipMemsetAsync(p.sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
   }
-  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(base + RSM_CRITIC.t_off());
-  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab, (size_t)n_replicas * sizeof(RsMultiEntry), hipMemcpyHostToDevice, st),
-                              "hipMemcpyAsync(replica table)")) return rc;
-  if (int rc = spo::hip_check(hipEventRecord(tab_ev, st), "hipEventRecord(replica table)")) return rc;
+  RsMultiEntry* const table_dev = reinterpret_cast<RsMultiEntry*>(sl.base + RSM_CRITIC.t_off());
+  if (int rc = spo::upload_table(table_dev, sl.tab_host, n_replicas, sl.ev, st, "replica table")) return rc;
   // every slot starts as the sentinel (a launch leaves them that way unless it stopped on an error)
-  if (int rc = spo::hip_check(hipMemsetAsync(base, 0xFF, (size_t)n_replicas * RSM_CRITIC.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
+  if (int rc = spo::hip_check(hipMemsetAsync(sl.base, 0xFF, (size_t)n_replicas * RSM_CRITIC.z_bytes, st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = c0.obs_dim <= 16 ? 16 : c0.obs_dim <= 32 ? 32 : 64;
   int rc = kin == 16 ? rs_critic_multi_launch_k<16>(table_dev, n_replicas, st)
          : kin == 32 ? rs_critic_multi_launch_k<32>(table_dev, n_replicas, st)

@@ -79,6 +79,64 @@ class _EngineGroup:
         """Context of run i's random-number state (a no-op context without rngs)."""
         return self.rngs[i] if self.rngs is not None else contextlib.nullcontext()
 
+    def _adopt(self, name, engines, rngs, base, check_type):
+        """The constructor checks both groups share, `name` as the message prefix: per engine check_type(i, e) and world size 1
+        (engines of class `base` only: anything else with its methods -- a recording stand-in in a test -- is stepped one by
+        one), one shape and device, one ReplicaRNG per engine."""
+        e0 = engines[0]
+        for i, e in enumerate(engines):
+            if isinstance(e, base):
+                check_type(i, e)
+                if e.comm.world_size != 1:
+                    raise _abi.SpoError(f"{name}: data-parallel engines cannot be grouped (world size 1 only)")
+            if (e.D, e.A, e.M) != (e0.D, e0.A, e0.M) or e.dev != e0.dev:
+                raise _abi.SpoError(f"{name}: engine {i} has obs / act / rows / device {e.D} / {e.A} / {e.M} / {e.dev}, "
+                                    f"engine 0 has {e0.D} / {e0.A} / {e0.M} / {e0.dev}")
+        if rngs is not None and len(rngs) != len(engines):
+            raise ValueError(f"{name}: one ReplicaRNG per engine")
+        self.engines, self.rngs = engines, rngs
+        self._native = all(isinstance(e, base) for e in engines)
+        self.lib = _abi.load() if self._native else None
+
+    def _default_perm_fns(self, perm_fns, who=""):
+        """perm_fns with every None replaced by the run's default shuffle, drawn under its ReplicaRNG."""
+        es, S = self.engines, len(self.engines)
+
+        def default_perm_fn(i):
+            def fn(it):
+                with self.rng(i):
+                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
+            return fn
+
+        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
+        if len(perm_fns) != S:
+            raise ValueError(f"{who}one perm_fn (or None) per engine")
+        return [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+
+    def _flags(self, who, perms, active):
+        """The active flags of one launch as a list of bools (default: every run), one perm and one flag per engine."""
+        S = len(self.engines)
+        active = [True] * S if active is None else [bool(x) for x in active]
+        if len(perms) != S or len(active) != S:
+            raise ValueError(f"{who}: one perm and one active flag per engine")
+        return active
+
+    def _perm_and_losses(self, i, perms, active, n_mb, nan_fill=False):
+        """Run i's shuffle and its loss rows [n_mb, 3] for one launch -- (None, None) for a run that sits out: it still names
+        its own arrays (the table is validated as a whole), but nothing of it is touched."""
+        if not active[i] or perms[i] is None:
+            return None, None
+        dev = self.engines[i].dev
+        return (_abi.require_gpu_tensor(perms[i], "perm", torch.int32),
+                torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=dev) if nan_fill
+                else torch.empty((n_mb, 3), dtype=torch.float32, device=dev))
+
+    @staticmethod
+    def _loss_dict(ls, keys=("loss_r", "loss_c")):
+        """A run's per-launch loss rows as the result dict's means (NaN without a launch) and the rows themselves."""
+        means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * len(keys)
+        return {**dict(zip(keys, means)), "losses": ls}
+
     def check_sync_error(self) -> None:
         """The engine's check_sync_error per run (every run has its own error word); the message names the run."""
         es = self.engines
@@ -108,32 +166,22 @@ class PPOLagEngineGroup(_EngineGroup):
         engines = list(engines)
         if not engines:
             raise ValueError("PPOLagEngineGroup: no engines")
-        e0 = engines[0]
         # the feature-split form: every engine a WidePPOLagEngine on that kernel (mixed groups are refused below)
         self._ks = all(type(e) is WidePPOLagEngine for e in engines)
-        for i, e in enumerate(engines):
-            if isinstance(e, PPOLagEngine):
-                if self._ks:
-                    if e.comm.world_size != 1:
-                        raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
-                    if not e._feature_split_kernel_ok(e._cfg_struct()):
-                        raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a WidePPOLagEngine outside the feature-split kernel "
-                                            "(hidden [64, 64], obs_dim <= 512, act_dim <= 32, batch <= 64, SPO_WIDE_KS not 0); "
-                                            "only those wide engines can be grouped")
-                elif type(e) is not PPOLagEngine:
-                    raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
-                                        "PPOLagEngine (hidden [64, 64], obs_dim <= 128, act_dim <= 16) can be grouped")
+
+        def check_type(i, e):
+            if self._ks:
                 if e.comm.world_size != 1:
                     raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
-            if (e.D, e.A, e.M) != (e0.D, e0.A, e0.M) or e.dev != e0.dev:
-                raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} has obs / act / rows / device {e.D} / {e.A} / {e.M} / {e.dev}, "
-                                    f"engine 0 has {e0.D} / {e0.A} / {e0.M} / {e0.dev}")
-        if rngs is not None and len(rngs) != len(engines):
-            raise ValueError("PPOLagEngineGroup: one ReplicaRNG per engine")
-        self.engines, self.rngs = engines, rngs
-        # (anything else that has PPOLagEngine's methods -- a recording stand-in in a test -- is stepped one by one)
-        self._native = all(isinstance(e, PPOLagEngine) for e in engines)
-        self.lib = _abi.load() if self._native else None
+                if not e._feature_split_kernel_ok(e._cfg_struct()):
+                    raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a WidePPOLagEngine outside the feature-split kernel "
+                                        "(hidden [64, 64], obs_dim <= 512, act_dim <= 32, batch <= 64, SPO_WIDE_KS not 0); "
+                                        "only those wide engines can be grouped")
+            elif type(e) is not PPOLagEngine:
+                raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
+                                    "PPOLagEngine (hidden [64, 64], obs_dim <= 128, act_dim <= 16) can be grouped")
+
+        self._adopt("PPOLagEngineGroup", engines, rngs, PPOLagEngine, check_type)
 
     # ------------------------------------------------------------------ one learning iteration of every active run
     def batched(self, cfgs=None) -> bool:
@@ -161,21 +209,17 @@ class PPOLagEngineGroup(_EngineGroup):
         return (all(e._feature_split_kernel_ok(c) for e, c in zip(self.engines, cfgs))
                 and bool(self.lib.spo_update_ks_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))))
 
-    def _ks_launch(self, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill):
-        """One spo_update_iter_ex_ks_multi launch for the active runs; the clocks advance as WidePPOLagEngine.learning_iter /
-        learning_iter_ex advance them."""
+    def _launch_ex(self, entry, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill=True):
+        """One launch of `entry` (spo_update_iter_ex_multi or spo_update_iter_ex_ks_multi) for the active runs; the clocks
+        advance as learning_iter_ex advances them.  nan_fill=False: the feature-split PPO-Lagrangian step -- loss rows left
+        uninitialised and the actor on the critics' clock, as WidePPOLagEngine.learning_iter launches it."""
         S, e0 = len(self.engines), self.engines[0]
         n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
         reps = (_abi.UpdateExReplica * S)()
         losses = [None] * S
         for i, e in enumerate(self.engines):
             d = e.buffer.data
-            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
-            perm = perms[i] if active[i] else None
-            if perm is not None:
-                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
-                losses[i] = (torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=e.dev) if nan_fill
-                             else torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev))
+            perm, losses[i] = self._perm_and_losses(i, perms, active, n_mb, nan_fill)
             adv = _abi.require_gpu_tensor(advs[i], "adv", torch.float32)
             r = reps[i]
             r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
@@ -185,8 +229,7 @@ class PPOLagEngineGroup(_EngineGroup):
             r.perm, r.old_mean, r.old_std = _abi.ptr(perm), _abi.ptr(e.mean_old), _abi.ptr(e.std_old)
             r.kl_bound, r.pg_coef, r.losses_out = float(kl_bounds[i]), float(pg_coefs[i]), _abi.ptr(losses[i])
             r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
-        _abi.check(self.lib.spo_update_iter_ex_ks_multi(reps, S, e0.M, int(actor_loss), int(bool(actor_only)), _abi.stream_ptr()),
-                   "spo_update_iter_ex_ks_multi")
+        _abi.check(getattr(self.lib, entry)(reps, S, e0.M, int(actor_loss), int(bool(actor_only)), _abi.stream_ptr()), entry)
         for i, e in enumerate(self.engines):
             if active[i]:
                 if actor_only:
@@ -200,27 +243,21 @@ class PPOLagEngineGroup(_EngineGroup):
         spo_ppo_lag_update_iter_multi launch where batched(), else one launch per run -- the same results.  Returns the
         per-minibatch losses [n_mb, 3] per run (None for a run that did not take part)."""
         S = len(self.engines)
-        active = [True] * S if active is None else [bool(x) for x in active]
-        if len(perms) != S or len(active) != S:
-            raise ValueError("learning_iter_all: one perm and one active flag per engine")
+        active = self._flags("learning_iter_all", perms, active)
         cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
         if not self.batched(cfgs):
             return [e.learning_iter(perms[i]) if active[i] else None for i, e in enumerate(self.engines)]
         if self._ks:
             # spo_ppo_lag_update_iter_ks is spo_update_iter_ex_ks with the clipped surrogate on adv_mix and equal clocks
-            return self._ks_launch(cfgs, perms, [e.buffer.adv_mix for e in self.engines], _abi.ACTOR_LOSS_CLIP,
-                                   [float("inf")] * S, [0.0] * S, False, active, nan_fill=False)
+            return self._launch_ex("spo_update_iter_ex_ks_multi", cfgs, perms, [e.buffer.adv_mix for e in self.engines],
+                                   _abi.ACTOR_LOSS_CLIP, [float("inf")] * S, [0.0] * S, False, active, nan_fill=False)
         e0 = self.engines[0]
         n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
         reps = (_abi.UpdateReplica * S)()
         losses = [None] * S
         for i, e in enumerate(self.engines):
             d, b = e.buffer.data, e.buffer
-            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
-            perm = perms[i] if active[i] else None
-            if perm is not None:
-                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
-                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            perm, losses[i] = self._perm_and_losses(i, perms, active, n_mb)
             r = reps[i]
             r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
             r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
@@ -253,44 +290,14 @@ class PPOLagEngineGroup(_EngineGroup):
         for e, lam in zip(es, lams):
             e.buffer.compute_gae(lam, e.comm)
             e.snapshot_old_distribution()
-
-        def default_perm_fn(i):
-            def fn(it):
-                with self.rng(i):
-                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
-            return fn
-
-        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
-        perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
-        n_its = [e.cfg["learning_iters"] for e in es]
-        active = [n > 0 for n in n_its]
-        perms = [perm_fns[i](0) if active[i] else None for i in range(S)]
-        all_losses = [[] for _ in range(S)]
-        stop_iter, kl = [0] * S, [1.0] * S
-        it = 0
-        while any(active):
-            idx = [i for i in range(S) if active[i]]
-            losses = self.learning_iter_all(perms, active)
-            for i in idx:
-                all_losses[i].append(losses[i])
-                es[i].kl_launch()
-            for i in idx:
-                perms[i] = perm_fns[i](it + 1) if it + 1 < n_its[i] else None
-            for i, v in zip(idx, self._read_kls(idx)):
-                kl[i] = v
-                stop_iter[i] += 1
-                if v > es[i].cfg["target_kl"] or it + 1 >= n_its[i]:
-                    active[i] = False
-            it += 1
+        all_losses, stop_iter, kl = self._kl_stopped_loop_all(self._default_perm_fns(perm_fns), [0] * S, self.learning_iter_all,
+                                                              draw_ahead=True)
         self.check_sync_error()
         outs = []
         for i, e in enumerate(es):
             e.buffer.reset()
-            means = torch.cat(all_losses[i], 0).mean(0).tolist() if all_losses[i] else [float("nan")] * 3
-            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2],
-                         "losses": all_losses[i]})
+            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], **self._loss_dict(all_losses[i], ("loss_r", "loss_c", "loss_pi"))})
         return outs
-
 
     # ------------------------------------------------------------------ FOCOPS / CUP: spo_update_iter_ex of every active run
     def batched_ex(self, actor_loss: int, cfgs=None) -> bool:
@@ -325,69 +332,33 @@ class PPOLagEngineGroup(_EngineGroup):
         if not self.batched_ex(actor_loss, cfgs):
             return [e.learning_iter_ex(perms[i], advs[i], actor_loss, kl_bounds[i], pg_coefs[i], actor_only) if active[i] else None
                     for i, e in enumerate(self.engines)]
-        if self._ks:
-            return self._ks_launch(cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill=True)
-        e0 = self.engines[0]
-        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
-        reps = (_abi.UpdateExReplica * S)()
-        losses = [None] * S
-        for i, e in enumerate(self.engines):
-            d = e.buffer.data
-            # (a run that sits out still names its own arrays -- the table is validated as a whole -- but nothing of it is touched)
-            perm = perms[i] if active[i] else None
-            if perm is not None:
-                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
-                losses[i] = torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=e.dev)
-            adv = _abi.require_gpu_tensor(advs[i], "adv", torch.float32)
-            r = reps[i]
-            r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
-            r.adam_step_critics, r.adam_step_actor = e.adam_step, e.adam_step + e.adam_step_actor_extra
-            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
-            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(adv)
-            r.perm, r.old_mean, r.old_std = _abi.ptr(perm), _abi.ptr(e.mean_old), _abi.ptr(e.std_old)
-            r.kl_bound, r.pg_coef, r.losses_out = float(kl_bounds[i]), float(pg_coefs[i]), _abi.ptr(losses[i])
-            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
-        _abi.check(self.lib.spo_update_iter_ex_multi(reps, S, e0.M, int(actor_loss), int(bool(actor_only)), _abi.stream_ptr()),
-                   "spo_update_iter_ex_multi")
-        for i, e in enumerate(self.engines):
-            if active[i]:
-                if actor_only:
-                    e.adam_step_actor_extra += n_mb
-                else:
-                    e.adam_step += n_mb
-        return losses
+        entry = "spo_update_iter_ex_ks_multi" if self._ks else "spo_update_iter_ex_multi"
+        return self._launch_ex(entry, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active)
 
-    def _default_perm_fns(self, perm_fns):
-        es, S = self.engines, len(self.engines)
-
-        def default_perm_fn(i):
-            def fn(it):
-                with self.rng(i):
-                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
-            return fn
-
-        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
-        if len(perm_fns) != S:
-            raise ValueError("one perm_fn (or None) per engine")
-        return [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
-
-    def _kl_stopped_loop_all(self, perm_fns, it0s, launch):
+    def _kl_stopped_loop_all(self, perm_fns, it0s, launch, draw_ahead=False):
         """PPOLagEngine._kl_stopped_loop for every run, one `launch(perms, active)` per pass: run i draws the shuffle
         perm_fns[i](it0s[i] + it) at the start of pass `it` and none after it stopped (its own target_kl, its own learning_iters);
         a run that stopped sits out the later launches.  The KLs of a pass are read in one host read.
+        draw_ahead: PPOLagEngine.update's order instead -- pass 0's shuffle before the loop, and the next pass's shuffle of every
+        run that took part (and has iterations left) BEFORE the pass's KLs are read, so also on the pass whose KL stops the run.
         Returns (losses, stop_iter, kl), each a list over the runs."""
         es, S = self.engines, len(self.engines)
         n_its = [e.cfg["learning_iters"] for e in es]
         active = [n > 0 for n in n_its]
         all_losses, stop_iter, kl = [[] for _ in range(S)], [0] * S, [1.0] * S
+        perms = [perm_fns[i](it0s[i]) if active[i] else None for i in range(S)] if draw_ahead else None
         it = 0
         while any(active):
             idx = [i for i in range(S) if active[i]]
-            perms = [perm_fns[i](it0s[i] + it) if active[i] else None for i in range(S)]
+            if not draw_ahead:
+                perms = [perm_fns[i](it0s[i] + it) if active[i] else None for i in range(S)]
             losses = launch(perms, list(active))
             for i in idx:
                 all_losses[i].append(losses[i])
                 es[i].kl_launch()
+            if draw_ahead:
+                for i in idx:
+                    perms[i] = perm_fns[i](it0s[i] + it + 1) if it + 1 < n_its[i] else None
             for i, v in zip(idx, self._read_kls(idx)):
                 kl[i] = v
                 stop_iter[i] += 1
@@ -414,9 +385,7 @@ class PPOLagEngineGroup(_EngineGroup):
         outs = []
         for i, e in enumerate(es):
             e.buffer.reset()
-            means = torch.cat(losses[i], 0).mean(0).tolist()
-            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2],
-                         "losses": losses[i]})
+            outs.append({"stop_iter": stop_iter[i], "kl": kl[i], **self._loss_dict(losses[i], ("loss_r", "loss_c", "loss_pi"))})
         return outs
 
     def update_cup(self, lams, perm_fns=None, cup_lambda: float = 0.95):
@@ -445,10 +414,8 @@ class PPOLagEngineGroup(_EngineGroup):
         outs = []
         for i, e in enumerate(es):
             e.buffer.reset()
-            means = torch.cat(losses[i], 0).mean(0).tolist()
             outs.append({"stop_iter": stop_iter[i], "second_stage_stop_iter": stop_iter2[i], "kl": kl2[i], "kl_first_stage": kl[i],
-                         "loss_r": means[0], "loss_c": means[1], "loss_pi": means[2], "losses": losses[i],
-                         "second_stage_losses": losses2[i]})
+                         **self._loss_dict(losses[i], ("loss_r", "loss_c", "loss_pi")), "second_stage_losses": losses2[i]})
         return outs
 
 
@@ -492,25 +459,13 @@ class CPOEngineGroup(_EngineGroup):
             cap = _abi.CRITIC_SPLIT_MAX_REPLICAS if takes_split(engines[0]) else _abi.RS_CRITIC_MAX_REPLICAS
         if len(engines) > cap:
             raise _abi.SpoError(f"CPOEngineGroup: {len(engines)} engines; at most {cap} critic fits share a launch")
-        e0 = engines[0]
-        for i, e in enumerate(engines):
-            if isinstance(e, CPOEngine):
-                if takes_split(e) or takes_ks(e):
-                    pass
-                elif type(e) is not CPOEngine:
-                    raise _abi.SpoError(f"CPOEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
-                                        "CPOEngine (hidden [64, 64], obs_dim <= 64, act_dim <= 16) can be grouped")
-                if e.comm.world_size != 1:
-                    raise _abi.SpoError("CPOEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
-            if (e.D, e.A, e.M) != (e0.D, e0.A, e0.M) or e.dev != e0.dev:
-                raise _abi.SpoError(f"CPOEngineGroup: engine {i} has obs / act / rows / device {e.D} / {e.A} / {e.M} / {e.dev}, "
-                                    f"engine 0 has {e0.D} / {e0.A} / {e0.M} / {e0.dev}")
-        if rngs is not None and len(rngs) != len(engines):
-            raise ValueError("CPOEngineGroup: one ReplicaRNG per engine")
-        self.engines, self.rngs = engines, rngs
-        # (anything else that has CPOEngine's critic_fit -- a recording stand-in in a test -- is fitted one by one)
-        self._native = all(isinstance(e, CPOEngine) for e in engines)
-        self.lib = _abi.load() if self._native else None
+
+        def check_type(i, e):
+            if not (takes_split(e) or takes_ks(e)) and type(e) is not CPOEngine:
+                raise _abi.SpoError(f"CPOEngineGroup: engine {i} is a {type(e).__name__}; only the persistent-kernel "
+                                    "CPOEngine (hidden [64, 64], obs_dim <= 64, act_dim <= 16) can be grouped")
+
+        self._adopt("CPOEngineGroup", engines, rngs, CPOEngine, check_type)
 
     def batched(self, cfgs=None) -> bool:
         """Does critic_fit_all run one launch per iteration?  Where the four-row-group row-split kernel is the stand-alone
@@ -527,34 +482,57 @@ class CPOEngineGroup(_EngineGroup):
             return False
         return all(e._split_setup() is None for e in self.engines)
 
-    def fit_iter_all(self, perms, active=None):
-        """One critic-fit iteration (ceil(M / batch) minibatch steps) of every run i with active[i] in ONE launch; adam_step
-        advances per run.  Returns the losses [n_mb, 3] per run (columns 0, 1 are written; None for a run that sat out)."""
-        S = len(self.engines)
-        active = [True] * S if active is None else [bool(x) for x in active]
-        if len(perms) != S or len(active) != S:
-            raise ValueError("fit_iter_all: one perm and one active flag per engine")
+    def _fit_iter(self, entry, who, perms, active):
+        """One launch of `entry` (spo_critic_fit_iter_multi or spo_critic_fit_iter_ks_multi: one table type) for the active runs."""
+        S, e0 = len(self.engines), self.engines[0]
+        active = self._flags(who, perms, active)
         cfgs = [e._cfg_struct() for e in self.engines]
-        e0 = self.engines[0]
         n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
         reps = (_abi.CriticFitReplica * S)()
         losses = [None] * S
         for i, e in enumerate(self.engines):
             d = e.buffer.data
-            perm = perms[i] if active[i] else None
-            if perm is not None:
-                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
-                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            perm, losses[i] = self._perm_and_losses(i, perms, active, n_mb)
             r = reps[i]
             r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
             r.obs, r.target_r, r.target_c = _abi.ptr(d["obs"]), _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"])
             r.perm, r.losses_out, r.stale_sq_io = _abi.ptr(perm), _abi.ptr(losses[i]), _abi.ptr(e.stale_sq)
             r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
-        _abi.check(self.lib.spo_critic_fit_iter_multi(reps, S, e0.M, _abi.stream_ptr()), "spo_critic_fit_iter_multi")
+        _abi.check(getattr(self.lib, entry)(reps, S, e0.M, _abi.stream_ptr()), entry)
         for i, e in enumerate(self.engines):
             if active[i]:
                 e.adam_step += n_mb
         return losses
+
+    def fit_iter_all(self, perms, active=None):
+        """One critic-fit iteration (ceil(M / batch) minibatch steps) of every run i with active[i] in ONE launch; adam_step
+        advances per run.  Returns the losses [n_mb, 3] per run (columns 0, 1 are written; None for a run that sat out)."""
+        return self._fit_iter("spo_critic_fit_iter_multi", "fit_iter_all", perms, active)
+
+    def _fit_loop(self, perm_fns, fit_iter):
+        """learning_iters iterations per run (a run with fewer sits out the later launches), one fit_iter(perms, active) each,
+        every iteration's shuffle drawn before its launch.  Returns the critics' loss columns per run and iteration."""
+        S = len(self.engines)
+        n_its = [e.cfg["learning_iters"] for e in self.engines]
+        all_losses = [[] for _ in range(S)]
+        for it in range(max(n_its)):
+            active = [it < n for n in n_its]
+            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
+            losses = fit_iter(perms, active)
+            for i in range(S):
+                if active[i]:
+                    all_losses[i].append(losses[i][:, :2])
+        return all_losses
+
+    def _backup(self):
+        """Every run's critics, moments, stale norm and adam_step before a critic fit that restores them on an exchange error."""
+        return [(e.policy.theta.clone(), e.adam_m.clone(), e.adam_v.clone(), e.stale_sq.clone(), e.adam_step) for e in self.engines]
+
+    def _restore(self, backups) -> None:
+        for e, b in zip(self.engines, backups):
+            e.sync_ws[8] = 0
+            e.policy.theta.copy_(b[0]); e.adam_m.copy_(b[1]); e.adam_v.copy_(b[2]); e.stale_sq.copy_(b[3])
+            e.adam_step = b[4]
 
     # ------------------------------------------------------------------ the two-replica split form (65-128 observations)
     def batched_split(self) -> bool:
@@ -585,11 +563,8 @@ class CPOEngineGroup(_EngineGroup):
         """One iteration of CPOEngine._critic_fit_split's loop for every run i with active[i] in ONE launch: the shuffle cut
         into its 64-column halves, both replicas stepped, the run's step tag and adam_step advanced.  Returns (l0 + l1) * 0.5
         per run ([n_mb, 3], columns 0 and 1 are written; None for a run that sat out)."""
-        S = len(self.engines)
-        active = [True] * S if active is None else [bool(x) for x in active]
-        if len(perms) != S or len(active) != S:
-            raise ValueError("fit_iter_split_all: one perm and one active flag per engine")
-        e0 = self.engines[0]
+        S, e0 = len(self.engines), self.engines[0]
+        active = self._flags("fit_iter_split_all", perms, active)
         n_mb, half = e0.M // 128, e0.M // 2
         reps = (_abi.CriticFitSplitReplica * S)()
         halves = [None] * S
@@ -629,37 +604,23 @@ class CPOEngineGroup(_EngineGroup):
         restored and the error raised, naming the run."""
         es, S = self.engines, len(self.engines)
         sts = [e._split_setup() for e in es]
-        backups = [(e.policy.theta.clone(), e.adam_m.clone(), e.adam_v.clone(), e.stale_sq.clone(), e.adam_step) for e in es]
+        backups = self._backup()
         for e, st in zip(es, sts):                      # the second replica starts as a copy of the first
             st["theta1"].copy_(e.policy.theta); st["m1"].copy_(e.adam_m); st["v1"].copy_(e.adam_v); st["stale1"].copy_(e.stale_sq)
-        n_its = [e.cfg["learning_iters"] for e in es]
-        all_losses = [[] for _ in range(S)]
-        for it in range(max(n_its)):
-            active = [it < n for n in n_its]
-            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
-            losses = self.fit_iter_split_all(perms, active)
-            for i in range(S):
-                if active[i]:
-                    all_losses[i].append(losses[i][:, :2])
+        all_losses = self._fit_loop(perm_fns, self.fit_iter_split_all)
         # WideCPOEngine.check_sync_error is a no-op: both error words of every run, one host read
         words = [e.sync_ws[8] for e in es] + [st["sync_ws"][8] for st in sts]
         codes = [int(c) & 0xFFFFFFFF for c in torch.stack([w.to(torch.int64) for w in words]).cpu().tolist()]
         bad = [i for i in range(S) if codes[i] | codes[S + i]]
         if bad:
-            for e, st, b in zip(es, sts, backups):
-                e.sync_ws[8] = 0
+            for st in sts:
                 st["sync_ws"][8] = 0
-                e.policy.theta.copy_(b[0]); e.adam_m.copy_(b[1]); e.adam_v.copy_(b[2]); e.stale_sq.copy_(b[3])
-                e.adam_step = b[4]
+            self._restore(backups)
             i = bad[0]
             raise _abi.SpoError(f"replica {i} of {S}: split critic fit: exchange error {codes[i] | codes[S + i]} (the workgroups of "
                                 "the seed-batched launch were not all resident); every run's critics, moments and stale norm are "
                                 "restored to the start of this critic fit")
-        outs = []
-        for ls in all_losses:
-            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
-            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
-        return outs
+        return [self._loss_dict(ls) for ls in all_losses]
 
     # ------------------------------------------------------------------ the feature-split form (129-512 observations)
     def batched_ks(self) -> bool:
@@ -684,31 +645,7 @@ class CPOEngineGroup(_EngineGroup):
         """One iteration of WideCPOEngine.critic_fit's feature-split loop for every run i with active[i] in ONE launch;
         adam_step advances per run.  Returns the losses [n_mb, 3] per run (columns 0, 1 are written; None for a run that sat
         out)."""
-        S = len(self.engines)
-        active = [True] * S if active is None else [bool(x) for x in active]
-        if len(perms) != S or len(active) != S:
-            raise ValueError("fit_iter_ks_all: one perm and one active flag per engine")
-        cfgs = [e._cfg_struct() for e in self.engines]
-        e0 = self.engines[0]
-        n_mb = (e0.M + cfgs[0].batch - 1) // cfgs[0].batch
-        reps = (_abi.CriticFitReplica * S)()
-        losses = [None] * S
-        for i, e in enumerate(self.engines):
-            d = e.buffer.data
-            perm = perms[i] if active[i] else None
-            if perm is not None:
-                perm = _abi.require_gpu_tensor(perm, "perm", torch.int32)
-                losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
-            r = reps[i]
-            r.theta, r.adam_m, r.adam_v, r.adam_step = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v), e.adam_step
-            r.obs, r.target_r, r.target_c = _abi.ptr(d["obs"]), _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"])
-            r.perm, r.losses_out, r.stale_sq_io = _abi.ptr(perm), _abi.ptr(losses[i]), _abi.ptr(e.stale_sq)
-            r.sync_ws, r.cfg, r.active = _abi.ptr(e.sync_ws), cfgs[i], int(active[i])
-        _abi.check(self.lib.spo_critic_fit_iter_ks_multi(reps, S, e0.M, _abi.stream_ptr()), "spo_critic_fit_iter_ks_multi")
-        for i, e in enumerate(self.engines):
-            if active[i]:
-                e.adam_step += n_mb
-        return losses
+        return self._fit_iter("spo_critic_fit_iter_ks_multi", "fit_iter_ks_all", perms, active)
 
     def _critic_fit_all_ks(self, perm_fns):
         """critic_fit_all where batched_ks(): the feature-split loop of WideCPOEngine.critic_fit for every run, one launch per
@@ -717,23 +654,12 @@ class CPOEngineGroup(_EngineGroup):
         moments, stale norm and adam_step are restored to the start of this critic fit (the stale vector has not been touched
         yet) and the error raised, naming the run."""
         es, S = self.engines, len(self.engines)
-        backups = [(e.policy.theta.clone(), e.adam_m.clone(), e.adam_v.clone(), e.stale_sq.clone(), e.adam_step) for e in es]
-        n_its = [e.cfg["learning_iters"] for e in es]
-        all_losses = [[] for _ in range(S)]
-        for it in range(max(n_its)):
-            active = [it < n for n in n_its]
-            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
-            losses = self.fit_iter_ks_all(perms, active)
-            for i in range(S):
-                if active[i]:
-                    all_losses[i].append(losses[i][:, :2])
+        backups = self._backup()
+        all_losses = self._fit_loop(perm_fns, self.fit_iter_ks_all)
         codes = [int(c) & 0xFFFFFFFF for c in torch.stack([e.sync_ws[8].to(torch.int64) for e in es]).cpu().tolist()]
         bad = [i for i in range(S) if codes[i]]
         if bad:
-            for e, b in zip(es, backups):
-                e.sync_ws[8] = 0
-                e.policy.theta.copy_(b[0]); e.adam_m.copy_(b[1]); e.adam_v.copy_(b[2]); e.stale_sq.copy_(b[3])
-                e.adam_step = b[4]
+            self._restore(backups)
             i = bad[0]
             raise _abi.SpoError(f"replica {i} of {S}: feature-split critic fit: exchange error {codes[i]} (the inter-workgroup "
                                 "exchange of the seed-batched launch timed out); every run's critics, moments and stale norm are "
@@ -741,8 +667,7 @@ class CPOEngineGroup(_EngineGroup):
         outs = []
         for e, b, ls in zip(es, backups, all_losses):
             e.flat_grad[e.ls_off:].mul_(torch.sqrt(e.stale_sq / b[3].clamp_min(1e-38)))
-            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
-            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
+            outs.append(self._loss_dict(ls))
         return outs
 
     def critic_fit_all(self, perm_fns=None):
@@ -752,36 +677,13 @@ class CPOEngineGroup(_EngineGroup):
         two-replica split form.  Where batched_ks() (a ks_form group at 129-512 observations): the same loop on the
         feature-split kernel.  Where none of them: each engine's own critic_fit, one after the other -- the same results.
         Returns the list of critic_fit()'s dicts."""
-        es, S = self.engines, len(self.engines)
-
-        def default_perm_fn(i):
-            def fn(it):
-                with self.rng(i):
-                    return torch.randperm(es[i].M, device=es[i].dev).to(torch.int32)
-            return fn
-
-        perm_fns = [None] * S if perm_fns is None else list(perm_fns)
-        if len(perm_fns) != S:
-            raise ValueError("critic_fit_all: one perm_fn (or None) per engine")
-        perm_fns = [f if f is not None else default_perm_fn(i) for i, f in enumerate(perm_fns)]
+        perm_fns = self._default_perm_fns(perm_fns, "critic_fit_all: ")
         if self.batched_split():
             return self._critic_fit_all_split(perm_fns)
         if self.batched_ks():
             return self._critic_fit_all_ks(perm_fns)
         if not self.batched():
-            return [e.critic_fit(perm_fns[i]) for i, e in enumerate(es)]
-        n_its = [e.cfg["learning_iters"] for e in es]
-        all_losses = [[] for _ in range(S)]
-        for it in range(max(n_its)):
-            active = [it < n for n in n_its]
-            perms = [perm_fns[i](it) if active[i] else None for i in range(S)]
-            losses = self.fit_iter_all(perms, active)
-            for i in range(S):
-                if active[i]:
-                    all_losses[i].append(losses[i][:, :2])
+            return [e.critic_fit(perm_fns[i]) for i, e in enumerate(self.engines)]
+        all_losses = self._fit_loop(perm_fns, self.fit_iter_all)
         self.check_sync_error()
-        outs = []
-        for ls in all_losses:
-            means = torch.cat(ls, 0).mean(0).tolist() if ls else [float("nan")] * 2
-            outs.append({"loss_r": means[0], "loss_c": means[1], "losses": ls})
-        return outs
+        return [self._loss_dict(ls) for ls in all_losses]
