@@ -17,7 +17,7 @@ inline int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// hipFuncSetAttribute is per device: "already done" flags are kept per device ordinal (round-2 advice)
+// a kernel's dynamic-LDS limit is set per device: "already done" flags are kept per device ordinal (round-2 advice)
 constexpr int SPO_MAX_DEVICES = 64;
 inline int current_device_slot() {
   int d = 0;
@@ -41,6 +41,21 @@ inline int hip_check(hipError_t e, const char* what) {
   do {                                                            \
     if (!(cond)) return ::spo::fail(-1, __VA_ARGS__);             \
   } while (0)
+
+// Every launch with dynamic LDS of update.hip, update_rs.hip, update_ks.hip and cpo.hip: raises the kernel's limit to `sh` bytes
+// once per device (attr_done: the call site's bool[SPO_MAX_DEVICES], one per kernel; `what` names the kernel in the error message),
+// then launches with `sh` bytes.
+template <class... P, class... A>
+int launch_dyn_lds(void (*kernel)(P...), bool* attr_done, const char* what, dim3 grid, dim3 block, size_t sh, hipStream_t st, A... args) {
+  const int dslot = current_device_slot();
+  if (!attr_done[dslot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return fail((int)e, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+    attr_done[dslot] = true;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, sh, st, args...);
+  return 0;
+}
 
 // exchange scratch of the feature-split kernels (update_ks.hip), freed together with the update kernels' by spo_update_scratch_release
 int ks_scratch_release(int dev, void* stream_or_null, int all);

@@ -515,33 +515,25 @@ __global__ void sum3_kernel(const double* partials, int n, double* out) {
 
 int pick_kin(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : 64; }
 
+template <int K, int MODE>
+int launch_cpo_k(const CpoArgs& a, int blocks, hipStream_t st) {
+  static bool attr_done[spo::SPO_MAX_DEVICES] = {};
+  return spo::launch_dyn_lds(&cpo_actor_kernel<K, MODE>, attr_done, "cpo", dim3(blocks), dim3(256),
+                             CpoLds<K, MODE>::SIZE * sizeof(float), st, a);
+}
+
 template <int MODE>
 int launch_cpo(const CpoArgs& a, int blocks, hipStream_t st) {
   const int kin = pick_kin(a.D);
-#define SPO_LAUNCH(K)                                                                                  \
-  {                                                                                                    \
-    const size_t sh = CpoLds<K, MODE>::SIZE * sizeof(float);                                           \
-    static bool done_dev[spo::SPO_MAX_DEVICES] = {};        /* the attribute is per device */           \
-    bool& done = done_dev[spo::current_device_slot()];                                                 \
-    if (!done) {                                                                                       \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cpo_actor_kernel<K, MODE>),    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);         \
-      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(cpo)");                       \
-      done = true;                                                                                     \
-    }                                                                                                  \
-    hipLaunchKernelGGL((cpo_actor_kernel<K, MODE>), dim3(blocks), dim3(256), sh, st, a);               \
-  }
-  if (kin == 16) SPO_LAUNCH(16) else if (kin == 32) SPO_LAUNCH(32) else SPO_LAUNCH(64)
-  return 0;
+  return kin == 16 ? launch_cpo_k<16, MODE>(a, blocks, st) : kin == 32 ? launch_cpo_k<32, MODE>(a, blocks, st)
+                                                                       : launch_cpo_k<64, MODE>(a, blocks, st);
 }
 
 template <int MODE>
 int launch_cpo128(const CpoArgs& a, int blocks, hipStream_t st) {
   static_assert(CpoLds<128, MODE>::SIZE * sizeof(float) <= 160 * 1024, "cpo128: LDS form does not fit one workgroup");
-  SPO_LAUNCH(128)
-  return 0;
+  return launch_cpo_k<128, MODE>(a, blocks, st);
 }
-#undef SPO_LAUNCH
 
 int check(int D, int A) {
   if (D < 1 || D > 64) return spo::fail(-2, "cpo: obs_dim %d outside [1,64]", D);
@@ -1211,16 +1203,8 @@ template <int MODE, bool X4>
 int launch_cpo512_form(const CpoArgs& a, int blocks, hipStream_t st) {
   constexpr size_t sh = Cpo512Lds<MODE>::SIZE * sizeof(float);
   static_assert(sh <= 160 * 1024, "cpo512: LDS form does not fit one workgroup");
-  static bool done_dev[spo::SPO_MAX_DEVICES] = {};          // the attribute is per device
-  bool& done = done_dev[spo::current_device_slot()];
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cpo512_actor_kernel<MODE, X4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(cpo512)");
-    done = true;
-  }
-  hipLaunchKernelGGL((cpo512_actor_kernel<MODE, X4>), dim3(blocks), dim3(256), sh, st, a);
-  return 0;
+  static bool attr_done[spo::SPO_MAX_DEVICES] = {};
+  return spo::launch_dyn_lds(&cpo512_actor_kernel<MODE, X4>, attr_done, "cpo512", dim3(blocks), dim3(256), sh, st, a);
 }
 template <int MODE>
 int launch_cpo512(const CpoArgs& a, int blocks, hipStream_t st) {

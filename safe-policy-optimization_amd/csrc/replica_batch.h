@@ -1,7 +1,8 @@
 // The host side of a replica-table launch, shared by the six seed-batched entry points (update_rs.hip:
 // spo_ppo_lag_update_iter_multi, spo_critic_fit_iter_multi; update.hip: spo_update_iter_ex_multi, spo_critic_fit_iter_split_multi;
 // update_ks.hip: spo_update_iter_ex_ks_multi, spo_critic_fit_iter_ks_multi).  Host-only: no device code lives here.
-//   small helpers    stream_is_capturing, env_flag, block_map_query, upload_table, launch_dyn_lds
+//   small helpers    stream_is_capturing, env_flag, block_map_query, upload_table
+//   scratch blocks   alloc_block, free_block, ScratchForm: how the StreamTable users (stream_table.h) allocate, free and refuse
 //   ReplicaPool      the scratch block + pinned table ring of one (device, stream), one instance per form
 //   table checks     table_head, same_shape, distinct: the refusals every table type shares, worded with the entry's name
 //   fill_run / fill_run_ex  the per-run fields of RsArgs / KsArgs / UpdArgs, one copy for the stand-alone entry and the table loop
@@ -11,6 +12,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "stream_table.h"
 #include "update_rs.h"
 
 namespace spo {
@@ -51,27 +53,55 @@ int upload_table(Entry* table_dev, const Entry* table_host, int n, hipEvent_t ev
   return hip_check2(hipEventRecord(ev, st), "hipEventRecord", what);
 }
 
-// Raises the kernel's dynamic-LDS limit once per device (attr_done: the call site's bool[SPO_MAX_DEVICES]), then launches.
-template <class... P, class... A>
-int launch_dyn_lds(void (*kernel)(P...), bool* attr_done, const char* attr_what, dim3 grid, dim3 block, size_t sh, hipStream_t st, A... args) {
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return hip_check(e, attr_what);
-    attr_done[dslot] = true;
-  }
-  hipLaunchKernelGGL(kernel, grid, block, sh, st, args...);
+// ---------------------------------------------------------------------------------------------------- scratch blocks
+// hipMalloc of a scratch block: optionally zeroed, optionally with the device synchronised behind the memset.
+inline int alloc_block(size_t bytes, bool zeroed, bool synced, const char* what, char** out) {
+  void* p = nullptr;
+  if (int rc = hip_check2(hipMalloc(&p, bytes), "hipMalloc", what)) return rc;
+  int rc = zeroed ? hip_check2(hipMemset(p, 0, bytes), "hipMemset", what) : 0;
+  if (!rc && zeroed && synced) rc = hip_check2(hipDeviceSynchronize(), "hipDeviceSynchronize", what);
+  if (rc) { (void)hipFree(p); return rc; }
+  *out = static_cast<char*>(p);
   return 0;
 }
 
+// hipFree of a block that spo_update_scratch_release lets go.  An error is recorded in the message buffer and otherwise ignored:
+// the release goes on to the remaining blocks and still counts this one.
+inline void free_block(void* p, const char* what) {
+  if (p) (void)hip_check2(hipFree(p), "hipFree", what);
+}
+
+// What a single-run form says about its StreamTable (stream_table.h): the words of its two refusals and of its HIP errors, the
+// size of a block and how a new one is prepared.
+struct ScratchForm {
+  const char* name;        // "<name>: more than ..." / "<name>: first launch on a stream under capture ..."
+  const char* holds;       // "... pairs hold <holds> in this process ..."
+  const char* made;        // "... (the <made> allocated on first use ..."
+  const char* what;        // "hipMalloc(<what>)"
+  size_t bytes; bool zeroed, synced;
+
+  int refuse_full(int cap) const {
+    return fail(-1, "%s: more than %d (device, stream) pairs hold %s in this process; call spo_update_scratch_release(stream) for "
+                    "streams that are gone", name, cap, holds);
+  }
+  // the block of a pair's first launch: never under capture (allocation and memset would invalidate it)
+  int first_use(hipStream_t st, char** out) const {
+    if (stream_is_capturing(st))
+      return fail(-1, "%s: first launch on a stream under capture (the %s allocated on first use: launch once outside the capture)",
+                  name, made);
+    return alloc_block(bytes, zeroed, synced, what, out);
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------- the replica-table pool
-// One block per (device, stream), made at the pair's first launch (never under capture: the entries refuse that before) and kept
-// until spo_update_scratch_release: `bytes` of device memory (0: none -- the split critic fit sizes its own), optionally zeroed
-// with the device synchronised behind it, and a pinned host ring of RING argument tables of MAX_REPS entries, each with an event
-// recorded behind its copy.  A launch takes the next ring slot and waits for that slot's event, so the host waits only when RING
-// launches are already queued behind one another.  `Extra`: per-block state of one form (value-initialised with the block).
-// `before_free`: runs on a block that release() is about to free (counters that must outlive it).  The pool has no lock of its
-// own: the caller holds the form's mutex around acquire() and keeps it until its table copy is enqueued, and around release().
+// One block per (device, stream) in a StreamTable, made at the pair's first launch (never under capture: the entries refuse that
+// before) and kept until spo_update_scratch_release: `bytes` of device memory (0: none -- the split critic fit sizes its own),
+// optionally zeroed with the device synchronised behind it, and a pinned host ring of RING argument tables of MAX_REPS entries,
+// each with an event recorded behind its copy.  A launch takes the next ring slot and waits for that slot's event, so the host
+// waits only when RING launches are already queued behind one another.  `Extra`: per-block state of one form (value-initialised
+// with the block).  `before_free`: runs on a block that release() is about to free (counters that must outlive it).  The pool has
+// no lock of its own: the caller holds the form's mutex around acquire() and keeps it until its table copy is enqueued, and
+// around release().
 struct NoExtra {};
 template <class Entry, int MAX_REPS, int CAP, class Extra = NoExtra>
 struct ReplicaPool {
@@ -88,11 +118,10 @@ struct ReplicaPool {
   const char* full_fmt;                              // the refusal at CAP pairs (one %d)
   const char* dev_what; const char* tab_what;        // names of the device block and of the table in HIP error messages
   void (*before_free)(Block&);
-  Block e[CAP] = {};
-  int n = 0;
+  StreamTable<Block, CAP> blocks = {};
 
   void free_block(Block& b) {
-    if (b.base) (void)hip_check2(hipFree(b.base), "hipFree", dev_what);
+    spo::free_block(b.base, dev_what);
     if (b.tab_host) (void)hip_check2(hipHostFree(b.tab_host), "hipHostFree", tab_what);
     for (hipEvent_t ev : b.ev)
       if (ev) (void)hip_check2(hipEventDestroy(ev), "hipEventDestroy", tab_what);
@@ -101,30 +130,21 @@ struct ReplicaPool {
 
   int acquire(hipStream_t st, unsigned nsteps, Slot* out) {
     const int dev = current_device_slot();
-    Block* b = nullptr;
-    for (int i = 0; i < n; ++i)
-      if (e[i].dev == dev && e[i].stream == (void*)st) b = &e[i];
+    Block* b = blocks.find(dev, (void*)st);
     if (!b) {
-      if (n == CAP) return fail(-1, full_fmt, CAP);
+      if (blocks.full()) return fail(-1, full_fmt, CAP);
       Block nb{};
       nb.dev = dev; nb.stream = (void*)st; nb.tag = 16u;
+      if (bytes)
+        if (int rc = alloc_block(bytes, zeroed, zeroed, dev_what, &nb.base)) return rc;
       void* p = nullptr;
-      if (bytes) {
-        if (int rc = hip_check2(hipMalloc(&p, bytes), "hipMalloc", dev_what)) return rc;
-        nb.base = static_cast<char*>(p);
-        if (zeroed) {
-          if (int rc = hip_check2(hipMemset(p, 0, bytes), "hipMemset", dev_what)) { free_block(nb); return rc; }
-          if (int rc = hip_check2(hipDeviceSynchronize(), "hipDeviceSynchronize", dev_what)) { free_block(nb); return rc; }
-        }
-      }
       if (int rc = hip_check2(hipHostMalloc(&p, (size_t)RING * MAX_REPS * sizeof(Entry), hipHostMallocDefault), "hipHostMalloc", tab_what)) {
         free_block(nb); return rc;
       }
       nb.tab_host = static_cast<Entry*>(p);
       for (hipEvent_t& ev : nb.ev)
         if (int rc = hip_check2(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate", tab_what)) { free_block(nb); return rc; }
-      e[n] = nb;
-      b = &e[n++];
+      b = blocks.add(nb);
     }
     const unsigned slot = b->calls++ % RING;
     *out = Slot{b, b->base, b->tag, b->tab_host + (size_t)slot * MAX_REPS, b->ev[slot]};
@@ -134,17 +154,10 @@ struct ReplicaPool {
   }
 
   int release(int dev, void* stream_or_null, int all) {
-    int freed = 0;
-    for (int i = 0; i < n;) {
-      if (e[i].dev == dev && (all || e[i].stream == stream_or_null)) {
-        if (before_free) before_free(e[i]);
-        free_block(e[i]);
-        e[i] = e[--n];
-        e[n] = Block{};
-        ++freed;
-      } else ++i;
-    }
-    return freed;
+    return blocks.release(dev, stream_or_null, all, [this](Block& b) {
+      if (before_free) before_free(b);
+      free_block(b);
+    });
   }
 };
 

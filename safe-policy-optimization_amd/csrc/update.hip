@@ -3009,50 +3009,31 @@ unsigned long long* g_prof_buf = nullptr;
 struct HScratch { int dev; void* stream; int idx; char* base; };
 constexpr size_t H_BACKUP_BYTES = sizeof(float4) * UPD_BACKUP_ROWS * 3 * 512, H_SLOT_BYTES = sizeof(unsigned long long) * 32;
 constexpr int H_SCRATCH_MAX = 256;
-HScratch g_hs[H_SCRATCH_MAX];
-int g_hs_n = 0;
+constexpr spo::ScratchForm H_FORM{"update kernel", "update scratch", "scratch block is", "update scratch", H_BACKUP_BYTES + H_SLOT_BYTES,
+                                  false, false};
+spo::StreamTable<HScratch, H_SCRATCH_MAX> g_hs;
 std::mutex g_hs_mu;
 int h_scratch_for(hipStream_t st, float** backup, unsigned long long** slots, int idx = 0) {
   // idx: 0 for ordinary launches; the one-grid split form keeps a second block (idx 1) for its second rank
   const int dev = current_device_slot();
   std::lock_guard<std::mutex> lk(g_hs_mu);
-  for (int i = 0; i < g_hs_n; ++i)
-    if (g_hs[i].dev == dev && g_hs[i].stream == (void*)st && g_hs[i].idx == idx) {
-      *backup = reinterpret_cast<float*>(g_hs[i].base);
-      *slots = reinterpret_cast<unsigned long long*>(g_hs[i].base + H_BACKUP_BYTES);
-      return 0;
-    }
-  if (g_hs_n == H_SCRATCH_MAX)
-    return spo::fail(-1, "update kernel: more than %d (device, stream) pairs hold update scratch in this process; call "
-                         "spo_update_scratch_release(stream) for streams that are gone", H_SCRATCH_MAX);
-  if (spo::stream_is_capturing(st))
-    return spo::fail(-1, "update kernel: first launch on a stream under capture (the scratch block is allocated on first use: "
-                         "launch once outside the capture)");
-  void* p = nullptr;
-  if (int rc = spo::hip_check(hipMalloc(&p, H_BACKUP_BYTES + H_SLOT_BYTES), "hipMalloc(update scratch)")) return rc;
-  g_hs[g_hs_n++] = HScratch{dev, (void*)st, idx, static_cast<char*>(p)};
-  *backup = reinterpret_cast<float*>(p);
-  *slots = reinterpret_cast<unsigned long long*>(static_cast<char*>(p) + H_BACKUP_BYTES);
+  HScratch* e = g_hs.find(dev, (void*)st, idx);
+  if (!e) {
+    if (g_hs.full()) return H_FORM.refuse_full(H_SCRATCH_MAX);
+    HScratch nb{dev, (void*)st, idx, nullptr};
+    if (int rc = H_FORM.first_use(st, &nb.base)) return rc;
+    e = g_hs.add(nb);
+  }
+  *backup = reinterpret_cast<float*>(e->base);
+  *slots = reinterpret_cast<unsigned long long*>(e->base + H_BACKUP_BYTES);
   return 0;
 }
 
+// Cached pair of exchange regions + census words of the one-grid split critic fit (split_local_for below)
 struct SplitLocal { int dev; void* stream; char* base; unsigned tag; };
 constexpr int SPLIT_LOCAL_MAX = 8;
-SplitLocal g_split_local[SPLIT_LOCAL_MAX] = {};
-int g_split_local_n = 0;
+spo::StreamTable<SplitLocal, SPLIT_LOCAL_MAX> g_split_local;
 std::mutex g_split_local_mu;
-int split_local_release(int dev, void* stream_or_null, int all) {
-  std::lock_guard<std::mutex> lk(g_split_local_mu);
-  int freed = 0;
-  for (int i = 0; i < g_split_local_n;) {
-    if (g_split_local[i].dev == dev && (all || g_split_local[i].stream == stream_or_null)) {
-      (void)spo::hip_check(hipFree(g_split_local[i].base), "hipFree(split exchange)");
-      g_split_local[i] = g_split_local[--g_split_local_n];
-      ++freed;
-    } else ++i;
-  }
-  return freed;
-}
 
 // Scratch of the seed-batched four-wave launch (spo_update_iter_ex_multi), one block per (device, stream), allocated on first use
 // (never under capture) and kept: [run] clip-norm granules [2][4] on a 128-byte line of their own -- contiguous, so ONE
@@ -3153,21 +3134,21 @@ int splitm_grow(SplitMultiState& e, int n_replicas) {
 // H_SCRATCH_MAX distinct pairs launches fail).  hipFree synchronises the device: not for the hot path.
 extern "C" int spo_update_scratch_release(void* stream_or_null, int all) {
   const int dev = spo::current_device_slot();
-  std::lock_guard<std::mutex> lk(g_hs_mu);
   int freed = 0;
-  for (int i = 0; i < g_hs_n;) {
-    if (g_hs[i].dev == dev && (all || g_hs[i].stream == stream_or_null)) {
-      if (int rc = spo::hip_check(hipFree(g_hs[i].base), "hipFree(update scratch)")) return rc;
-      g_hs[i] = g_hs[--g_hs_n];
-      ++freed;
-    } else ++i;
+  // (every table under its own mutex, one after the other)
+  {
+    std::lock_guard<std::mutex> lk(g_hs_mu);
+    freed += g_hs.release(dev, stream_or_null, all, [](HScratch& b) { spo::free_block(b.base, "update scratch"); });
   }
-  freed += split_local_release(dev, stream_or_null, all);
+  {
+    std::lock_guard<std::mutex> lk(g_split_local_mu);
+    freed += g_split_local.release(dev, stream_or_null, all, [](SplitLocal& b) { spo::free_block(b.base, "split exchange"); });
+  }
   freed += spo::ks_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_scratch_release(dev, stream_or_null, all);
   freed += spo::rs_multi_scratch_release(dev, stream_or_null, all);
-  { std::lock_guard<std::mutex> lk2(g_exm_mu); freed += g_exm.release(dev, stream_or_null, all); }
-  { std::lock_guard<std::mutex> lk2(g_splitm_mu); freed += g_splitm.release(dev, stream_or_null, all); }
+  { std::lock_guard<std::mutex> lk(g_exm_mu); freed += g_exm.release(dev, stream_or_null, all); }
+  { std::lock_guard<std::mutex> lk(g_splitm_mu); freed += g_splitm.release(dev, stream_or_null, all); }
   return freed;
 }
 namespace {
@@ -3196,32 +3177,34 @@ inline int helper_xr_mode() {
   return v;
 }
 
+// SPO_UPDATE_SPEC (read once per process): the main + helper kernels' spec_mode, 1 unless set
+inline int update_spec() {
+  static const int v = [] { const char* e = getenv("SPO_UPDATE_SPEC"); return e ? atoi(e) : 1; }();
+  return v;
+}
+
 template <int K, bool PROF = false, int XR = 0, int XRD = 2>
 int launch_update_h(const UpdArgs& a_in, int blocks, hipStream_t st) {
   UpdArgs a = a_in;
   if (int rc = h_scratch_for(st, &a.backup, &a.slots)) return rc;
-  {
-    static const int spec_env = [] { const char* e = getenv("SPO_UPDATE_SPEC"); return e ? atoi(e) : 1; }();
-    a.spec_mode = spec_env;
-  }
+  a.spec_mode = update_spec();
   // [parity][network][helper wave] norm granules of this form (tags restart at 1 with every launch)
   if (int rc = spo::hip_check(hipMemsetAsync(a.slots, 0, H_SLOT_BYTES, st), "hipMemsetAsync(update scratch slots)")) return rc;
-  const size_t sh = UpdHLds<K>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_h_kernel<K, PROF, XR, XRD>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_h)");
-    attr_done[dslot] = true;
-  }
-  hipLaunchKernelGGL((ppo_update_h_kernel<K, PROF, XR, XRD>), dim3(8 * (blocks - 1) + 1), dim3(512), sh, st, a);
-  return 0;
+  return launch_dyn_lds(&ppo_update_h_kernel<K, PROF, XR, XRD>, attr_done, "update_h", dim3(8 * (blocks - 1) + 1),
+                        dim3(512), UpdHLds<K>::SIZE * sizeof(float), st, a);
 }
 
 // Does the main + helper kernel take a persistent clipped-surrogate launch without an in-kernel exchange (launch_update below;
 // spo_update_ex_multi_matches_single answers from it)?
 inline bool h_form_takes(int obs_dim, int batch) { return pick_kin(obs_dim) <= 64 && batch <= 64 && update_form() >= 2; }
+
+template <int K, bool PERSIST, bool PROF, int AMODE, int XR>
+int launch_update_k(const UpdArgs& a, int blocks, const char* attr_what, hipStream_t st) {
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  return launch_dyn_lds(&ppo_update_kernel<K, PERSIST, PROF, AMODE, XR>, attr_done, attr_what, dim3(PERSIST ? 8 * (blocks - 1) + 1 : blocks),
+                        dim3(256), UpdLds<K>::SIZE * sizeof(float), st, a);
+}
 
 template <bool PERSIST, int AMODE = 0, int XR = 0>
 int launch_update(const UpdArgs& a, int blocks, hipStream_t st) {
@@ -3232,37 +3215,19 @@ int launch_update(const UpdArgs& a, int blocks, hipStream_t st) {
     if (kin == 32) return launch_update_h<32>(a, blocks, st);
     return launch_update_h<64>(a, blocks, st);
   }
-  if (PERSIST && AMODE == 0 && a.prof && kin == 64) {
-    const size_t sh = UpdLds<64>::SIZE * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_kernel<64, true, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update prof)");
-    hipLaunchKernelGGL((ppo_update_kernel<64, true, true>), dim3(8 * (blocks - 1) + 1), dim3(256), sh, st, a);
-    return 0;
-  }
-#define SPO_LAUNCH(K)                                                                                   \
-  {                                                                                                     \
-    const size_t sh = UpdLds<K>::SIZE * sizeof(float);                                                  \
-    static bool attr_done[SPO_MAX_DEVICES] = {};                                                        \
-    const int dslot = current_device_slot();                                                            \
-    if (!attr_done[dslot]) {                                                                            \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_kernel<K, PERSIST, false, AMODE, XR>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);          \
-      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update)");                     \
-      attr_done[dslot] = true;                                                                          \
-    }                                                                                                   \
-    hipLaunchKernelGGL((ppo_update_kernel<K, PERSIST, false, AMODE, XR>), dim3(PERSIST ? 8 * (blocks - 1) + 1 : blocks), \
-                       dim3(256), sh, st, a);                                                          \
-  }
-  if (kin == 16) SPO_LAUNCH(16) else if (kin == 32) SPO_LAUNCH(32) else if (kin == 64) SPO_LAUNCH(64) else SPO_LAUNCH(128)
-#undef SPO_LAUNCH
-  return 0;
+  // the instrumented build (KIN = 64, the clipped-surrogate step without exchange), only with a profile buffer set
+  if (PERSIST && AMODE == 0 && a.prof && kin == 64) return launch_update_k<64, true, true, 0, 0>(a, blocks, "update prof", st);
+  constexpr const char* WHAT = "update";
+  return kin == 16 ? launch_update_k<16, PERSIST, false, AMODE, XR>(a, blocks, WHAT, st)
+       : kin == 32 ? launch_update_k<32, PERSIST, false, AMODE, XR>(a, blocks, WHAT, st)
+       : kin == 64 ? launch_update_k<64, PERSIST, false, AMODE, XR>(a, blocks, WHAT, st)
+                   : launch_update_k<128, PERSIST, false, AMODE, XR>(a, blocks, WHAT, st);
 }
 
 template <int K, int AMODE>
 int launch_update_multi_k(const UpdMultiEntry* table_dev, int n_replicas, int wgs, hipStream_t st) {
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  return launch_dyn_lds(&ppo_update_multi_kernel<K, AMODE>, attr_done, "hipFuncSetAttribute(update_multi)",
+  return launch_dyn_lds(&ppo_update_multi_kernel<K, AMODE>, attr_done, "update_multi",
                         dim3(rs_multi_grid(n_replicas, wgs)), dim3(256), UpdLds<K>::SIZE * sizeof(float), st, table_dev, n_replicas, wgs);
 }
 
@@ -3298,68 +3263,54 @@ extern "C" int spo_critic_fit_multi_matches_single(int obs_dim, int act_dim, int
   return (batch > 64 && rs_takes(&c, 2) && spo::rs_row_groups(obs_dim, batch) == 4) ? 1 : 0;
 }
 
+// SPO_LAUNCH_CHECK worded "<entry><suffix>: <error>", for the helpers that serve two entries
+static int launch_check(const char* entry, const char* suffix = "") {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : spo::fail((int)e, "%s%s: %s", entry, suffix, hipGetErrorString(e));
+}
+
+// spo_ppo_lag_update_iter (n_nets 3) and spo_critic_fit_iter (n_nets 2: no act / logp_old / adv; stale_sq_io; no profile buffer):
+// the refusals worded with `name`, then the row-split kernel where rs_takes, else the main + helper or the four-wave kernel.
+static int update_iter(const char* name, const char* entry, int n_nets, float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
+                       const float* obs, const float* act, const float* logp_old, const float* target_r, const float* target_c,
+                       const float* adv, const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host, float* stale_sq_io,
+                       float* losses_out, void* sync_ws, void* stream) {
+  if (int rc = check_cfg(cfg_host)) return rc;
+  SPO_REQUIRE(theta && adam_m && adam_v && obs && (n_nets == 2 || (act && logp_old && adv)) && target_r && target_c && perm &&
+                  losses_out && sync_ws, "%s: null pointer", name);
+  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "%s: bad sizes", name);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
+  unsigned long long* const prof = n_nets == 3 ? g_prof_buf : nullptr;
+  if (rs_takes(cfg_host, n_nets)) {
+    if (int rc = spo::rs_update_launch(theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
+                                       cfg_host, n_nets, stale_sq_io, losses_out, sync_ws, prof, stream)) return rc;
+    return launch_check(entry, " (row-split)");
+  }
+  UpdArgs a{};
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_host, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
+                   *cfg_host, n_nets, 0, stale_sq_io, losses_out, sync_ws);
+  a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
+  a.prof = prof;
+  if (int rc = launch_update<true>(a, n_nets, st)) return rc;
+  return launch_check(entry);
+}
+
 extern "C" int spo_ppo_lag_update_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                                        const float* obs, const float* act, const float* logp_old,
                                        const float* target_r, const float* target_c, const float* adv,
                                        const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host, float* losses_out,
                                        void* sync_ws, void* stream) {
-  if (int rc = check_cfg(cfg_host)) return rc;
-  SPO_REQUIRE(theta && adam_m && adam_v && obs && act && logp_old && target_r && target_c && adv && perm &&
-                  losses_out && sync_ws, "update_iter: null pointer");
-  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "update_iter: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  if (rs_takes(cfg_host, 3)) {
-    if (int rc = spo::rs_update_launch(theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
-                                       cfg_host, 3, nullptr, losses_out, sync_ws, g_prof_buf, stream)) return rc;
-    SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter (row-split)");
-    return 0;
-  }
-  UpdArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.M = M; a.cfg = *cfg_host; a.losses = losses_out;
-  a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-  a.first_net = 0; a.n_nets = 3; a.stale_sq = 0.f; a.stale_io = nullptr;
-  a.flat_grad = nullptr; a.mean_count = 0; a.prof = g_prof_buf;
-  if (int rc = launch_update<true>(a, 3, st)) return rc;
-  SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter");
-  return 0;
+  return update_iter("update_iter", "spo_ppo_lag_update_iter", 3, theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r,
+                     target_c, adv, perm, M, cfg_host, nullptr, losses_out, sync_ws, stream);
 }
 
 extern "C" int spo_critic_fit_iter(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
                                    const float* obs, const float* target_r, const float* target_c,
                                    const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host, float* stale_sq_io,
                                    float* losses_out, void* sync_ws, void* stream) {
-  if (int rc = check_cfg(cfg_host)) return rc;
-  SPO_REQUIRE(theta && adam_m && adam_v && obs && target_r && target_c && perm && losses_out && sync_ws,
-              "critic_fit_iter: null pointer");
-  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "critic_fit_iter: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  if (rs_takes(cfg_host, 2)) {
-    if (int rc = spo::rs_update_launch(theta, adam_m, adam_v, adam_step_host, obs, nullptr, nullptr, target_r, target_c, nullptr,
-                                       perm, M, cfg_host, 2, stale_sq_io, losses_out, sync_ws, nullptr, stream)) return rc;
-    SPO_LAUNCH_CHECK("spo_critic_fit_iter (row-split)");
-    return 0;
-  }
-  UpdArgs a{};
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.tgt_r = target_r; a.tgt_c = target_c; a.perm = perm; a.M = M; a.cfg = *cfg_host;
-  a.losses = losses_out;
-  a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-  a.first_net = 0; a.n_nets = 2; a.stale_sq = 0.f; a.stale_io = stale_sq_io;
-  if (int rc = launch_update<true>(a, 2, st)) return rc;
-  SPO_LAUNCH_CHECK("spo_critic_fit_iter");
-  return 0;
+  return update_iter("critic_fit_iter", "spo_critic_fit_iter", 2, theta, adam_m, adam_v, adam_step_host, obs, nullptr, nullptr, target_r,
+                     target_c, nullptr, perm, M, cfg_host, stale_sq_io, losses_out, sync_ws, stream);
 }
 
 extern "C" int spo_update_iter_ex(float* theta, float* adam_m, float* adam_v, int64_t adam_step_critics_host,
@@ -3622,38 +3573,34 @@ extern "C" int spo_p2p_selftest(int rank, int world, void* const* regions, uint3
   return 0;
 }
 
-extern "C" int spo_ppo_lag_update_iter_dp(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
-                                          const float* obs, const float* act, const float* logp_old,
-                                          const float* target_r, const float* target_c, const float* adv,
-                                          const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host, float* losses_out,
-                                          void* sync_ws, int rank, int world, void* const* regions, uint32_t step0,
-                                          void* stream) {
+// spo_ppo_lag_update_iter_dp (n_nets 3) and spo_critic_fit_iter_dp (n_nets 2: no act / logp_old / adv; stale_sq_io): one rank's
+// launch with the in-kernel gradient exchange.  Three networks only: the row-split kernel where SPO_XR_FORM_ROW_SPLIT is the form
+// and the shape is its own, and the all-to-all exchange on the helper waves.
+static int update_iter_dp(const char* name, const char* entry, int n_nets, float* theta, float* adam_m, float* adam_v,
+                          int64_t adam_step_host, const float* obs, const float* act, const float* logp_old, const float* target_r,
+                          const float* target_c, const float* adv, const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host,
+                          float* stale_sq_io, float* losses_out, void* sync_ws, int rank, int world, void* const* regions,
+                          uint32_t step0, void* stream) {
   if (int rc = check_cfg(cfg_host)) return rc;
-  SPO_REQUIRE(theta && adam_m && adam_v && obs && act && logp_old && target_r && target_c && adv && perm &&
-                  losses_out && sync_ws, "update_iter_dp: null pointer");
-  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "update_iter_dp: bad sizes");
+  SPO_REQUIRE(theta && adam_m && adam_v && obs && (n_nets == 2 || (act && logp_old && adv)) && target_r && target_c && perm &&
+                  losses_out && sync_ws, "%s: null pointer", name);
+  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "%s: bad sizes", name);
   hipStream_t st = (hipStream_t)stream;
   if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
   UpdArgs a{};
   if (int rc = fill_xr(a, rank, world, regions, step0)) return rc;
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.perm = perm; a.M = M; a.cfg = *cfg_host; a.losses = losses_out;
+  spo::fill_run_ex(a, theta, adam_m, adam_v, adam_step_host, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
+                   *cfg_host, n_nets, 0, stale_sq_io, losses_out, sync_ws);
   a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-  a.first_net = 0; a.n_nets = 3; a.stale_sq = 0.f; a.stale_io = nullptr;
   int rc = 0;
   const int kin = pick_kin(cfg_host->obs_dim);
   // SPO_XR_FORM_ROW_SPLIT (round 6): the row-split kernel with a one-hand-off all-to-all of the rank's gradient behind the row
   // groups' L2 hand-off (csrc/update_rs.hip, XW)
-  if (xr_form(world) == SPO_XR_FORM_ROW_SPLIT && spo_update_rs_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, 3)) {
+  if (n_nets == 3 && xr_form(world) == SPO_XR_FORM_ROW_SPLIT &&
+      spo_update_rs_supported(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, 3)) {
     if (int rc2 = spo::rs_update_launch_dp(theta, adam_m, adam_v, adam_step_host, obs, act, logp_old, target_r, target_c, adv, perm, M,
                                            cfg_host, losses_out, sync_ws, rank, world, regions, step0, RSX_OFF, stream)) return rc2;
-    SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_dp (row-split)");
-    return 0;
+    return launch_check(entry, " (row-split)");
   }
   // SPO_P2P_A2A=1 (opt-in): main + helper kernel with the flag-based all-to-all exchange on the helper waves.  One exchange
   // round at any world size, layer by layer beside the main waves' MFMAs -- but in single-GPU loopback (all ranks sharing
@@ -3666,20 +3613,30 @@ extern "C" int spo_ppo_lag_update_iter_dp(float* theta, float* adam_m, float* ad
   // against 14.3 / 16.7 / 19.1 for the default below (four-wave kernel, ONE exchange of the whole gradient per step): between P1
   // and Q2 the helper waves already gate the step, so hand-offs placed there are exposed in full and there are two per step.
   const int form = xr_four_wave_form(world);
-  const bool a2a = form == SPO_XR_FORM_HELPER_A2A;
+  // (the all-to-all form has no two-network instantiation: the helpers' doubling stands in)
+  const bool a2a = n_nets == 3 && form == SPO_XR_FORM_HELPER_A2A;
   a.xr_helper_rd = a2a ? 0 : 1;
-  if ((a2a || form == SPO_XR_FORM_HELPER_DOUBLING) && kin <= 64 && cfg_host->batch <= 64 && update_form() >= 2) {
+  if ((form == SPO_XR_FORM_HELPER_A2A || form == SPO_XR_FORM_HELPER_DOUBLING) && kin <= 64 && cfg_host->batch <= 64 && update_form() >= 2) {
     // main + helper form, exchange on the helper waves
-#define SPO_H_XR(K, D) (world == 2 ? launch_update_h<K, false, 2, D>(a, 3, st) : world == 4 ? launch_update_h<K, false, 4, D>(a, 3, st) \
-                                                                                               : launch_update_h<K, false, 8, D>(a, 3, st))
+#define SPO_H_XR(K, D) (world == 2 ? launch_update_h<K, false, 2, D>(a, n_nets, st) : world == 4 ? launch_update_h<K, false, 4, D>(a, n_nets, st) \
+                                                                                                     : launch_update_h<K, false, 8, D>(a, n_nets, st))
     if (a2a) rc = kin == 16 ? SPO_H_XR(16, 0) : kin == 32 ? SPO_H_XR(32, 0) : SPO_H_XR(64, 0);
     else rc = kin == 16 ? SPO_H_XR(16, 2) : kin == 32 ? SPO_H_XR(32, 2) : SPO_H_XR(64, 2);
 #undef SPO_H_XR
-  } else if (a.xr_algo == 1 && (world & (world - 1)) == 0) rc = launch_update<true, 0, 2>(a, 3, st);
-  else rc = launch_update<true, 0, 1>(a, 3, st);
+  } else if (a.xr_algo == 1 && (world & (world - 1)) == 0) rc = launch_update<true, 0, 2>(a, n_nets, st);
+  else rc = launch_update<true, 0, 1>(a, n_nets, st);
   if (rc) return rc;
-  SPO_LAUNCH_CHECK("spo_ppo_lag_update_iter_dp");
-  return 0;
+  return launch_check(entry);
+}
+
+extern "C" int spo_ppo_lag_update_iter_dp(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host,
+                                          const float* obs, const float* act, const float* logp_old,
+                                          const float* target_r, const float* target_c, const float* adv,
+                                          const int32_t* perm, int64_t M, const spo_ppo_cfg* cfg_host, float* losses_out,
+                                          void* sync_ws, int rank, int world, void* const* regions, uint32_t step0,
+                                          void* stream) {
+  return update_iter_dp("update_iter_dp", "spo_ppo_lag_update_iter_dp", 3, theta, adam_m, adam_v, adam_step_host, obs, act, logp_old,
+                        target_r, target_c, adv, perm, M, cfg_host, nullptr, losses_out, sync_ws, rank, world, regions, step0, stream);
 }
 
 // CPO critic fit for one rank of a data-parallel job: spo_critic_fit_iter with the in-kernel gradient exchange
@@ -3688,40 +3645,9 @@ extern "C" int spo_critic_fit_iter_dp(float* theta, float* adam_m, float* adam_v
                                       const float* target_r, const float* target_c, const int32_t* perm, int64_t M,
                                       const spo_ppo_cfg* cfg_host, float* stale_sq_io, float* losses_out, void* sync_ws,
                                       int rank, int world, void* const* regions, uint32_t step0, void* stream) {
-  if (int rc = check_cfg(cfg_host)) return rc;
-  SPO_REQUIRE(theta && adam_m && adam_v && obs && target_r && target_c && perm && losses_out && sync_ws,
-              "critic_fit_iter_dp: null pointer");
-  SPO_REQUIRE(M > 0 && adam_step_host >= 0, "critic_fit_iter_dp: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = spo::hip_check(hipMemsetAsync(sync_ws, 0, 64, st), "hipMemsetAsync(sync_ws)")) return rc;
-  UpdArgs a{};
-  if (int rc = fill_xr(a, rank, world, regions, step0)) return rc;
-  a.theta = theta; a.adam_m = adam_m; a.adam_v = adam_v;
-  a.obs = obs; a.tgt_r = target_r; a.tgt_c = target_c; a.perm = perm; a.M = M; a.cfg = *cfg_host;
-  a.losses = losses_out;
-  a.slots = reinterpret_cast<unsigned long long*>(sync_ws);
-  a.err = reinterpret_cast<int*>(reinterpret_cast<char*>(sync_ws) + 64);
-  a.pow_b1 = pow((double)cfg_host->beta1, (double)adam_step_host);
-  a.pow_b2 = pow((double)cfg_host->beta2, (double)adam_step_host);
-  a.pow_b1_actor = a.pow_b1; a.pow_b2_actor = a.pow_b2;
-  a.first_net = 0; a.n_nets = 2; a.stale_sq = 0.f; a.stale_io = stale_sq_io;
-  int rc = 0;
-  const int kin = pick_kin(cfg_host->obs_dim);
-  const int form = xr_four_wave_form(world);  // (the all-to-all form has no two-network instantiation: the helpers' doubling stands in)
-  a.xr_helper_rd = 1;
-  if ((form == SPO_XR_FORM_HELPER_A2A || form == SPO_XR_FORM_HELPER_DOUBLING) && kin <= 64 && cfg_host->batch <= 64 && update_form() >= 2) {
-    // main + helper form with recursive doubling on the helper waves (see spo_ppo_lag_update_iter_dp)
-#define SPO_H_XR(K) (world == 2 ? launch_update_h<K, false, 2, 2>(a, 2, st) : world == 4 ? launch_update_h<K, false, 4, 2>(a, 2, st) \
-                                                                                            : launch_update_h<K, false, 8, 2>(a, 2, st))
-    if (kin == 16) rc = SPO_H_XR(16);
-    else if (kin == 32) rc = SPO_H_XR(32);
-    else rc = SPO_H_XR(64);
-#undef SPO_H_XR
-  } else if (a.xr_algo == 1 && (world & (world - 1)) == 0) rc = launch_update<true, 0, 2>(a, 2, st);
-  else rc = launch_update<true, 0, 1>(a, 2, st);
-  if (rc) return rc;
-  SPO_LAUNCH_CHECK("spo_critic_fit_iter_dp");
-  return 0;
+  return update_iter_dp("critic_fit_iter_dp", "spo_critic_fit_iter_dp", 2, theta, adam_m, adam_v, adam_step_host, obs, nullptr, nullptr,
+                        target_r, target_c, nullptr, perm, M, cfg_host, stale_sq_io, losses_out, sync_ws, rank, world, regions, step0,
+                        stream);
 }
 
 // ---- one-grid split critic fit (single GPU): a 128-row minibatch as two 64-row halves on TWO workgroup pairs of ONE launch.
@@ -3734,24 +3660,20 @@ extern "C" int spo_critic_fit_iter_dp(float* theta, float* adam_m, float* adam_v
 // Cached pair of exchange regions + census words of the one-grid split form (round 5), one block per (device, stream),
 // allocated on first use, released by spo_update_scratch_release.  Cleared by every launch (tags restart with every engine;
 // 13 MB at HBM speed is ~5 us against a 0.5 s launch).
+// (`holds` is empty: a full table is no refusal here, the launch takes the uncached regions)
+constexpr spo::ScratchForm SPLIT_LOCAL_FORM{"split critic fit", "", "cached exchange regions are", "split exchange",
+                                            2 * XR_REGION_BYTES + 256, true, false};
 static int split_local_for(hipStream_t st, UpdArgs& a, UpdArgs& b) {
   static const bool off = [] { const char* e = getenv("SPO_CPO_SPLIT_L2"); return e && !strcmp(e, "0"); }();
   if (off) return 0;
   const int dev = current_device_slot();
   std::lock_guard<std::mutex> lk(g_split_local_mu);
-  SplitLocal* sl = nullptr;
-  for (int i = 0; i < g_split_local_n; ++i)
-    if (g_split_local[i].dev == dev && g_split_local[i].stream == (void*)st) sl = &g_split_local[i];
+  SplitLocal* sl = g_split_local.find(dev, (void*)st);
   if (!sl) {
-    if (g_split_local_n == SPLIT_LOCAL_MAX) return 0;               // (table full: the uncached regions, as before round 5)
-    if (spo::stream_is_capturing(st))                               // (allocation + memset would invalidate a capture)
-      return spo::fail(-1, "split critic fit: first launch on a stream under capture (the cached exchange regions are allocated on "
-                           "first use: launch once outside the capture)");
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, 2 * XR_REGION_BYTES + 256), "hipMalloc(split exchange, cached)")) return rc;
-    if (int rc = spo::hip_check(hipMemset(p, 0, 2 * XR_REGION_BYTES + 256), "hipMemset(split exchange)")) { (void)hipFree(p); return rc; }
-    g_split_local[g_split_local_n] = SplitLocal{dev, (void*)st, static_cast<char*>(p), 1u};
-    sl = &g_split_local[g_split_local_n++];
+    if (g_split_local.full()) return 0;                             // (table full: the uncached regions, as before round 5)
+    SplitLocal nb{dev, (void*)st, nullptr, 1u};
+    if (int rc = SPLIT_LOCAL_FORM.first_use(st, &nb.base)) return rc;
+    sl = g_split_local.add(nb);
   }
   if (int rc = spo::hip_check(hipMemsetAsync(sl->base, 0, 2 * XR_REGION_BYTES, st), "hipMemsetAsync(split exchange)")) return rc;
   for (UpdArgs* u : {&a, &b}) {
@@ -3761,6 +3683,20 @@ static int split_local_for(hipStream_t st, UpdArgs& a, UpdArgs& b) {
   }
   sl->tag += 1u;
   return 0;
+}
+
+// The two kernels of the one-grid split form: both ranks' workgroups in one grid
+template <int K>
+int launch_split_h_k(const UpdArgs& a, const UpdArgs& b, hipStream_t st) {
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  return launch_dyn_lds(&ppo_update_h_split_kernel<K>, attr_done, "update h split", dim3(8 * (2 * a.n_nets - 1) + 1),
+                        dim3(512), UpdHLds<K>::SIZE * sizeof(float), st, a, b);
+}
+template <int K>
+int launch_split_k(const UpdArgs& a, const UpdArgs& b, hipStream_t st) {
+  static bool attr_done[SPO_MAX_DEVICES] = {};
+  return launch_dyn_lds(&ppo_update_split_kernel<K>, attr_done, "update split", dim3(8 * (2 * a.n_nets - 1) + 1),
+                        dim3(256), UpdLds<K>::SIZE * sizeof(float), st, a, b);
 }
 
 extern "C" int spo_critic_fit_iter_split(float* theta0, float* adam_m0, float* adam_v0, float* theta1, float* adam_m1,
@@ -3797,46 +3733,19 @@ extern "C" int spo_critic_fit_iter_split(float* theta0, float* adam_m0, float* a
   if (split_h && kin <= 64 && cfg_host->batch <= 64 && update_form() >= 2) {
     if (int rc = h_scratch_for(st, &a.backup, &a.slots, 0)) return rc;
     if (int rc = h_scratch_for(st, &b.backup, &b.slots, 1)) return rc;
-    static const int spec_env = [] { const char* e = getenv("SPO_UPDATE_SPEC"); return e ? atoi(e) : 1; }();
-    a.spec_mode = b.spec_mode = spec_env;
+    a.spec_mode = b.spec_mode = update_spec();
     a.xr_helper_rd = b.xr_helper_rd = 1;
     if (int rc = split_local_for(st, a, b)) return rc;
     if (int rc = spo::hip_check(hipMemsetAsync(a.slots, 0, H_SLOT_BYTES, st), "hipMemsetAsync(update scratch slots)")) return rc;
     if (int rc = spo::hip_check(hipMemsetAsync(b.slots, 0, H_SLOT_BYTES, st), "hipMemsetAsync(update scratch slots)")) return rc;
-#define SPO_SPLIT_H(K)                                                                                            \
-  {                                                                                                               \
-    const size_t sh = UpdHLds<K>::SIZE * sizeof(float);                                                           \
-    static bool attr_done[SPO_MAX_DEVICES] = {};                                                                  \
-    const int dslot = current_device_slot();                                                                      \
-    if (!attr_done[dslot]) {                                                                                      \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_h_split_kernel<K>),            \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                    \
-      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update h split)");                       \
-      attr_done[dslot] = true;                                                                                    \
-    }                                                                                                             \
-    hipLaunchKernelGGL((ppo_update_h_split_kernel<K>), dim3(8 * (2 * a.n_nets - 1) + 1), dim3(512), sh, st, a, b); \
-  }
-    if (kin == 16) SPO_SPLIT_H(16) else if (kin == 32) SPO_SPLIT_H(32) else SPO_SPLIT_H(64)
-#undef SPO_SPLIT_H
+    if (int rc = kin == 16 ? launch_split_h_k<16>(a, b, st) : kin == 32 ? launch_split_h_k<32>(a, b, st) : launch_split_h_k<64>(a, b, st))
+      return rc;
     SPO_LAUNCH_CHECK("spo_critic_fit_iter_split");
     return 0;
   }
   if (int rc = split_local_for(st, a, b)) return rc;   // (SPO_CPO_SPLIT_L2=0: the uncached regions whatever the placement)
-#define SPO_SPLIT(K)                                                                                              \
-  {                                                                                                               \
-    const size_t sh = UpdLds<K>::SIZE * sizeof(float);                                                            \
-    static bool attr_done[SPO_MAX_DEVICES] = {};                                                                  \
-    const int dslot = current_device_slot();                                                                      \
-    if (!attr_done[dslot]) {                                                                                      \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_split_kernel<K>),              \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                    \
-      if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update split)");                         \
-      attr_done[dslot] = true;                                                                                    \
-    }                                                                                                             \
-    hipLaunchKernelGGL((ppo_update_split_kernel<K>), dim3(8 * (2 * a.n_nets - 1) + 1), dim3(256), sh, st, a, b);  \
-  }
-  if (kin == 16) SPO_SPLIT(16) else if (kin == 32) SPO_SPLIT(32) else if (kin == 64) SPO_SPLIT(64) else SPO_SPLIT(128)
-#undef SPO_SPLIT
+  if (int rc = kin == 16 ? launch_split_k<16>(a, b, st) : kin == 32 ? launch_split_k<32>(a, b, st)
+             : kin == 64 ? launch_split_k<64>(a, b, st) : launch_split_k<128>(a, b, st)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_split");
   return 0;
 }
@@ -3856,12 +3765,12 @@ extern "C" int spo_debug_critic_fit_split_multi_counters(unsigned long long* out
   SPO_REQUIRE(out3_host, "critic_fit_split_multi_counters: null pointer");
   for (int i = 0; i < 3; ++i) out3_host[i] = reset ? g_splitm_counters[i].exchange(0ull) : g_splitm_counters[i].load();
   std::lock_guard<std::mutex> lk(g_splitm_mu);
-  if (g_splitm.n == 0) return 0;                                           // (no block: no device access)
+  if (g_splitm.blocks.n == 0) return 0;                                    // (no block: no device access)
   const int dev = current_device_slot();
-  for (int i = 0; i < g_splitm.n; ++i) {
-    if (g_splitm.e[i].dev != dev) continue;
+  for (int i = 0; i < g_splitm.blocks.n; ++i) {
+    if (g_splitm.blocks.e[i].dev != dev) continue;
     unsigned long long l2 = 0;
-    if (int rc = splitm_read_l2(g_splitm.e[i], &l2, reset != 0)) return rc;
+    if (int rc = splitm_read_l2(g_splitm.blocks.e[i], &l2, reset != 0)) return rc;
     out3_host[2] += l2;
   }
   return 0;
@@ -3950,7 +3859,7 @@ extern "C" int spo_critic_fit_iter_split_multi(const spo_critic_fit_split_replic
   if (int rc = spo::hip_check(hipMemsetAsync(base, 0, (size_t)n_replicas * SPLITM_RUN_BYTES, st), "hipMemsetAsync(split exchange)"))
     return rc;
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  if (int rc = spo::launch_dyn_lds(&ppo_update_split_multi_kernel<128>, attr_done, "hipFuncSetAttribute(update split multi)",
+  if (int rc = spo::launch_dyn_lds(&ppo_update_split_multi_kernel<128>, attr_done, "update split multi",
                                    dim3(spo::rs_multi_grid(n_replicas, SPLITM_WGS)), dim3(256), UpdLds<128>::SIZE * sizeof(float), st,
                                    table_dev, n_replicas)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_split_multi");

@@ -1078,33 +1078,24 @@ __global__ __launch_bounds__(256, 1) void critic_fit_ks_multi_kernel(const KsMul
 // atomics).  One block per device, allocated on first use, zeroed once (tags never repeat).
 struct KsScratch { float* z; unsigned long long* gran; };
 constexpr size_t KS_G_BYTES = (size_t)(2 * 2 * 3 * KS_MAX_SLICES + 3 * KS_MAX_SLICES) * 8;   // granules + the placement census
-// One block per (device, stream), like the update kernels' scratch in update.hip: launches on one stream are ordered and share
-// it, two engines on two streams get two blocks and may run concurrently.  Released by spo_update_scratch_release.
+// One block per (device, stream): launches on one stream are ordered and share it, two engines on two streams get two blocks and
+// may run concurrently.  Released by spo_update_scratch_release.
 struct KsEntry { int dev; void* stream; char* base; unsigned tag; bool primed; };   // primed: the slots have been set to the sentinel once
 constexpr int KS_SCRATCH_MAX = 16;
-KsEntry g_ks[KS_SCRATCH_MAX] = {};
-int g_ks_n = 0;
+constexpr spo::ScratchForm KS_FORM{"feature-split update kernel", "exchange scratch", "scratch block is", "ks scratch",
+                                   KS_Z_BYTES + KS_G_BYTES, true, true};
+spo::StreamTable<KsEntry, KS_SCRATCH_MAX> g_ks;
 std::mutex g_ks_mu;
 
 int ks_scratch(hipStream_t st, KsScratch* out, unsigned* tag_base, unsigned nsteps, bool** primed = nullptr) {
   const int dev = current_device_slot();
   std::lock_guard<std::mutex> lk(g_ks_mu);
-  KsEntry* e = nullptr;
-  for (int i = 0; i < g_ks_n; ++i)
-    if (g_ks[i].dev == dev && g_ks[i].stream == (void*)st) e = &g_ks[i];
+  KsEntry* e = g_ks.find(dev, (void*)st);
   if (!e) {
-    if (g_ks_n == KS_SCRATCH_MAX)
-      return spo::fail(-1, "feature-split update kernel: more than %d (device, stream) pairs hold exchange scratch in this process; "
-                           "call spo_update_scratch_release(stream) for streams that are gone", KS_SCRATCH_MAX);
-    if (spo::stream_is_capturing(st))
-      return spo::fail(-1, "feature-split update kernel: first launch on a stream under capture (the scratch block is allocated on "
-                           "first use: launch once outside the capture)");
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, KS_Z_BYTES + KS_G_BYTES), "hipMalloc(ks scratch)")) return rc;
-    if (int rc = spo::hip_check(hipMemset(p, 0, KS_Z_BYTES + KS_G_BYTES), "hipMemset(ks scratch)")) { (void)hipFree(p); return rc; }
-    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(ks scratch)")) { (void)hipFree(p); return rc; }
-    g_ks[g_ks_n] = KsEntry{dev, (void*)st, static_cast<char*>(p), 16u, false};
-    e = &g_ks[g_ks_n++];
+    if (g_ks.full()) return KS_FORM.refuse_full(KS_SCRATCH_MAX);
+    KsEntry nb{dev, (void*)st, nullptr, 16u, false};
+    if (int rc = KS_FORM.first_use(st, &nb.base)) return rc;
+    e = g_ks.add(nb);
   }
   out->z = reinterpret_cast<float*>(e->base);
   out->gran = reinterpret_cast<unsigned long long*>(e->base + KS_Z_BYTES);
@@ -1172,16 +1163,10 @@ int spo::ks_scratch_release(int dev, void* stream_or_null, int all) {
   int freed = 0;
   {
     std::lock_guard<std::mutex> lk(g_ks_mu);
-    for (int i = 0; i < g_ks_n;) {
-      if (g_ks[i].dev == dev && (all || g_ks[i].stream == stream_or_null)) {
-        (void)spo::hip_check(hipFree(g_ks[i].base), "hipFree(ks scratch)");
-        g_ks[i] = g_ks[--g_ks_n];
-        ++freed;
-      } else ++i;
-    }
+    freed += g_ks.release(dev, stream_or_null, all, [](KsEntry& b) { spo::free_block(b.base, "ks scratch"); });
   }
-  std::lock_guard<std::mutex> lk(g_ksm_mu);
-  return freed + g_ksm.release(dev, stream_or_null, all);
+  { std::lock_guard<std::mutex> lk(g_ksm_mu); freed += g_ksm.release(dev, stream_or_null, all); }
+  return freed;
 }
 
 #ifdef SPO_KS_PROF
@@ -1212,24 +1197,11 @@ static int ks_launch(KsArgs& a, void* sync_ws, hipStream_t st, int kind) {
     if (int rc = spo::hip_check(hipMemsetAsync(sc.z, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)")) return rc;
     *primed = true;
   }
-  const size_t sh = KsLds::SIZE * sizeof(float);
-  static bool attr_done[SPO_MAX_DEVICES][4] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot][kind]) {
-    const void* fn = kind == 1 ? reinterpret_cast<const void*>(&critic_fit_ks_kernel)
-                   : kind == 3 ? reinterpret_cast<const void*>(&ppo_grad_ks_kernel)
-                   : kind == 2 ? reinterpret_cast<const void*>(&klpen_update_ks_kernel)
-                               : reinterpret_cast<const void*>(&ppo_update_ks_kernel);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_ks)");
-    attr_done[dslot][kind] = true;
-  }
-  const dim3 grid(8 * (a.n_nets * a.S - 1) + 1);
-  if (kind == 3) hipLaunchKernelGGL(ppo_grad_ks_kernel, grid, dim3(256), sh, st, a);
-  else if (kind == 1) hipLaunchKernelGGL(critic_fit_ks_kernel, grid, dim3(256), sh, st, a);
-  else if (kind == 2) hipLaunchKernelGGL(klpen_update_ks_kernel, grid, dim3(256), sh, st, a);
-  else hipLaunchKernelGGL(ppo_update_ks_kernel, grid, dim3(256), sh, st, a);
-  return 0;
+  void (*const kernel)(KsArgs) = kind == 1 ? &critic_fit_ks_kernel : kind == 3 ? &ppo_grad_ks_kernel
+                               : kind == 2 ? &klpen_update_ks_kernel : &ppo_update_ks_kernel;
+  static bool attr_done[4][SPO_MAX_DEVICES] = {};  // one row per kernel
+  return spo::launch_dyn_lds(kernel, attr_done[kind], "update_ks", dim3(8 * (a.n_nets * a.S - 1) + 1), dim3(256),
+                             KsLds::SIZE * sizeof(float), st, a);
 }
 
 extern "C" int spo_ppo_lag_update_iter_ks(float* theta, float* adam_m, float* adam_v, int64_t adam_step_host, const float* obs,
@@ -1346,9 +1318,9 @@ extern "C" int spo_debug_update_ks_multi_counters(unsigned long long* out3_host,
   std::lock_guard<std::mutex> lk(g_ksm_mu);
   const int dev = current_device_slot();
   unsigned long long wt = g_ksm_wt_released;
-  for (int i = 0; i < g_ksm.n; ++i)
-    if (g_ksm.e[i].dev == dev)
-      if (int rc = ksm_harvest(g_ksm.e[i], &wt, reset != 0)) return rc;
+  for (int i = 0; i < g_ksm.blocks.n; ++i)
+    if (g_ksm.blocks.e[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm.blocks.e[i], &wt, reset != 0)) return rc;
   if (reset) g_ksm_wt_released = 0;
   for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_counters[i].exchange(0ull) : g_ksm_counters[i].load();
   out3_host[2] = wt;
@@ -1420,7 +1392,7 @@ extern "C" int spo_update_iter_ex_ks_multi(const spo_update_ex_replica* reps_hos
   const bool klpen = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
   static bool attr_done[2][SPO_MAX_DEVICES] = {};
   if (int rc = spo::launch_dyn_lds(klpen ? &klpen_update_ks_multi_kernel : &ppo_update_ks_multi_kernel, attr_done[klpen],
-                                   "hipFuncSetAttribute(update_ks_multi)", dim3(spo::rs_multi_grid(n_replicas, wgs)), dim3(256),
+                                   "update_ks_multi", dim3(spo::rs_multi_grid(n_replicas, wgs)), dim3(256),
                                    KsLds::SIZE * sizeof(float), st, table_dev, n_replicas, wgs)) return rc;
   SPO_LAUNCH_CHECK("spo_update_iter_ex_ks_multi");
   g_ksm_counters[0] += 1ull;
@@ -1452,9 +1424,9 @@ extern "C" int spo_debug_critic_fit_ks_multi_counters(unsigned long long* out3_h
   std::lock_guard<std::mutex> lk(g_ksm_mu);
   const int dev = current_device_slot();
   unsigned long long wt = g_ksm_cfit_wt_released;
-  for (int i = 0; i < g_ksm.n; ++i)
-    if (g_ksm.e[i].dev == dev)
-      if (int rc = ksm_harvest(g_ksm.e[i], &wt, reset != 0, 1)) return rc;
+  for (int i = 0; i < g_ksm.blocks.n; ++i)
+    if (g_ksm.blocks.e[i].dev == dev)
+      if (int rc = ksm_harvest(g_ksm.blocks.e[i], &wt, reset != 0, 1)) return rc;
   if (reset) g_ksm_cfit_wt_released = 0;
   for (int i = 0; i < 2; ++i) out3_host[i] = reset ? g_ksm_cfit_counters[i].exchange(0ull) : g_ksm_cfit_counters[i].load();
   out3_host[2] = wt;
@@ -1520,7 +1492,7 @@ extern "C" int spo_critic_fit_iter_ks_multi(const spo_critic_fit_replica* reps_h
       if (int rc = spo::hip_check(hipMemsetAsync(sl.base + (size_t)r * KSM_STRIDE, 0xFF, KS_ZZERO_OFF, st), "hipMemsetAsync(ks partials)"))
         return rc;
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  if (int rc = spo::launch_dyn_lds(&critic_fit_ks_multi_kernel, attr_done, "hipFuncSetAttribute(critic_fit_ks_multi)",
+  if (int rc = spo::launch_dyn_lds(&critic_fit_ks_multi_kernel, attr_done, "critic_fit_ks_multi",
                                    dim3(spo::rs_multi_grid(n_replicas, wgs)), dim3(256), KsLds::SIZE * sizeof(float), st, table_dev,
                                    n_replicas, wgs)) return rc;
   SPO_LAUNCH_CHECK("spo_critic_fit_iter_ks_multi");

@@ -1679,62 +1679,46 @@ __global__ __launch_bounds__(512) void ppo_update_rs_multi_kernel(const RsMultiE
 }
 
 // Exchange scratch: the partial-gradient slots and the norm granules, ordinary device memory.  One block per (device, stream),
-// allocated on first use (update_ks.hip's scheme): launches on one stream are ordered and share it.
+// allocated on first use: launches on one stream are ordered and share it.
 struct RsEntry { int dev; void* stream; char* base; unsigned tag; char* stage; size_t stage_bytes; };   // stage: the staged-input block (grown on demand)
 constexpr int RS_SCRATCH_MAX = 16;
-RsEntry g_rs[RS_SCRATCH_MAX] = {};
-int g_rs_n = 0;
-std::mutex g_rs_mu;
 constexpr size_t RS_Z_MAX = rs_z_bytes(RS_MAX_R);
 constexpr size_t RS_G_BYTES = (size_t)(RS_GRAN_WORDS + RS_CENSUS_WORDS) * 8;
+constexpr spo::ScratchForm RS_FORM{"row-split update kernel", "exchange scratch", "scratch block is", "rs scratch", RS_Z_MAX + RS_G_BYTES,
+                                   true, true};
+spo::StreamTable<RsEntry, RS_SCRATCH_MAX> g_rs;
+std::mutex g_rs_mu;
 
-int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* tag_base, unsigned nsteps) {
+// The stream's block and the tags of one launch of nsteps steps.  The caller holds g_rs_mu, and keeps it while it uses *entry (a
+// release on another stream may move the entry).
+int rs_scratch(hipStream_t st, float** z, unsigned long long** gran, unsigned* tag_base, unsigned nsteps, RsEntry** entry = nullptr) {
   const int dev = current_device_slot();
-  std::lock_guard<std::mutex> lk(g_rs_mu);
-  RsEntry* e = nullptr;
-  for (int i = 0; i < g_rs_n; ++i)
-    if (g_rs[i].dev == dev && g_rs[i].stream == (void*)st) e = &g_rs[i];
+  RsEntry* e = g_rs.find(dev, (void*)st);
   if (!e) {
-    if (g_rs_n == RS_SCRATCH_MAX)
-      return spo::fail(-1, "row-split update kernel: more than %d (device, stream) pairs hold exchange scratch in this process; "
-                           "call spo_update_scratch_release(stream) for streams that are gone", RS_SCRATCH_MAX);
-    if (spo::stream_is_capturing(st))
-      return spo::fail(-1, "row-split update kernel: first launch on a stream under capture (the scratch block is allocated on "
-                           "first use: launch once outside the capture)");
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, RS_Z_MAX + RS_G_BYTES), "hipMalloc(rs scratch)")) return rc;
-    if (int rc = spo::hip_check(hipMemset(p, 0, RS_Z_MAX + RS_G_BYTES), "hipMemset(rs scratch)")) { (void)hipFree(p); return rc; }
-    if (int rc = spo::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(rs scratch)")) { (void)hipFree(p); return rc; }
-    g_rs[g_rs_n] = RsEntry{dev, (void*)st, static_cast<char*>(p), 16u, nullptr, 0};
-    e = &g_rs[g_rs_n++];
+    if (g_rs.full()) return RS_FORM.refuse_full(RS_SCRATCH_MAX);
+    RsEntry nb{dev, (void*)st, nullptr, 16u, nullptr, 0};
+    if (int rc = RS_FORM.first_use(st, &nb.base)) return rc;
+    e = g_rs.add(nb);
   }
   *z = reinterpret_cast<float*>(e->base);
   *gran = reinterpret_cast<unsigned long long*>(e->base + RS_Z_MAX);
   *tag_base = e->tag;
   e->tag += nsteps + 2u;                           // (wraps after 4e9 steps: a tag then meets words 2^32 steps old)
+  if (entry) *entry = e;
   return 0;
 }
 
-// The staged-input block of the stream's scratch entry (made by rs_scratch just before), at least `bytes` long: grown on demand
-// (hipFree waits for the launches that still read the old block), never inside a capture -- *out stays null there unless the
-// block is already large enough, and the launch takes the in-kernel gather.
-int rs_stage_block(hipStream_t st, size_t bytes, char** out) {
+// The staged-input block of the stream's scratch entry (found by rs_scratch just before, under the same hold of g_rs_mu), at least
+// `bytes` long: grown on demand (hipFree waits for the launches that still read the old block), never inside a capture -- *out
+// stays null there unless the block is already large enough, and the launch takes the in-kernel gather.
+int rs_stage_block(RsEntry* e, hipStream_t st, size_t bytes, char** out) {
   *out = nullptr;
-  const int dev = current_device_slot();
-  std::lock_guard<std::mutex> lk(g_rs_mu);
-  RsEntry* e = nullptr;
-  for (int i = 0; i < g_rs_n; ++i)
-    if (g_rs[i].dev == dev && g_rs[i].stream == (void*)st) e = &g_rs[i];
-  if (!e) return spo::fail(-1, "row-split update kernel: no scratch entry for this stream");
   if (e->stage_bytes < bytes) {
     if (spo::stream_is_capturing(st)) return 0;
-    if (e->stage) {
-      (void)spo::hip_check(hipFree(e->stage), "hipFree(rs stage)");
-      e->stage = nullptr; e->stage_bytes = 0;
-    }
-    void* p = nullptr;
-    if (int rc = spo::hip_check(hipMalloc(&p, bytes), "hipMalloc(rs stage)")) return rc;
-    e->stage = static_cast<char*>(p); e->stage_bytes = bytes;
+    spo::free_block(e->stage, "rs stage");
+    e->stage = nullptr; e->stage_bytes = 0;
+    if (int rc = spo::alloc_block(bytes, false, false, "rs stage", &e->stage)) return rc;
+    e->stage_bytes = bytes;
   }
   *out = e->stage;
   return 0;
@@ -1798,33 +1782,19 @@ float rs_clip_threshold(float mg) {
 
 template <int KIN, int R, bool PROF, int XW = 0, int NCT = 2, bool L1P = false, int STG = 0>
 int rs_launch_k(const RsArgs& a, hipStream_t st) {
-  const size_t sh = RsLds<KIN, NCT, STG == 1>::SIZE * sizeof(float);
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  const int dslot = current_device_slot();
-  if (!attr_done[dslot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P, STG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return spo::hip_check(e, "hipFuncSetAttribute(update_rs)");
-    attr_done[dslot] = true;
-  }
-  hipLaunchKernelGGL((ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P, STG>), dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), sh, st, a);
-  return 0;
+  return spo::launch_dyn_lds(&ppo_update_rs_kernel<KIN, R, PROF, XW, NCT, L1P, STG>, attr_done, "update_rs",
+                             dim3(8 * (a.n_nets * R - 1) + 1), dim3(512), RsLds<KIN, NCT, STG == 1>::SIZE * sizeof(float), st, a);
 }
 
 }  // namespace
 
 int spo::rs_scratch_release(int dev, void* stream_or_null, int all) {
   std::lock_guard<std::mutex> lk(g_rs_mu);
-  int freed = 0;
-  for (int i = 0; i < g_rs_n;) {
-    if (g_rs[i].dev == dev && (all || g_rs[i].stream == stream_or_null)) {
-      (void)spo::hip_check(hipFree(g_rs[i].base), "hipFree(rs scratch)");
-      if (g_rs[i].stage) (void)spo::hip_check(hipFree(g_rs[i].stage), "hipFree(rs stage)");
-      g_rs[i] = g_rs[--g_rs_n];
-      ++freed;
-    } else ++i;
-  }
-  return freed;
+  return g_rs.release(dev, stream_or_null, all, [](RsEntry& b) {
+    spo::free_block(b.base, "rs scratch");
+    spo::free_block(b.stage, "rs stage");
+  });
 }
 
 int spo::rs_counters(unsigned long long* out2_host, int reset) {
@@ -1905,7 +1875,9 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   const bool l1p = rs_l1_pipe();
   const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
   SPO_REQUIRE(nsteps < (1ll << 30), "update_rs: too many minibatch steps in one launch");
-  if (int rc = rs_scratch(st, &a.zbuf, &a.gran, &a.tag_base, (unsigned)nsteps)) return rc;
+  std::unique_lock<std::mutex> lk(g_rs_mu);                                // (until rs_stage_block below has settled the staging block)
+  RsEntry* entry = nullptr;
+  if (int rc = rs_scratch(st, &a.zbuf, &a.gran, &a.tag_base, (unsigned)nsteps, &entry)) return rc;
   // Rows of a minibatch per workgroup: 32 (two row groups up to 64 rows, four up to 128: the critic fit's 128-row minibatches) or,
   // opt-in, 16 (SPO_RS_ROWS=16: four row groups up to 64 rows, the column waves as four feature quarters of one column tile --
   // measured SLOWER, 9.46 against 7.9 us per step: the matrix work per SIMD halves again, but three peers' partials to poll, add
@@ -1919,11 +1891,15 @@ int spo::rs_update_launch(float* theta, float* adam_m, float* adam_v, int64_t ad
   // ---- staged inputs (the PPO-Lagrangian step, two row groups, KIN <= 64): the pre-pass on this stream, then the STG kernel.
   // (SPO_RS_L1_PIPE=0 at KIN = 64, the one-batch A/B form, has no STG instantiation: it gathers in the kernel as before.)
   int stg = 0;
+  size_t bytes = 0;
+  char* block = nullptr;
   if (n_nets == 3 && !(kin == 64 && !l1p) && (stg = rs_stage_form()) != 0) {
-    const size_t bytes = (size_t)spo_rs_stage_bytes(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, M);
-    char* block = nullptr;
+    bytes = (size_t)spo_rs_stage_bytes(cfg_host->obs_dim, cfg_host->act_dim, cfg_host->batch, M);
     if (bytes != 0 && bytes <= rs_stage_max_bytes() && bytes < ((size_t)1 << 31))
-      if (int rc = rs_stage_block(st, bytes, &block)) return rc;
+      if (int rc = rs_stage_block(entry, st, bytes, &block)) return rc;
+  }
+  lk.unlock();                                                             // (`entry` is not used below; `block` is device memory)
+  if (stg) {
     if (block) {
       if (int rc = rs_stage_launch(a, block, nsteps, st)) return rc;
       a.stage = block; a.stage_bytes = (unsigned)bytes;
@@ -1982,7 +1958,10 @@ int spo::rs_update_launch_dp(float* theta, float* adam_m, float* adam_v, int64_t
   a.xr_rank = rank; a.xr_step0 = step0; a.rsx_off = rsx_off;
   const int64_t nsteps = (M + cfg_host->batch - 1) / cfg_host->batch;
   SPO_REQUIRE(nsteps < (1ll << 30), "update_rs: too many minibatch steps in one launch");
-  if (int rc = rs_scratch(st, &a.zbuf, &a.gran, &a.tag_base, (unsigned)nsteps)) return rc;
+  {
+    std::lock_guard<std::mutex> lk(g_rs_mu);
+    if (int rc = rs_scratch(st, &a.zbuf, &a.gran, &a.tag_base, (unsigned)nsteps)) return rc;
+  }
   if (int rc = spo::hip_check(hipMemsetAsync(a.zbuf, 0xFF, rs_z_bytes(2), st), "hipMemsetAsync(rs slots)")) return rc;
   const int kin = cfg_host->obs_dim <= 16 ? 16 : cfg_host->obs_dim <= 32 ? 32 : 64;
 #define RS_GO_DP(K) (world == 2 ? rs_launch_k<K, 2, false, 2>(a, st) : world == 4 ? rs_launch_k<K, 2, false, 4>(a, st) \
@@ -2020,7 +1999,7 @@ spo::ReplicaPool<RsMultiEntry, SPO_RS_CRITIC_MAX_REPLICAS, RS_SCRATCH_MAX> g_rsm
 template <int KIN, bool L1P>
 int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, L1P, 2, 3>, attr_done, "hipFuncSetAttribute(update_rs_multi)",
+  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, L1P, 2, 3>, attr_done, "update_rs_multi",
                              dim3(rs_multi_grid(n_replicas, RS_MULTI_WG)), dim3(512), RsLds<KIN, 2>::SIZE * sizeof(float), st, table_dev,
                              n_replicas);
 }
@@ -2028,7 +2007,7 @@ int rs_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t
 template <int KIN>
 int rs_critic_multi_launch_k(const RsMultiEntry* table_dev, int n_replicas, hipStream_t st) {
   static bool attr_done[SPO_MAX_DEVICES] = {};
-  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, false, 4, 2>, attr_done, "hipFuncSetAttribute(update_rs_multi)",
+  return spo::launch_dyn_lds(&ppo_update_rs_multi_kernel<KIN, false, 4, 2>, attr_done, "update_rs_multi",
                              dim3(rs_multi_grid(n_replicas, RS_CRITIC_MULTI_WG)), dim3(512), RsLds<KIN, 2>::SIZE * sizeof(float), st,
                              table_dev, n_replicas);
 }
