@@ -1041,6 +1041,50 @@ int spo_wide_rows_clip_adam_dev_log(float* parts, int64_t rows, float* theta, fl
                                     const spo_ppo_cfg* cfg, double* pow4_dev, float* losses3_out, float* scalars4_out,
                                     double* partial_ws, int partial_capacity, float* loss_log_dev, int64_t* cursor_dev,
                                     int64_t cursor_step, void* stream);
+/* Seed-batched form of the fused step above (spo_wide_ppo_grad_rows + spo_wide_rows_clip_adam_dev_log): S independent runs of ONE
+ * shape (critic, actor, rows) in the same three launches, run r on the grid slice blockIdx.y == r.  Each run's blocks read the
+ * arguments its stand-alone launches would receive from a device table and run the same kernel bodies on the same blockIdx.x /
+ * gridDim.x, so per run the step is bit for bit its own stand-alone sequence (partial sums and their order included).  No workgroup
+ * of these kernels waits for another: there is no exchange, no placement census, no per-XCD budget and no timeout path -- the cap
+ * of 32 runs bounds the table only.  A run with active == 0 is skipped: its blocks return before they touch memory, nothing of it
+ * is read or written, and its pointers may be NULL.
+ * spo_wide_rows_replica -- one run's pointers: everything the two stand-alone entries take.  perm / cursor_dev / loss_log_dev are a
+ *   PermWindow's arrays (the rows perm[*cursor_dev .. + rows); the step stores its losses at loss_log_dev[3 * (*cursor_dev /
+ *   cursor_step)] and moves the cursor on; loss_log_dev may be NULL), pow4_dev the run's device clocks and learning rates
+ *   (double[6], spo_wide_clip_adam_dev), partial_ws double[partial_capacity >= 3 * min(ceil(n_params / 256), 1024)].  cfg: clip, the
+ *   L2 / value-coefficient options, max_grad_norm, betas, eps (learning rates: pow4_dev[4..5] where >= 0).
+ * spo_wide_rows_multi_supported -- 1 where spo_wide_grad_rows_supported(critic, actor, rows) holds with an actor and
+ *   1 <= n_replicas <= SPO_WIDE_ROWS_MAX_REPLICAS.  Host only.
+ * spo_wide_rows_multi_table_bytes -- bytes of the device table for n_replicas runs (-1 outside the cap).
+ * spo_wide_rows_multi_upload -- validates reps_host[n_replicas] (a HOST array), fills every active run's kernel arguments through the
+ *   code the stand-alone entries use and copies the table to table_dev (stream-ordered; returns when the copy is done).  Refused
+ *   before any HIP call, in this order: a null table, n_replicas outside the cap, an unsupported shape, a null pointer of an active
+ *   run, two active runs sharing theta, parts or cursor_dev, parameter ranges out of order, a partial workspace too small,
+ *   cursor_step <= 0; then a stream under capture.
+ * spo_wide_rows_step_multi -- the three launches for all runs of an uploaded table: no allocation, no copy, no host read, so the
+ *   call can be captured into a HIP graph and replayed (the table is read at every replay: upload a new one between replays to
+ *   change the active flags). */
+#define SPO_WIDE_ROWS_MAX_REPLICAS 32
+typedef struct {
+  float *theta, *adam_m, *adam_v;          /* the run's own parameters and moments */
+  float *grad, *parts;                     /* float[n_params]; float[spo_wide_grad_rows_part_floats(n_params, rows)] */
+  const float *obs, *act, *logp_old, *target_r, *target_c, *adv;   /* the FULL arrays of the run's buffer */
+  const int64_t* perm;                     /* the run's shuffle (device) */
+  int64_t* cursor_dev;                     /* position in perm, advanced by cursor_step per step */
+  double* pow4_dev;                        /* double[6]: beta powers of both optimiser clocks, the two learning rates */
+  float *losses3_out, *scalars4_out;       /* the step's losses; {clip coefficient, L2 terms, gradient norm} */
+  double* partial_ws;
+  int partial_capacity;
+  float* loss_log_dev;                     /* [steps of a pass][3], or NULL */
+  spo_ppo_cfg cfg;
+  int active;
+} spo_wide_rows_replica;
+int spo_wide_rows_multi_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int n_replicas);
+int64_t spo_wide_rows_multi_table_bytes(int n_replicas);
+int spo_wide_rows_multi_upload(void* table_dev, const spo_wide_rows_replica* reps_host, int n_replicas, const spo_mlp_net* critic,
+                               const spo_mlp_net* actor, int64_t rows, int64_t cursor_step, void* stream);
+int spo_wide_rows_step_multi(const void* table_dev, int n_replicas, const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows,
+                             void* stream);
 /* The KL-penalty loss of FOCOPS (focops.py:326-347) and of CUP's actor-only second stage (cup.py:370-386) on the row groups of
  * spo_wide_ppo_grad_rows: same rows (idx / cursor_dev / rows as there), same theta layout, one launch.  The loss needs
  * F = mean_i(ind_i), ind_i = [KL_i <= kl_bound], before its cotangent; its gradient is linear in F, g_actor = g_KL + F * g_PG with

@@ -40,6 +40,7 @@
 #include "mlp_mfma.h"
 #include "adam.h"
 #include <cstdlib>
+#include <vector>
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -83,6 +84,30 @@ struct MrArgs {
   const float* old_mean; const float* old_std;     // KL-penalty launch: old_mean[M][act_dim] (read through the index window), old_std[act_dim]
   float kl_bound, pg_coef;
   MrNet net[4];
+};
+
+struct MrOptArgs {
+  const float* parts; int R; int64_t stride;
+  float* theta; float* grad; float* m; float* v; int64_t P, r_end, c_end, actor_begin; int64_t rows;
+  float l2, vcoef_r, max_norm, lr_actor, lr_critic, b1, b2, eps;
+  double* partial; float* scal; float* losses3; double* pow4;
+  float* loss_log; int64_t* cursor; int64_t cursor_step; int nblocks;
+};
+// the seed-batched step's device table: per run the arguments of its stand-alone launches; MrKernArg: a kernel's parameter type
+struct MrMultiEntry {
+  MrArgs g;
+  MrOptArgs o;
+  int active;
+};
+template <bool MULTI> struct MrKernArg {
+  typedef MrArgs Grad;
+  typedef MrOptArgs Opt;
+  static __device__ __forceinline__ const MrOptArgs& opt(const MrOptArgs& x) { return x; }
+};
+template <> struct MrKernArg<true> {
+  typedef const MrMultiEntry* __restrict__ Grad;
+  typedef const MrMultiEntry* __restrict__ Opt;
+  static __device__ __forceinline__ const MrOptArgs& opt(const MrMultiEntry* __restrict__ t) { return t[blockIdx.y].o; }
 };
 
 __host__ __device__ inline int mr_up16(int v) { return (v + 15) & ~15; }
@@ -202,8 +227,18 @@ __device__ unsigned long long g_mr_prof[2][32];
 // (the fraction F of rows inside the bound taken as 1: the loss's gradient is g_KL + F g_PG, and F is known once every row's
 // indicator is, i.e. in the group sum behind this launch).  One cotangent per workgroup: the backward stages are those of the
 // clipped surrogate.  Per-row arithmetic: wide_klpen_split_kernel's (csrc/wide.hip).
-template <bool VEC, int LOSS = MR_PPO>
-__global__ __launch_bounds__(512) void mlp_rows_grad_kernel(MrArgs a) {
+// MULTI (the seed-batched launch, spo_wide_rows_step_multi): the same body for run blockIdx.y of S independent runs of one shape -- `a` is
+// then that run's entry of a device table (what its stand-alone launch receives as kernel arguments; uniform index, const
+// __restrict__: scalar loads) instead of the kernel-argument struct.  blockIdx.x and gridDim.x are the stand-alone launch's, no
+// block waits for another: run r is a slice of the grid.  A block of a run with active == 0 returns before it touches anything else.
+template <bool VEC, int LOSS = MR_PPO, bool MULTI = false>
+__global__ __launch_bounds__(512) void mlp_rows_grad_kernel(typename MrKernArg<MULTI>::Grad arg) {
+  const MrArgs* ap;
+  if constexpr (MULTI) {
+    if (!arg[blockIdx.y].active) return;
+    ap = &arg[blockIdx.y].g;
+  } else ap = &arg;
+  const MrArgs& a = *ap;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, q = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -614,14 +649,12 @@ __global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(MrKlReduceAr
 // the Adam pass behind a device counter -- the last workgroup to arrive wrote the clocks: one same-address atomic per workgroup,
 // +20 us a step with 290 workgroups, still +1.5 us with 19 large ones.)  Same arithmetic, element for element, as
 // spo_wide_reduce_parts + spo_wide_clip_adam_dev_log.
-struct MrOptArgs {
-  const float* parts; int R; int64_t stride;
-  float* theta; float* grad; float* m; float* v; int64_t P, r_end, c_end, actor_begin; int64_t rows;
-  float l2, vcoef_r, max_norm, lr_actor, lr_critic, b1, b2, eps;
-  double* partial; float* scal; float* losses3; double* pow4;
-  float* loss_log; int64_t* cursor; int64_t cursor_step; int nblocks;
-};
-__global__ __launch_bounds__(256) void mlp_rows_prep_kernel(MrOptArgs a) {
+template <bool MULTI = false>
+__global__ __launch_bounds__(256) void mlp_rows_prep_kernel(typename MrKernArg<MULTI>::Opt arg) {
+  if constexpr (MULTI) {
+    if (!arg[blockIdx.y].active) return;
+  }
+  const MrOptArgs a = MrKernArg<MULTI>::opt(arg);        // (a copy: the stand-alone kernel's code is then what it was with `a` its parameter)
   __shared__ double red[4][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double gs = 0.0, pr = 0.0, pc = 0.0;
@@ -653,7 +686,12 @@ __global__ __launch_bounds__(256) void mlp_rows_prep_kernel(MrOptArgs a) {
     if (a.cursor) a.cursor[0] += a.cursor_step;
   }
 }
-__global__ __launch_bounds__(256) void mlp_rows_adam_kernel(MrOptArgs a) {
+template <bool MULTI = false>
+__global__ __launch_bounds__(256) void mlp_rows_adam_kernel(typename MrKernArg<MULTI>::Opt arg) {
+  if constexpr (MULTI) {
+    if (!arg[blockIdx.y].active) return;
+  }
+  const MrOptArgs a = MrKernArg<MULTI>::opt(arg);        // (a copy: the stand-alone kernel's code is then what it was with `a` its parameter)
   __shared__ float sh[4];
   const int tid = threadIdx.x;
   if (tid < 64) {
@@ -727,6 +765,76 @@ size_t mr_kl_lds_floats(const MrNet& critic, const MrNet& actor, int A) {
   const size_t lc = (size_t)mr_lds_floats(critic, A), la = (size_t)mr_lds_floats(actor, A) + (size_t)mr_klx(mr_ap(A));
   return la > lc ? la : lc;
 }
+// ---- the arguments of the fused PPO step's three launches, filled in ONE place for the stand-alone entries
+// (spo_wide_ppo_grad_rows, spo_wide_rows_clip_adam_dev_log) and for every run of a seed-batched table (spo_wide_rows_multi_upload):
+// run r of a table gets its stand-alone launch's arguments by construction.  No checks here: the callers made them.
+void mr_fill_grad(const float* theta, const spo_mlp_net* critic, const spo_mlp_net* actor, const float* obs, const float* act,
+                  const float* logp_old, const float* target_r, const float* target_c, const float* adv, const int64_t* idx,
+                  const int64_t* cursor_dev, int64_t rows, float clip, float* parts, MrArgs* out, size_t* lds_bytes, bool* vec_out) {
+  MrArgs& a = *out;
+  a = MrArgs{};
+  a.theta = theta; a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
+  a.idx = idx; a.cursor = cursor_dev; a.rows = (int)rows; a.R = (int)((rows + 15) / 16); a.clip = clip;
+  const int64_t Pc = spo_mlp_param_count(critic);
+  mr_fill_net(critic, 0, 0, &a.net[0]);
+  mr_fill_net(critic, Pc, 1, &a.net[1]);
+  a.n_nets = 2; a.P = 2 * Pc; a.A = 0; a.ls_off = 2 * Pc;
+  const int A_launch = actor ? actor->dims[actor->n_layers] : 0;
+  size_t lds_floats = (size_t)mr_lds_floats(a.net[0], A_launch);
+  if (actor) {
+    a.A = actor->dims[actor->n_layers];
+    mr_fill_net(actor, 2 * Pc + a.A, 2, &a.net[2]);
+    a.n_nets = 3; a.P = 2 * Pc + a.A + spo_mlp_param_count(actor);
+    const size_t la = (size_t)mr_lds_floats(a.net[2], A_launch);
+    lds_floats = la > lds_floats ? la : lds_floats;
+  }
+  a.parts = parts; a.stride = mr_stride(a.P);
+  *lds_bytes = lds_floats * sizeof(float);
+  bool vec = true;                                   // every weight row a whole number of 16-byte fragments
+  for (int k = 0; k < a.n_nets; ++k)
+    for (int l = 0; l < a.net[k].n; ++l) vec = vec && (a.net[k].d[l] & 3) == 0;
+  *vec_out = vec;
+}
+// the dynamic-LDS limit of the four PPO gradient kernels (stand-alone and table-driven), raised once per device
+int mr_grad_attr_once() {
+  static bool done_dev[SPO_MAX_DEVICES] = {};
+  bool& done = done_dev[spo::current_device_slot()];
+  if (!done) {
+    for (const void* f : {reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true>), reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true, MR_PPO, true>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false, MR_PPO, true>)})
+      if (int rc = spo::hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MR_MAX_LDS),
+                                  "hipFuncSetAttribute(mlp_rows)"))
+        return rc;
+    done = true;
+  }
+  return 0;
+}
+int64_t mr_opt_blocks(int64_t n_params) {
+  const int64_t blocks = (n_params + 255) / 256;
+  return blocks > 1024 ? 1024 : blocks;
+}
+// the optimiser launches' refusals behind the null-pointer check, worded with the entry's name (`who`)
+int mr_check_ranges(const char* who, int64_t n_params, int64_t reward_critic_end, int64_t cost_critic_end, int64_t actor_begin) {
+  SPO_REQUIRE(0 <= reward_critic_end && reward_critic_end <= cost_critic_end && cost_critic_end <= actor_begin && actor_begin <= n_params,
+              "%s: parameter ranges out of order", who);
+  return 0;
+}
+int mr_check_partial(const char* who, int64_t n_params, int partial_capacity) {
+  SPO_REQUIRE((int64_t)partial_capacity >= mr_opt_blocks(n_params) * 3, "%s: partial workspace too small", who);
+  return 0;
+}
+void mr_fill_opt(float* parts, int64_t rows, float* theta, float* grad, float* adam_m, float* adam_v, int64_t n_params,
+                 int64_t reward_critic_end, int64_t cost_critic_end, int64_t actor_begin, const spo_ppo_cfg* cfg, double* pow4_dev,
+                 float* losses3_out, float* scalars4_out, double* partial_ws, float* loss_log_dev, int64_t* cursor_dev,
+                 int64_t cursor_step, MrOptArgs* out) {
+  const int R = (int)((rows + 15) / 16);
+  const int64_t stride = mr_stride(n_params);
+  *out = MrOptArgs{parts, R, stride, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, rows,
+                   cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
+                   cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, partial_ws, scalars4_out, losses3_out, pow4_dev, loss_log_dev,
+                   cursor_dev, cursor_step, (int)mr_opt_blocks(n_params)};
+}
 }  // namespace
 
 #ifdef SPO_MR_PROF
@@ -762,36 +870,11 @@ extern "C" int spo_wide_ppo_grad_rows(const float* theta, const spo_mlp_net* cri
   SPO_REQUIRE(spo_wide_grad_rows_supported(critic, actor, rows), "wide_ppo_grad_rows: shape outside the row-group kernel (rows %lld)",
               (long long)rows);
   MrArgs a{};
-  a.theta = theta; a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.idx = idx; a.cursor = cursor_dev; a.rows = (int)rows; a.R = (int)((rows + 15) / 16); a.clip = clip;
-  const int64_t Pc = spo_mlp_param_count(critic);
-  mr_fill_net(critic, 0, 0, &a.net[0]);
-  mr_fill_net(critic, Pc, 1, &a.net[1]);
-  a.n_nets = 2; a.P = 2 * Pc; a.A = 0; a.ls_off = 2 * Pc;
-  const int A_launch = actor ? actor->dims[actor->n_layers] : 0;
-  size_t lds_floats = (size_t)mr_lds_floats(a.net[0], A_launch);
-  if (actor) {
-    a.A = actor->dims[actor->n_layers];
-    mr_fill_net(actor, 2 * Pc + a.A, 2, &a.net[2]);
-    a.n_nets = 3; a.P = 2 * Pc + a.A + spo_mlp_param_count(actor);
-    const size_t la = (size_t)mr_lds_floats(a.net[2], A_launch);
-    lds_floats = la > lds_floats ? la : lds_floats;
-  }
-  a.parts = parts; a.stride = mr_stride(a.P);
-  const size_t sh = lds_floats * sizeof(float);
+  size_t sh = 0;
+  bool vec = true;
+  mr_fill_grad(theta, critic, actor, obs, act, logp_old, target_r, target_c, adv, idx, cursor_dev, rows, clip, parts, &a, &sh, &vec);
   hipStream_t st = (hipStream_t)stream;
-  bool vec = true;                                   // every weight row a whole number of 16-byte fragments
-  for (int k = 0; k < a.n_nets; ++k)
-    for (int l = 0; l < a.net[k].n; ++l) vec = vec && (a.net[k].d[l] & 3) == 0;
-  static bool done_dev[SPO_MAX_DEVICES] = {};
-  bool& done = done_dev[spo::current_device_slot()];
-  if (!done) {
-    for (const void* f : {reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true>), reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false>)})
-      if (int rc = spo::hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MR_MAX_LDS),
-                                  "hipFuncSetAttribute(mlp_rows)"))
-        return rc;
-    done = true;
-  }
+  if (int rc = mr_grad_attr_once()) return rc;
   if (vec) hipLaunchKernelGGL(mlp_rows_grad_kernel<true>, dim3(a.n_nets * a.R), dim3(512), sh, st, a);
   else hipLaunchKernelGGL(mlp_rows_grad_kernel<false>, dim3(a.n_nets * a.R), dim3(512), sh, st, a);
   SPO_LAUNCH_CHECK("spo_wide_ppo_grad_rows");
@@ -824,22 +907,111 @@ extern "C" int spo_wide_rows_clip_adam_dev_log(float* parts, int64_t rows, float
                                                int64_t* cursor_dev, int64_t cursor_step, void* stream) {
   SPO_REQUIRE(parts && theta && grad && adam_m && adam_v && cfg && pow4_dev && losses3_out && scalars4_out && partial_ws && n_params > 0 &&
                   rows >= 1 && rows <= 16 * MR_MAX_GROUPS, "wide_rows_clip_adam: bad args");
-  SPO_REQUIRE(0 <= reward_critic_end && reward_critic_end <= cost_critic_end && cost_critic_end <= actor_begin && actor_begin <= n_params,
-              "wide_rows_clip_adam: parameter ranges out of order");
+  if (int rc = mr_check_ranges("wide_rows_clip_adam", n_params, reward_critic_end, cost_critic_end, actor_begin)) return rc;
   SPO_REQUIRE(!cursor_dev || cursor_step > 0, "wide_rows_clip_adam: cursor_step must be > 0");
-  int64_t blocks = (n_params + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  SPO_REQUIRE((int64_t)partial_capacity >= blocks * 3, "wide_rows_clip_adam: partial workspace too small");
-  const int R = (int)((rows + 15) / 16);
-  const int64_t stride = mr_stride(n_params);
-  MrOptArgs a{parts, R, stride, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, rows,
-              cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
-              cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, partial_ws, scalars4_out, losses3_out, pow4_dev, loss_log_dev,
-              cursor_dev, cursor_step, (int)blocks};
+  if (int rc = mr_check_partial("wide_rows_clip_adam", n_params, partial_capacity)) return rc;
+  const int64_t blocks = mr_opt_blocks(n_params);
+  MrOptArgs a;
+  mr_fill_opt(parts, rows, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, cfg, pow4_dev,
+              losses3_out, scalars4_out, partial_ws, loss_log_dev, cursor_dev, cursor_step, &a);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mlp_rows_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(mlp_rows_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mlp_rows_prep_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mlp_rows_adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
   SPO_LAUNCH_CHECK("spo_wide_rows_clip_adam_dev_log");
+  return 0;
+}
+
+// ---- the seed-batched fused PPO step: S runs of one shape in the stand-alone step's three launches (include/safepo_hip.h)
+extern "C" int spo_wide_rows_multi_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int n_replicas) {
+  if (!actor || n_replicas < 1 || n_replicas > SPO_WIDE_ROWS_MAX_REPLICAS) return 0;
+  return spo_wide_grad_rows_supported(critic, actor, rows);
+}
+
+extern "C" int64_t spo_wide_rows_multi_table_bytes(int n_replicas) {
+  if (n_replicas < 1 || n_replicas > SPO_WIDE_ROWS_MAX_REPLICAS) return -1;
+  return (int64_t)n_replicas * (int64_t)sizeof(MrMultiEntry);
+}
+
+extern "C" int spo_wide_rows_multi_upload(void* table_dev, const spo_wide_rows_replica* reps_host, int n_replicas,
+                                          const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int64_t cursor_step,
+                                          void* stream) {
+  SPO_REQUIRE(table_dev && reps_host, "wide_rows_multi_upload: null table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_WIDE_ROWS_MAX_REPLICAS, "wide_rows_multi_upload: n_replicas %d outside [1,%d]",
+              n_replicas, SPO_WIDE_ROWS_MAX_REPLICAS);
+  SPO_REQUIRE(spo_wide_rows_multi_supported(critic, actor, rows, n_replicas),
+              "wide_rows_multi_upload: shape outside the row-group kernel (rows %lld)", (long long)rows);
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_wide_rows_replica& p = reps_host[r];
+    SPO_REQUIRE(!p.active || (p.theta && p.adam_m && p.adam_v && p.grad && p.parts && p.obs && p.act && p.logp_old && p.target_r &&
+                              p.target_c && p.adv && p.perm && p.cursor_dev && p.pow4_dev && p.losses3_out && p.scalars4_out &&
+                              p.partial_ws),
+                "wide_rows_multi_upload: replica %d: null pointer", r);
+  }
+  for (int r = 0; r < n_replicas; ++r)
+    for (int q = 0; q < r; ++q) {
+      const spo_wide_rows_replica &x = reps_host[q], &y = reps_host[r];
+      if (!x.active || !y.active) continue;
+      SPO_REQUIRE(x.theta != y.theta, "wide_rows_multi_upload: replicas %d and %d share theta", q, r);
+      SPO_REQUIRE(x.parts != y.parts, "wide_rows_multi_upload: replicas %d and %d share parts", q, r);
+      SPO_REQUIRE(x.cursor_dev != y.cursor_dev, "wide_rows_multi_upload: replicas %d and %d share cursor_dev", q, r);
+    }
+  const int64_t Pc = spo_mlp_param_count(critic);
+  const int64_t P = 2 * Pc + actor->dims[actor->n_layers] + spo_mlp_param_count(actor);
+  if (int rc = mr_check_ranges("wide_rows_multi_upload", P, Pc, 2 * Pc, 2 * Pc)) return rc;
+  for (int r = 0; r < n_replicas; ++r)
+    if (reps_host[r].active)
+      if (int rc = mr_check_partial("wide_rows_multi_upload", P, reps_host[r].partial_capacity)) return rc;
+  SPO_REQUIRE(cursor_step > 0, "wide_rows_multi_upload: cursor_step must be > 0");
+  // (the entries of inactive runs stay zero: their blocks read `active` and nothing else)
+  static thread_local std::vector<MrMultiEntry> tab;
+  tab.assign((size_t)n_replicas, MrMultiEntry{});
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_wide_rows_replica& p = reps_host[r];
+    if (!p.active) continue;
+    MrMultiEntry& e = tab[(size_t)r];
+    size_t sh;
+    bool vec;
+    mr_fill_grad(p.theta, critic, actor, p.obs, p.act, p.logp_old, p.target_r, p.target_c, p.adv, p.perm, p.cursor_dev, rows,
+                 p.cfg.clip, p.parts, &e.g, &sh, &vec);
+    mr_fill_opt(p.parts, rows, p.theta, p.grad, p.adam_m, p.adam_v, P, Pc, 2 * Pc, 2 * Pc, &p.cfg, p.pow4_dev, p.losses3_out,
+                p.scalars4_out, p.partial_ws, p.loss_log_dev, p.cursor_dev, cursor_step, &e.o);
+    e.active = 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return spo::fail(-1, "wide_rows_multi_upload: the stream is under capture (the argument table is copied from host memory: "
+                         "upload outside the capture, capture spo_wide_rows_step_multi)");
+  // stream-ordered behind the replays that still read the previous table; the host table is reused by the next call: wait
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab.data(), (size_t)n_replicas * sizeof(MrMultiEntry), hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(wide_rows_multi table)"))
+    return rc;
+  return spo::hip_check(hipStreamSynchronize(st), "hipStreamSynchronize(wide_rows_multi table)");
+}
+
+extern "C" int spo_wide_rows_step_multi(const void* table_dev, int n_replicas, const spo_mlp_net* critic, const spo_mlp_net* actor,
+                                        int64_t rows, void* stream) {
+  SPO_REQUIRE(table_dev, "wide_rows_step_multi: null table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_WIDE_ROWS_MAX_REPLICAS, "wide_rows_step_multi: n_replicas %d outside [1,%d]",
+              n_replicas, SPO_WIDE_ROWS_MAX_REPLICAS);
+  SPO_REQUIRE(spo_wide_rows_multi_supported(critic, actor, rows, n_replicas),
+              "wide_rows_step_multi: shape outside the row-group kernel (rows %lld)", (long long)rows);
+  // the launch shape of a run: what mr_fill_grad / mr_fill_opt give its stand-alone launches (pointers play no part in it)
+  MrArgs a;
+  size_t sh;
+  bool vec;
+  mr_fill_grad(nullptr, critic, actor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows, 0.f, nullptr, &a, &sh,
+               &vec);
+  const unsigned blocks = (unsigned)mr_opt_blocks(a.P);
+  const MrMultiEntry* tab = static_cast<const MrMultiEntry*>(table_dev);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mr_grad_attr_once()) return rc;
+  const dim3 ggrid((unsigned)(a.n_nets * a.R), (unsigned)n_replicas), ogrid(blocks, (unsigned)n_replicas);
+  if (vec) hipLaunchKernelGGL((mlp_rows_grad_kernel<true, MR_PPO, true>), ggrid, dim3(512), sh, st, tab);
+  else hipLaunchKernelGGL((mlp_rows_grad_kernel<false, MR_PPO, true>), ggrid, dim3(512), sh, st, tab);
+  hipLaunchKernelGGL(mlp_rows_prep_kernel<true>, ogrid, dim3(256), 0, st, tab);
+  hipLaunchKernelGGL(mlp_rows_adam_kernel<true>, ogrid, dim3(256), 0, st, tab);
+  SPO_LAUNCH_CHECK("spo_wide_rows_step_multi");
   return 0;
 }
 

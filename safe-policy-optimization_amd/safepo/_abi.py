@@ -48,6 +48,15 @@ class CriticFitSplitReplica(Structure):
                 ("regions2", c_void_p * 2), ("step0", c_uint32), ("cfg", PpoCfg), ("active", c_int)]
 
 
+class WideRowsReplica(Structure):
+    """spo_wide_rows_replica (include/safepo_hip.h): one run of a seed-batched row-group step (spo_wide_rows_step_multi)."""
+    _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("grad", c_void_p), ("parts", c_void_p),
+                ("obs", c_void_p), ("act", c_void_p), ("logp_old", c_void_p), ("target_r", c_void_p), ("target_c", c_void_p),
+                ("adv", c_void_p), ("perm", c_void_p), ("cursor_dev", c_void_p), ("pow4_dev", c_void_p), ("losses3_out", c_void_p),
+                ("scalars4_out", c_void_p), ("partial_ws", c_void_p), ("partial_capacity", c_int), ("loss_log_dev", c_void_p),
+                ("cfg", PpoCfg), ("active", c_int)]
+
+
 class UpdateExReplica(Structure):
     """spo_update_ex_replica (include/safepo_hip.h): one run of a seed-batched spo_update_iter_ex launch (FOCOPS, CUP)."""
     _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step_critics", c_int64),
@@ -102,6 +111,7 @@ RS_MAX_REPLICAS = 32                               # include/safepo_hip.h SPO_RS
 RS_CRITIC_MAX_REPLICAS = 24                        # include/safepo_hip.h SPO_RS_CRITIC_MAX_REPLICAS
 UPDATE_EX_MAX_REPLICAS = 32                        # include/safepo_hip.h SPO_UPDATE_EX_MAX_REPLICAS
 CRITIC_SPLIT_MAX_REPLICAS = 32                     # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
+WIDE_ROWS_MAX_REPLICAS = 32                        # include/safepo_hip.h SPO_WIDE_ROWS_MAX_REPLICAS
 KS_MAX_REPLICAS = 16                               # include/safepo_hip.h SPO_KS_MAX_REPLICAS
 MA_LS_WS_DOUBLES, MA_CG_WS_DOUBLES = 4096, 520     # include/safepo_hip.h SPO_MA_LS_WS_DOUBLES, SPO_MA_CG_WS_DOUBLES
 
@@ -131,6 +141,10 @@ PROTOTYPES = {
     "spo_wide_reduce_parts": (c_int, [P, c_int64, c_int64, c_int, P, P, P]),
     "spo_wide_rows_clip_adam_dev_log": (c_int, [P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, POINTER(PpoCfg), P, P, P, P,
                                                 c_int, P, P, c_int64, P]),
+    "spo_wide_rows_multi_supported": (c_int, [POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int]),
+    "spo_wide_rows_multi_table_bytes": (c_int64, [c_int]),
+    "spo_wide_rows_multi_upload": (c_int, [P, POINTER(WideRowsReplica), c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int64, P]),
+    "spo_wide_rows_step_multi": (c_int, [P, c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, P]),
     "spo_wide_kl_penalty_grad_rows_supported": (c_int, [POINTER(MlpNet), POINTER(MlpNet), c_int64]),
     "spo_wide_kl_penalty_rows_part_floats": (c_int64, [c_int64, c_int64, c_int64]),
     "spo_wide_kl_penalty_grad_rows": (c_int, [P, POINTER(MlpNet), POINTER(MlpNet)] + [P] * 10 + [c_int64, c_float, c_float, c_int, P, P]),

@@ -159,7 +159,12 @@ class PPOLagEngineGroup(_EngineGroup):
     A group made entirely of one-GPU WidePPOLagEngines whose minibatch step is on the feature-split kernel
     (_feature_split_kernel_ok: hidden [64, 64], up to 512 observations / 32 actions, HumanoidVelocity's 376 / 17) is taken too:
     its learning iterations share one spo_update_iter_ex_ks_multi launch (csrc/update_ks.hip: run r on its own
-    3 x ceil(obs_dim / 64) co-XCD workgroups), each bit for bit its own spo_ppo_lag_update_iter_ks / spo_update_iter_ex_ks."""
+    3 x ceil(obs_dim / 64) co-XCD workgroups), each bit for bit its own spo_ppo_lag_update_iter_ks / spo_update_iter_ex_ks.
+    A third kind: one-GPU WidePPOLagEngines of one shape NONE of which is on the feature-split kernel -- hidden_sizes other than
+    [64, 64], act_dim > 32 or obs_dim > 512 --, whose PPO-Lagrangian step is the row-group gradient kernel with the fused
+    optimiser (csrc/mlp_rows.hip).  Where _rows_batched holds, the whole minibatches of a learning iteration are replayed from
+    one captured graph of spo_wide_rows_step_multi (run r = blockIdx.y of the step's three launches), each run bit for bit its
+    own graph-replayed pass; update() only (FOCOPS / CUP step such a group engine by engine)."""
 
     def __init__(self, engines, rngs=None):
         from safepo.common.engine import PPOLagEngine, WidePPOLagEngine
@@ -167,10 +172,20 @@ class PPOLagEngineGroup(_EngineGroup):
         if not engines:
             raise ValueError("PPOLagEngineGroup: no engines")
         # the feature-split form: every engine a WidePPOLagEngine on that kernel (mixed groups are refused below)
-        self._ks = all(type(e) is WidePPOLagEngine for e in engines)
+        wide = all(type(e) is WidePPOLagEngine for e in engines)
+        # the row-group form: every engine a WidePPOLagEngine and none of them on the feature-split kernel
+        self._rows = wide and not any(e._feature_split_kernel_ok(e._cfg_struct()) for e in engines)
+        self._ks = wide and not self._rows
+        self._rows_graphs = {}
 
         def check_type(i, e):
-            if self._ks:
+            if self._rows:
+                if e.comm.world_size != 1:
+                    raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
+                if list(e.policy.hidden_sizes) != list(engines[0].policy.hidden_sizes):
+                    raise _abi.SpoError(f"PPOLagEngineGroup: engine {i} has hidden_sizes {list(e.policy.hidden_sizes)}, engine 0 has "
+                                        f"{list(engines[0].policy.hidden_sizes)}")
+            elif self._ks:
                 if e.comm.world_size != 1:
                     raise _abi.SpoError("PPOLagEngineGroup: data-parallel engines cannot be grouped (world size 1 only)")
                 if not e._feature_split_kernel_ok(e._cfg_struct()):
@@ -194,6 +209,8 @@ class PPOLagEngineGroup(_EngineGroup):
         c0 = cfgs[0]
         if any(c.batch != c0.batch for c in cfgs):
             return False
+        if self._rows:
+            return self._rows_batched(cfgs)
         if self._ks:
             return self._ks_batched(cfgs)
         if os.environ.get("SPO_FORCE_DP", "0") == "1":
@@ -208,6 +225,103 @@ class PPOLagEngineGroup(_EngineGroup):
         c0 = cfgs[0]
         return (all(e._feature_split_kernel_ok(c) for e, c in zip(self.engines, cfgs))
                 and bool(self.lib.spo_update_ks_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, len(self.engines))))
+
+    def _rows_batched(self, cfgs) -> bool:
+        """A group of WidePPOLagEngines on the row-group kernel: one spo_wide_rows_step_multi per minibatch step where every
+        engine's own pass would be the graph-replayed fused step -- world size 1, wide.rows_grad_ok(batch), the fused optimiser
+        on (SPO_WIDE_ROWS_FUSED not 0), 0 < batch <= graph_max_batch with more than two minibatches, not on the feature-split
+        kernel (all read at every call, as the engine reads them) -- and the library takes this many runs."""
+        es, c0 = self.engines, cfgs[0]
+        n_mb = (es[0].M + c0.batch - 1) // max(c0.batch, 1)
+        return (os.environ.get("SPO_WIDE_ROWS_FUSED", "1") != "0" and n_mb > 2
+                and all(e.comm.world_size == 1 and 0 < c.batch <= e.graph_max_batch and e.wide.rows_grad_ok(c.batch)
+                        and not e._feature_split_kernel_ok(c) for e, c in zip(es, cfgs))
+                and bool(self.lib.spo_wide_rows_multi_supported(es[0].wide.net_c, es[0].wide.net_a, c0.batch, len(es))))
+
+    def _rows_learning_iter_all(self, cfgs, perms, active):
+        """WidePPOLagEngine.learning_iter's graph-replayed pass for the active runs: every run's device clocks from its own host
+        step counts (_sync_pow4) and its own PermWindow loaded with its own shuffle, the argument table uploaded once (outside any
+        capture), the whole minibatches replayed from ONE captured graph of spo_wide_rows_step_multi (eight steps per graph launch:
+        SPO_WIDE_GRAPH_UNROLL, as the engine), the ragged last minibatch through each engine's own eager minibatch_step."""
+        from safepo.common.wide import PermWindow
+        es, S, e0, lib = self.engines, len(self.engines), self.engines[0], self.lib
+        batch, M = int(cfgs[0].batch), e0.M
+        n_mb, n_full = (M + batch - 1) // batch, M // batch
+        nc, na = e0.wide.net_c, e0.wide.net_a
+        ent = self._rows_graphs.get(batch)
+        if ent is None:
+            ent = self._rows_graphs[batch] = {
+                "wins": [PermWindow(M, batch, e.dev) for e in es],
+                "loss3": [torch.full((3,), float("nan"), dtype=torch.float32, device=e.dev) for e in es],
+                "parts": [e.wide._scratch.setdefault(("parts", batch, False), torch.zeros(
+                    int(lib.spo_wide_grad_rows_part_floats(e.wide.P, batch)), dtype=torch.float32, device=e.dev)) for e in es],
+                "table": torch.zeros(int(lib.spo_wide_rows_multi_table_bytes(S)), dtype=torch.uint8, device=e0.dev),
+                "graphs": None}
+        wins = ent["wins"]
+        perms64, losses = [None] * S, [None] * S
+        reps = (_abi.WideRowsReplica * S)()
+        for i, e in enumerate(es):
+            r = reps[i]
+            r.cfg, r.active = cfgs[i], int(active[i] and perms[i] is not None)
+            if not r.active:
+                continue
+            perms64[i] = _abi.require_gpu_tensor(perms[i], "perm", torch.int32).long()
+            losses[i] = torch.empty((n_mb, 3), dtype=torch.float32, device=e.dev)
+            e._sync_pow4()
+            wins[i].load(perms64[i])
+            d, M_ = e.buffer.data, e.M
+            r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
+            r.grad, r.parts = _abi.ptr(e.flat_grad), _abi.ptr(ent["parts"][i])
+            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(e.buffer.adv_mix)
+            r.perm, r.cursor_dev, r.pow4_dev = _abi.ptr(wins[i].perm), _abi.ptr(wins[i].cursor), _abi.ptr(e.pow4)
+            r.losses3_out, r.scalars4_out = _abi.ptr(ent["loss3"][i]), _abi.ptr(e.scal4)
+            r.partial_ws, r.partial_capacity = _abi.ptr(e.loss_partials), e.loss_partials.numel()
+            r.loss_log_dev = _abi.ptr(wins[i].loss_log)
+        idx = [i for i in range(S) if reps[i].active]
+        if not idx:
+            return losses
+        table = ent["table"]
+
+        def step():
+            _abi.check(lib.spo_wide_rows_step_multi(_abi.ptr(table), S, nc, na, batch, _abi.stream_ptr()), "spo_wide_rows_step_multi")
+
+        _abi.check(lib.spo_wide_rows_multi_upload(_abi.ptr(table), reps, S, nc, na, batch, batch, _abi.stream_ptr()),
+                   "spo_wide_rows_multi_upload")
+        if ent["graphs"] is None:
+            # first use: one eager step for the lazy per-kernel set-up, its effects on every taking-part run's parameters / moments /
+            # clocks / gradient / cursor undone (as _graphed_pass does for one engine), then the captures
+            state = [t for i in idx for t in (es[i].policy.theta, es[i].adam_m, es[i].adam_v, es[i].pow4, es[i].flat_grad, wins[i].cursor)]
+            snap = [t.clone() for t in state]
+            step()
+            for t, b in zip(state, snap):
+                t.copy_(b)
+            torch.cuda.synchronize(e0.dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                step()
+            unroll = max(1, int(os.environ.get("SPO_WIDE_GRAPH_UNROLL", "8")))
+            g_many = None
+            if unroll > 1:
+                g_many = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_many, capture_error_mode="thread_local"):
+                    for _ in range(unroll):
+                        step()
+            ent["graphs"] = (g, g_many, unroll)         # (the table, windows, loss and part buffers live in `ent` beside them)
+        g, g_many, unroll = ent["graphs"]
+        done = 0
+        if g_many is not None:
+            for _ in range(n_full // unroll):
+                g_many.replay()
+            done = (n_full // unroll) * unroll
+        for _ in range(n_full - done):
+            g.replay()
+        for i in idx:
+            losses[i][:n_full].copy_(wins[i].loss_log[:n_full])
+            es[i].adam_step += n_full
+            for k in range(n_full, n_mb):               # (the ragged last minibatch: eager, host clocks, as stand-alone)
+                es[i].minibatch_step(perms64[i][k * batch:(k + 1) * batch], losses[i][k], cfg=cfgs[i])
+        return losses
 
     def _launch_ex(self, entry, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill=True):
         """One launch of `entry` (spo_update_iter_ex_multi or spo_update_iter_ex_ks_multi) for the active runs; the clocks
@@ -247,6 +361,8 @@ class PPOLagEngineGroup(_EngineGroup):
         cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
         if not self.batched(cfgs):
             return [e.learning_iter(perms[i]) if active[i] else None for i, e in enumerate(self.engines)]
+        if self._rows:
+            return self._rows_learning_iter_all(cfgs, perms, active)
         if self._ks:
             # spo_ppo_lag_update_iter_ks is spo_update_iter_ex_ks with the clipped surrogate on adv_mix and equal clocks
             return self._launch_ex("spo_update_iter_ex_ks_multi", cfgs, perms, [e.buffer.adv_mix for e in self.engines],
@@ -311,6 +427,8 @@ class PPOLagEngineGroup(_EngineGroup):
         c0 = cfgs[0]
         if any(c.batch != c0.batch for c in cfgs):
             return False
+        if self._rows:
+            return False                         # (the KL-penalty loss has no table-driven row-group form)
         if self._ks:
             return self._ks_batched(cfgs)
         return bool(self.lib.spo_update_ex_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss), len(self.engines))

@@ -23,7 +23,7 @@ from safepo.common.lagrange import Lagrange, PIDLagrangian
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import isaac_gym_map, refuse_seed_batch, seed_list
+from safepo.utils.config import WIDE_ROWS_NOT_BUILT, fold_overrides, isaac_gym_map, refuse_seed_batch, seed_list
 
 NO_CLIP = 1e30      # clamp(ratio, 1-1e30, 1+1e30) is the identity: pg's unclipped surrogate on the same kernel
 
@@ -108,6 +108,8 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
     if variant != "ppo" and getattr(args, "batch_wide_obs", False) and not getattr(args, "batch_update", False):
         raise SystemExit("--batch-wide-obs True widens --batch-update True for focops and cup (hidden [64, 64], up to 512 observations "
                          "/ 32 actions: HumanoidVelocity): give both")
+    if variant != "ppo" and getattr(args, "batch_wide_rows", False):
+        raise SystemExit(WIDE_ROWS_NOT_BUILT.format(what="focops and cup"))
     if len(seed_list(args)) > 1:
         if variant != "ppo" and not getattr(args, "batch_update", False):
             refuse_seed_batch(args, "focops and cup",
@@ -127,7 +129,7 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
     if args.task in isaac_gym_map:
         raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
     config = dict(default_cfg)
-    config.update(getattr(args, "cfg_override", None) or {})
+    fold_overrides(config, args)
     config = {k: v for k, v in config.items() if v is not None}      # an override of None drops the key (e.g. batch_size,
     config["clip"] = NO_CLIP if clip is None else clip              # so that num_mini_batch decides as in isaac_gym_specific_cfg)
 
@@ -241,6 +243,31 @@ def _ks_shape_ok(obs_dim: int, act_dim: int, config: dict, rows: int) -> bool:
     return os.environ.get("SPO_WIDE_KS", "1") != "0" and bool(_abi.load().spo_ks_supported(int(obs_dim), int(act_dim), int(batch)))
 
 
+def _require_rows_batch(obs_dim: int, act_dim: int, config: dict, rows: int, n_seeds: int) -> None:
+    """--batch-wide-rows True: SystemExit naming the limit unless `n_seeds` one-GPU WidePPOLagEngines of this shape and config
+    would step as one seed-batched row-group launch (PPOLagEngineGroup._rows_batched, answered before an engine exists)."""
+    lib = _abi.load()
+    hidden = [int(h) for h in config["hidden_sizes"]]
+    batch = int(config.get("batch_size", max(rows // config.get("num_mini_batch", 1), 1)))
+    shape = f"{obs_dim} observations / {act_dim} actions, hidden_sizes {hidden}, minibatches of {batch} rows"
+    if n_seeds > _abi.WIDE_ROWS_MAX_REPLICAS:
+        raise SystemExit(f"--seeds: at most {_abi.WIDE_ROWS_MAX_REPLICAS} seeds share the row-group step's launches "
+                         f"(--batch-wide-rows True), got {n_seeds}")
+    if not 1 <= act_dim <= _abi.WIDE_MAX_ACT or not 1 <= len(hidden) <= 4:
+        raise SystemExit(f"--batch-wide-rows True: {shape} is outside the wide-network path (act_dim <= {_abi.WIDE_MAX_ACT}, up to four "
+                         "hidden layers)")
+    net_c, net_a = _abi.MlpNet.of([obs_dim] + hidden + [1]), _abi.MlpNet.of([obs_dim] + hidden + [act_dim])
+    if not lib.spo_wide_rows_multi_supported(net_c, net_a, batch, n_seeds):
+        raise SystemExit(f"--batch-wide-rows True: {shape} does not fit the row-group kernel (at most 256 rows per minibatch, every "
+                         "level's images of a 16-row group within one CU's 160 KB of LDS; SPO_WIDE_ROWS not 0): one process per seed")
+    if os.environ.get("SPO_WIDE_ROWS_FUSED", "1") == "0":
+        raise SystemExit("--batch-wide-rows True needs the fused optimiser of the row-group step (SPO_WIDE_ROWS_FUSED=0 is set)")
+    graph_max = int(os.environ.get("SPO_WIDE_GRAPH_MAX_BATCH", "2048"))
+    if not (0 < batch <= graph_max and (rows + batch - 1) // batch > 2):
+        raise SystemExit(f"--batch-wide-rows True: {shape} over {rows} rows is not a graph-replayed pass (more than two minibatches of "
+                         f"at most SPO_WIDE_GRAPH_MAX_BATCH = {graph_max} rows): nothing to share, one process per seed")
+
+
 class _SeedRun:
     """One run of a seed-batched process: what run() holds in local variables, per seed."""
 
@@ -265,7 +292,7 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
     if args.task in isaac_gym_map:
         raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
     config = dict(default_cfg)
-    config.update(getattr(args, "cfg_override", None) or {})
+    fold_overrides(config, args)
     config = {k: v for k, v in config.items() if v is not None}
     config["clip"] = NO_CLIP if clip is None else clip
     log_dirs = getattr(args, "log_dirs", None) or [os.path.join(args.log_dir, "-".join(["seed", str(s).zfill(3)])) for s in seeds]
@@ -278,6 +305,7 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
     epochs = total_steps // steps_per_epoch
 
     wide_obs = bool(getattr(args, "batch_wide_obs", False))
+    wide_rows = bool(getattr(args, "batch_wide_rows", False))
     if wide_obs and list(config["hidden_sizes"]) == [64, 64] and len(seeds) > _abi.KS_MAX_REPLICAS:
         raise SystemExit(f"--seeds: at most {_abi.KS_MAX_REPLICAS} seeds share a launch with --batch-wide-obs True (8 above 256 "
                          f"observations), got {len(seeds)}")
@@ -306,6 +334,13 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
                     cap = max(n for n in range(1, _abi.KS_MAX_REPLICAS + 1) if lib.spo_update_ks_multi_supported(D, A, 1, n))
                     raise SystemExit(f"--seeds: at most {cap} seeds share the feature-split kernel's launch at {D} observations "
                                      f"(--batch-wide-obs True: {_abi.KS_MAX_REPLICAS} up to 256 observations, 8 up to 512), got {len(seeds)}")
+                r.engine = WidePPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
+            elif wide_rows and not (list(config["hidden_sizes"]) == [64, 64] and _ks_shape_ok(
+                    obs_space.shape[0], act_space.shape[0], config, args.num_envs * local_steps_per_epoch)):
+                # --batch-wide-rows True: the shapes WidePPOLagEngine steps through the row-group kernel (csrc/mlp_rows.hip) --
+                # WidePPOLagEngines, whose minibatch steps share the three launches of spo_wide_rows_step_multi.  Whether the shape and
+                # the seed count fit is known once the (first) environment tells the dims: checked before anything is logged
+                _require_rows_batch(obs_space.shape[0], act_space.shape[0], config, args.num_envs * local_steps_per_epoch, len(seeds))
                 r.engine = WidePPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
             else:
                 raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "

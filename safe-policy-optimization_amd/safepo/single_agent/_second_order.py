@@ -23,7 +23,7 @@ from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
 from safepo.single_agent.cpo import _to_dev, make_engine, run_seed_batch
-from safepo.utils.config import critic_seed_batch, isaac_gym_map, seed_list
+from safepo.utils.config import critic_seed_batch, fold_overrides, isaac_gym_map, seed_list
 
 
 def _actor_update(engine, logger, lagrange, comm, device, line_search: bool):
@@ -108,7 +108,7 @@ def run(args, cfg_env, default_cfg: dict, line_search: bool, use_lagrange: bool)
     if args.task in isaac_gym_map:
         raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
     config = dict(default_cfg)
-    config.update(getattr(args, "cfg_override", None) or {})
+    fold_overrides(config, args)
     require_equal_shards(args.num_envs, comm)
     _, n_local = shard_envs(args.num_envs, comm)          # one process per GPU: a contiguous shard of the envs each
     env, obs_space, act_space = make_sa_mujoco_env(num_envs=n_local, env_id=args.task, seed=args.seed + 1000 * comm.rank,

@@ -26,7 +26,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from safepo.utils.config import CRITIC_KS_BATCH_FIGURES, CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES
+from safepo.utils.config import CRITIC_KS_BATCH_FIGURES, CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES, ROWS_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -90,6 +90,13 @@ def parse_args(argv=None):
                         "/ cppo_pid, and with --batch-focops-cup for focops / cup, at most 8 seeds per subprocess "
                         "(--batch-wide-obs True on those commands).  " + KS_BATCH_FIGURES + "  Default off: HumanoidVelocity keeps "
                         "one subprocess per seed")
+    p.add_argument("--hidden-sizes", type=int, nargs="+", default=None,
+                   help="--hidden-sizes of every command (widths of the hidden layers; default: the scripts' [64, 64]).  Any other "
+                        "widths run on the wide-network kernels: no script's --seeds form takes them except with --batch-wide-rows")
+    p.add_argument("--batch-wide-rows", action="store_true",
+                   help="with --seeds-per-run and --hidden-sizes other than 64 64: group ppo_lag / ppo / pg / cppo_pid (up to 32 seeds "
+                        "per subprocess, --batch-wide-rows True on those commands): their minibatch steps share the three launches of "
+                        "the row-group step.  " + ROWS_BATCH_FIGURES + "  Default off: such widths keep one subprocess per seed")
     return p.parse_args(argv)
 
 
@@ -100,6 +107,7 @@ CRITIC_BATCH_MAX = 24                                         # include/safepo_h
 WIDE_OBS_NAV_ROBOTS = ("Ant", "Car", "Doggo", "Racecar")      # navigation tasks with 65 .. 128 observations: WideCPOEngine
 CRITIC_SPLIT_BATCH_MAX = 32                                   # include/safepo_hip.h SPO_CRITIC_SPLIT_MAX_REPLICAS
 CRITIC_KS_BATCH_MAX = 8                                       # seeds per subprocess at 376 observations: one run per XCD label
+ROWS_BATCH_MAX = 32                                           # include/safepo_hip.h SPO_WIDE_ROWS_MAX_REPLICAS
 KS_BATCH_MAX = 8                                              # spo_update_ks_multi_supported at 376 observations (S = 6: one run per XCD)
 
 
@@ -171,8 +179,19 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                              and _takes_critic_ks_batch(algo, task))
                 wide = (getattr(args, "batch_wide_obs", False)
                         and _takes_wide_obs_batch(algo, task, getattr(args, "batch_focops_cup", False)))
+                # --hidden-sizes other than [64, 64]: every script steps on the wide-network kernels, whose only seed-batched form is
+                # the row-group step of the PPO family (--batch-wide-rows)
+                hidden = getattr(args, "hidden_sizes", None)
+                custom = hidden is not None and [int(h) for h in hidden] != [64, 64]
+                rows = custom and getattr(args, "batch_wide_rows", False) and algo in SEED_BATCHED_ALGOS
+                if custom:
+                    critic = klpen = split = critic_ks = wide = False
                 runs = [[s] for s in group]
-                if len(group) > 1 and (_takes_seeds(algo, task) or klpen):
+                if len(group) > 1 and rows:
+                    runs = [group[i:i + ROWS_BATCH_MAX] for i in range(0, len(group), ROWS_BATCH_MAX)]
+                elif custom:
+                    pass
+                elif len(group) > 1 and (_takes_seeds(algo, task) or klpen):
                     runs = [group]
                 elif len(group) > 1 and wide:
                     runs = [group[i:i + KS_BATCH_MAX] for i in range(0, len(group), KS_BATCH_MAX)]
@@ -191,7 +210,9 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                         + (["--batch-critic-fit", "True", "--batch-critic-fit-split", "True"] if batched and split else [])
                         + (["--batch-critic-fit", "True", "--batch-critic-fit-feature-split", "True"] if batched and critic_ks else [])
                         + (["--batch-update", "True"] if batched and (klpen or (wide and algo in KLPEN_BATCHED_ALGOS)) else [])
-                        + (["--batch-wide-obs", "True"] if batched and wide else []) + [
+                        + (["--batch-wide-obs", "True"] if batched and wide else [])
+                        + (["--hidden-sizes"] + [str(int(h)) for h in hidden] if hidden is not None else [])
+                        + (["--batch-wide-rows", "True"] if batched and rows else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
                         str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))

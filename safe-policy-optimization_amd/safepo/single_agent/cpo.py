@@ -27,7 +27,7 @@ from safepo.common.env import make_sa_mujoco_env
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import critic_seed_batch, isaac_gym_map, run_as_script, seed_list
+from safepo.utils.config import critic_seed_batch, fold_overrides, isaac_gym_map, run_as_script, seed_list
 
 STEP_FRACTION = 0.8
 CPO_SEARCHING_STEPS = 15
@@ -872,7 +872,7 @@ def main(args, cfg_env=None, _update="cpo"):
     if args.task in isaac_gym_map:
         raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
     config = dict(default_cfg)
-    config.update(getattr(args, "cfg_override", None) or {})
+    fold_overrides(config, args)
     require_equal_shards(args.num_envs, comm)
     _, n_local = shard_envs(args.num_envs, comm)          # one process per GPU: a contiguous shard of the envs each
     env, obs_space, act_space = make_sa_mujoco_env(num_envs=n_local, env_id=args.task, seed=args.seed + 1000 * comm.rank,
@@ -963,7 +963,7 @@ def run_seed_batch(args, default_cfg: dict, rollout, actor_update, log_epoch, ma
     if args.task in isaac_gym_map:
         raise NotImplementedError("Isaac Gym tasks (isaac_gym_specific_cfg) are not part of this build")
     config = dict(default_cfg)
-    config.update(getattr(args, "cfg_override", None) or {})
+    fold_overrides(config, args)
     log_dirs = getattr(args, "log_dirs", None) or [os.path.join(args.log_dir, "-".join(["seed", str(s).zfill(3)])) for s in seeds]
     if len(log_dirs) != len(seeds):
         raise ValueError("args.log_dirs: one directory per seed")

@@ -62,6 +62,21 @@ def seed_list(args) -> list:
     return [int(s) for s in seeds] if seeds else [int(args.seed)]
 
 
+def fold_overrides(config: dict, args) -> dict:
+    """A script's default_cfg with the command line's and the caller's overrides folded in: --hidden-sizes first, then
+    args.cfg_override (set programmatically), which wins."""
+    hidden = getattr(args, "hidden_sizes", None)
+    if hidden is not None:
+        config["hidden_sizes"] = [int(h) for h in hidden]
+    config.update(getattr(args, "cfg_override", None) or {})
+    return config
+
+
+WIDE_ROWS_NOT_BUILT = ("--batch-wide-rows True is not available for {what}: the seed-batched row-group step is built for the clipped "
+                       "surrogate of ppo_lag, ppo, pg and cppo_pid only; the KL-penalty loss of focops / cup and the wide critic fit of "
+                       "the second-order scripts have no such form.  Run one process per seed")
+
+
 def refuse_seed_batch(args, what: str, hint: str = "") -> None:
     """For the scripts without a seed-batched form: more than one seed is an error, not a silent single run."""
     if len(seed_list(args)) > 1:
@@ -73,6 +88,8 @@ def refuse_seed_batch(args, what: str, hint: str = "") -> None:
 def critic_seed_batch(args) -> bool:
     """The second-order scripts (cpo, pcpo, rcpo, trpo_lag, trpo, natural_pg): several seeds run in one process only with
     --batch-critic-fit True (their critic fits then share one launch per iteration); without it they are refused as ever."""
+    if getattr(args, "batch_wide_rows", False):
+        raise SystemExit(WIDE_ROWS_NOT_BUILT.format(what="the second-order scripts"))
     if getattr(args, "batch_critic_fit_split", False) and not getattr(args, "batch_critic_fit", False):
         raise SystemExit("--batch-critic-fit-split True widens --batch-critic-fit True (65-128 observations, up to 32 seeds): give both")
     if getattr(args, "batch_critic_fit_feature_split", False) and not getattr(args, "batch_critic_fit", False):
@@ -125,6 +142,15 @@ KS_BATCH_FIGURES = ("Measured at 376 / 17, 4096 x 128 rows, batch 64: one clippe
                     "seeds at 376 / 17: Time/Update 3.06 s against 21.31 s, one sample each (profiles/seed_batch_ks/step_times.txt).")
 
 
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_rows/step_times.txt)
+ROWS_BATCH_FIGURES = ("Measured at 60 / 8, 4096 x 128 rows, batch 64: with hidden [128, 128] one step of ALL seeds takes 32.7 / 36.2 / 44.3 / "
+                      "52.4 / 91.3 us at 2 / 4 / 8 / 16 / 32 seeds against 30.3 us per seed one after the other (1.87 x / 3.38 x / 5.55 x / "
+                      "9.38 x / 10.84 x the aggregate step rate; the time per seed-step stops falling between 16 and 32 seeds, where 12 "
+                      "gradient workgroups per seed pass the card's 256 CUs); with [256, 256] 68.0 / 76.9 / 100.1 / 138.5 / 267.3 us against "
+                      "59.8 per seed (1.76 x / 3.11 x / 4.78 x / 6.90 x / 7.16 x: flat beyond 16); one seed alone: 30.82 against 30.28 us, "
+                      "which is why one seed stays `--seed` (profiles/seed_batch_rows/step_times.txt).")
+
+
 def single_agent_args(argv=None):
     """-> (args, cfg_env).  cfg_env is {} for non-Isaac tasks (reference config.py:172-191)."""
     parser = build_parser()
@@ -164,6 +190,18 @@ def single_agent_args(argv=None):
                              "steps then share one launch per pass (spo_update_iter_ex_ks_multi: up to 16 seeds up to 256 observations, "
                              "8 up to 512; 3 x ceil(obs_dim / 64) workgroups each, run r on XCD r mod 8), each seed the run its `--seed` "
                              "would be.  " + KS_BATCH_FIGURES + "  Default False: such tasks are refused with several seeds")
+    parser.add_argument("--hidden-sizes", type=int, nargs="+", default=None,
+                        help="widths of the hidden layers of all three networks (reference model.py:131), e.g. --hidden-sizes 128 128.  "
+                             "Default: the script's default_cfg ([64, 64]: the persistent kernels).  Any other widths run on the "
+                             "wide-network kernels; an args.cfg_override[\"hidden_sizes\"] set programmatically still wins")
+    parser.add_argument("--batch-wide-rows", type=_bool, default=False,
+                        help="ppo_lag, ppo, pg and cppo_pid with --seeds: also take shapes that step on the wide-network path's "
+                             "row-group kernel -- hidden sizes other than [64, 64] (--hidden-sizes), more than 512 observations or more "
+                             "than 32 actions, minibatches of up to 256 rows whose images fit one CU's LDS -- whose minibatch steps then "
+                             "share the step's three launches (spo_wide_rows_step_multi: up to 32 seeds, run r a slice of the grid; no "
+                             "per-XCD budget: no workgroup waits for another), each seed the run its `--seed` would be.  "
+                             + ROWS_BATCH_FIGURES + "  Default False: such shapes are refused with several seeds; focops, cup and the "
+                             "second-order scripts refuse the flag (not built)")
     args = parser.parse_args(argv)
     if args.task in isaac_gym_map:
         raise Exception("Please install isaacgym to run Isaac Gym tasks!")
