@@ -1412,7 +1412,7 @@ __global__ void norm_finish_kernel(const double* partial, int n, float* norm_out
 }
 __global__ void ma_adam_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m,
                                float* __restrict__ v, int64_t n, const float* __restrict__ norm, float max_norm, int use_clip,
-                               float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+                               float lr, float omb1, float b2, float omb2, float eps, float wd, float bc1, float bc2_sqrt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float coef = 1.f;
@@ -1423,8 +1423,10 @@ __global__ void ma_adam_kernel(float* __restrict__ theta, const float* __restric
   float g = grad[i] * coef;
   const float p = theta[i];
   if (wd != 0.f) g += wd * p;
-  const float mm = m[i] + (1.f - b1) * (g - m[i]);                       // exp_avg.lerp_
-  const float vv = v[i] * b2 + (1.f - b2) * g * g;
+  // omb1 = 1 - beta1, omb2 = 1 - beta2 formed in double on the host, as torch forms its lerp weight and addcmul value from python
+  // floats: 1.f - 0.999f is 0.99998713e-3, 1.3e-5 (relative) off the reference's float(0.001)
+  const float mm = m[i] + omb1 * (g - m[i]);                              // exp_avg.lerp_
+  const float vv = v[i] * b2 + omb2 * g * g;
   m[i] = mm; v[i] = vv;
   const float denom = sqrtf(vv) / bc2_sqrt + eps;
   theta[i] = p - (lr / bc1) * (mm / denom);
@@ -1862,7 +1864,8 @@ extern "C" int spo_ma_clip_adam(float* theta, const float* grad, float* adam_m, 
   const double t = (double)(adam_step_host + 1);
   const float bc1 = (float)(1.0 - pow(b1, t)), bc2s = (float)sqrt(1.0 - pow(b2, t));
   hipLaunchKernelGGL(ma_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, theta, grad, adam_m, adam_v, n,
-                     grad_norm_out, max_grad_norm, use_max_grad_norm, lr, (float)b1, (float)b2, adam_eps, weight_decay, bc1, bc2s);
+                     grad_norm_out, max_grad_norm, use_max_grad_norm, lr, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), adam_eps, weight_decay,
+                     bc1, bc2s);
   SPO_LAUNCH_CHECK("spo_ma_clip_adam");
   return 0;
 }

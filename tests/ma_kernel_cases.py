@@ -1,0 +1,645 @@
+"""The cases of tests/test_gpu_ma_kernels.py (no test in here): the multi-agent trainer kernels of csrc/ma_net.hip that are reached
+by direct ABI calls -- spo_ma_actor_loss, spo_ma_value_loss, spo_ma_popart_stats / spo_ma_popart_forward, spo_ma_clip_adam,
+spo_ma_lamda_update, spo_ma_sample / spo_ma_log_probs -- and spo_ma_gae of csrc/multi_agent.hip.  Here are the case tables, every
+problem built on the CPU from seeds, the same operation in plain torch (oracle/ma_restatement.py, autograd,
+torch.nn.utils.clip_grad_norm_, torch.optim.Adam) in float32 -- the yardstick -- and float64 -- the reference --, and the gates.
+tests/test_ma_kernel_cases_host.py checks on the CPU that the problems keep the gates meaningful and that the gates refuse
+deliberately wrong oracles (the `variant` argument of the oracles).
+
+The two losses are discontinuous per row (ratio = 1 +- clip_param, the sign of the hybrid advantage, |values - value_preds| =
+clip_param, |e| = huber_delta, ho = hc).  Every problem is drawn in float32, its decision quantities are evaluated in float64, and
+every row within MARGIN (relative to the boundary value) of one of them is drawn again -- the whole row -- until none is left, so
+the float32 and the float64 oracle (and a correct kernel) take the same branch in every row.  One family is exempt on purpose:
+the "on_bound" value-loss rows have value_preds = 0 and values = +-clip_param, where values - value_preds is exact in every
+arithmetic and sits ON the inclusive bound (torch.clamp's gradient passes there, and so must the kernel's).
+
+Every oracle result is computed once per process (functools.lru_cache) and shared; callers do not modify what they get.  The
+oracles run on ORACLE_THREADS torch threads whatever the host offers (blocked sums round differently with the thread count, and
+the float32 oracle's rounding is the yardstick), and put the count back."""
+import functools
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "safe-policy-optimization_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from oracle import ma_restatement as MR  # noqa: E402
+import ma_yardstick as Y  # noqa: E402
+
+f32v = lambda x: float(np.float32(x))                            # the float32 value of a constant, as the C ABI receives it
+
+# ---- launch arithmetic of the row-parallel kernels: 256-thread workgroups, grid-stride, at most 1024 workgroups
+WG, WG_CAP = 256, 1024
+CAP_ROWS = WG * WG_CAP                                            # 262 144 rows fill one pass of the capped grid
+ROWS = [1, 63, 65, 255, 256, 257, 1000]
+ROWS_PAST_CAP = [CAP_ROWS + 1, CAP_ROWS + 257]                    # 262 145: one row in workgroup 0's second pass; 262 401: workgroup 0
+#                                                                   gets a full second pass and workgroup 1 one row
+ACT_DIMS = [1, 2, 5, 15, 16]
+MAX_ACT, AL_NS = 16, 4                                            # SPO_MAX_ACT; scalar partials of ma_actor_loss_kernel
+ACTOR_PARTIAL_DOUBLES = WG_CAP * (AL_NS + MAX_ACT)                # documented partial_ws sizes (include/safepo_hip.h, ma_net.hip)
+VALUE_PARTIAL_DOUBLES, POPART_PARTIAL_DOUBLES, ADAM_PARTIAL_DOUBLES = WG_CAP, 2 * WG_CAP, WG_CAP
+SHARD_ROWS = 257                                                  # two-shard cases: rows_global = 2 x 257
+MARGIN = 1e-4                                                     # tests/test_gpu_ma_full_size.py's margin around a clip boundary
+MIN_SHARE = 0.10                                                  # every branch class holds at least this share of the rows
+ORACLE_THREADS = 4
+STD_COEFS = (1.0, 0.5)                                            # std_x_coef, std_y_coef of the reference's configs
+CLIP, HUBER_DELTA, VALUE_LOSS_COEF = f32v(0.2), f32v(0.7), 0.5
+UNCLIPPED = f32v(3e38)                                            # MACPO's clip_param
+
+# spo_ma_actor_loss: form -> configuration.  `cost`: cost_adv is non-zero.  MAPPO's loss has no factor (mappo.py:150-160; the
+# Runner tracks one all the same), so the oracle has none, and the buffer handed to the kernel holds the non-trivial draw that
+# the per-dimension branch must not read.
+FORMS = {
+    "mappolag": dict(per_dim=0, lamda=f32v(0.7), cost=True, clip=CLIP, ent=f32v(0.01)),
+    "happo": dict(per_dim=0, lamda=0.0, cost=False, clip=CLIP, ent=f32v(0.01)),
+    "mappo": dict(per_dim=1, lamda=0.0, cost=False, clip=CLIP, ent=f32v(0.01)),
+    "macpo": dict(per_dim=0, lamda=0.0, cost=False, clip=UNCLIPPED, ent=0.0),
+}
+ACTOR_FORMS = [("mappolag", 0), ("mappolag", 1), ("happo", 0), ("happo", 1), ("mappo", 0), ("mappo", 1), ("macpo", 0)]
+PAST_CAP_ACT_DIM = {("mappolag", 0): 16, ("mappolag", 1): 1, ("happo", 0): 5, ("happo", 1): 16, ("mappo", 0): 16, ("mappo", 1): 1,
+                    ("macpo", 0): 15}
+# single-row cases: (region of the ratio, sign of the hybrid advantage); log ratio drawn inside the region
+ACTOR_CLASSES = [(r, s) for r in ("below", "inside", "above") for s in (1.0, -1.0)]
+LOG_RATIO = {"below": (-0.7, -0.3), "inside": (-0.15, 0.15), "above": (0.25, 0.7)}
+LOG_RATIO_STD = 0.46                                              # P(|N(0, 0.46)| < 0.2) ~ 1/3: a third of the ratios in each region
+VALUE_CLASSES = ["quad", "pos", "neg", "clipped", "unclipped", "max_orig", "max_clip"]
+VALUE_FORMS = [0, 1]                                              # active pointer: null / given
+
+# spo_ma_clip_adam
+ADAM_N = [1, 255, 257, 1000, CAP_ROWS + 257]
+ADAM_LR, ADAM_EPS = f32v(5e-4), f32v(1e-5)
+ADAM_CONFIGS = [dict(clip=c, wd=w, step=t) for c in ("off", "below", "above3") for w in (0.0, f32v(1e-2)) for t in (0, 9999)]
+ADAM_CONFIGS.append(dict(clip="just_over", wd=0.0, step=0))      # norm ~1e-3, 0.05 % over the bound: the 1e-6 of the coefficient shows
+ADAM_CONFIGS.append(dict(clip="off", wd=0.0, step=0, fresh=True))  # a new optimiser: zero moments, so v = (1 - beta2) g^2 bare
+ADAM_BIG_CONFIGS = [ADAM_CONFIGS[0], ADAM_CONFIGS[7], ADAM_CONFIGS[11], ADAM_CONFIGS[13]]
+adam_name = lambda c: f"{c['clip']}/wd{c['wd']:.0e}/t{c['step']}" + ("/fresh" if c.get("fresh") else "")
+
+# spo_ma_popart_*: (train, state, input, beta)
+POPART_EPS = f32v(1e-5)
+POPART_ALL = [(t, s, i, b) for t in (1, 0) for s in ("fresh", "aged") for i in ("narrow", "wide") for b in (0.99999, 0.9) if t or b == 0.9]
+POPART_FEW = [(1, "fresh", "wide", 0.99999), (1, "aged", "narrow", 0.9), (0, "aged", "wide", 0.9), (0, "fresh", "narrow", 0.9)]
+popart_name = lambda c: f"train{c[0]}/{c[1]}/{c[2]}/beta{c[3]}"
+
+# spo_ma_sample / spo_ma_log_probs: (rows, act_dim); 51 x 5 = 255, 16 x 16 = 256, 257 x 1 elements, then ROWS at act_dim 1, 5, 16
+SAMPLE_SHAPES = [(51, 5), (16, 16), (257, 1)] + [(r, a) for r in ROWS for a in (1, 5, 16) if (r, a) != (257, 1)]
+SAMPLE_COEFS = [STD_COEFS, (2.0, 1.5)]
+GAE_T, GAE_N = [1, 7, 9], [1, 255, 257]                           # below, around and past UNROLL = 8; one and two workgroups
+
+
+def _on_oracle_threads(fn):
+    @functools.wraps(fn)
+    def run(*a, **k):
+        threads = torch.get_num_threads()
+        torch.set_num_threads(ORACLE_THREADS)
+        try:
+            return fn(*a, **k)
+        finally:
+            torch.set_num_threads(threads)
+    return run
+
+
+def _seed(*parts):
+    s = 7
+    for p in parts:
+        s = (s * 1000003 + (sum(ord(c) for c in p) if isinstance(p, str) else int(p) + 11)) % (2 ** 31 - 1)
+    return s
+
+
+def _std(log_std, coefs=STD_COEFS):
+    return torch.sigmoid(log_std / coefs[0]) * coefs[1]
+
+
+def _redraw_until_clear(draw, bad_rows, n, what):
+    """draw(k) -> dict of k fresh rows; bad_rows(p) -> bool [rows].  Rows flagged are replaced whole by fresh draws until none is
+    left.  Returns (problem, rows drawn again in total)."""
+    p, again = draw(n), 0
+    for _ in range(2000):
+        bad = bad_rows(p)
+        k = int(bad.sum())
+        if k == 0:
+            return p, again
+        again += k
+        q = draw(k)
+        for key in p:
+            p[key][bad] = q[key]
+    raise AssertionError(f"{what}: the redraw did not converge")
+
+
+# ------------------------------------------------------------------------------------------------------- spo_ma_actor_loss
+def actor_decisions(p, form, dtype=torch.float64):
+    """The branch every row (joint forms) or element (per-dimension form) takes, evaluated in `dtype`:
+    region -1 / 0 / +1 = ratio below / inside (bounds inclusive) / above the clip range [rows, A or 1], the sign of the hybrid
+    advantage [rows], and `near` [rows]: within MARGIN of a discontinuity."""
+    f = FORMS[form]
+    t = {k: v.to(dtype) for k, v in p.items() if torch.is_tensor(v)}
+    imp = torch.exp(MR.log_probs(t["mean"], _std(t["log_std"]), t["act"]) - t["old_logp"])
+    if not f["per_dim"]:
+        imp = torch.prod(imp, dim=-1, keepdim=True)
+    advh = t["adv"] - torch.tensor(f["lamda"], dtype=dtype) * t["cost_adv"]
+    lo, hi = 1.0 - f["clip"], 1.0 + f["clip"]
+    region = (imp > hi).long() - (imp < lo).long()
+    near = ((imp - lo).abs() <= MARGIN * abs(lo)) | ((imp - hi).abs() <= MARGIN * abs(hi))
+    return region, torch.sign(advh), near.any(-1) | (advh.abs() <= MARGIN)
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def actor_problem(form, masks, A, rows, cls=None):
+    """float32 inputs of spo_ma_actor_loss.  old_logp = the float64 log-probability of the actions, rounded once, minus a log
+    ratio: N(0, LOG_RATIO_STD) per row (split over the dimensions) or per element (per-dimension form); with cls = (region, sign)
+    every row's log ratio is drawn inside LOG_RATIO[region] and its hybrid advantage has that sign.  ~20 % of the rows are inactive
+    (all active at one row); the mask is handed to the kernel whether or not the configuration uses it."""
+    f = FORMS[form]
+    g = torch.Generator().manual_seed(_seed("actor", form, masks, A, rows, str(cls)))
+    log_std = 0.5 * torch.randn(A, generator=g)
+    std64 = _std(log_std.double())
+
+    def draw(n):
+        r = lambda *s: torch.randn(*s, generator=g)
+        mean = 0.5 * r(n, A)
+        act = (mean.double() + std64 * r(n, A).double()).float()
+        lp = MR.log_probs(mean.double(), std64, act.double())
+        cost_adv = r(n) if f["cost"] else torch.zeros(n)
+        if cls is None:
+            if f["per_dim"]:
+                lr = LOG_RATIO_STD * r(n, A).double()
+            else:
+                jit = 0.05 * r(n, A).double()
+                lr = LOG_RATIO_STD * r(n, 1).double() / A + jit - jit.mean(-1, keepdim=True)
+            adv = r(n)
+        else:
+            lo, hi = LOG_RATIO[cls[0]]
+            u = torch.rand(n, A if f["per_dim"] else 1, generator=g).double()
+            lr = lo + (hi - lo) * u
+            lr = lr if f["per_dim"] else (lr / A).expand(n, A)
+            adv = cls[1] * (0.2 + r(n).abs()) + f["lamda"] * cost_adv
+        active = (torch.rand(n, generator=g) > 0.2).float() if rows > 1 else torch.ones(n)
+        return {"mean": mean, "act": act, "old_logp": (lp - lr).float(), "adv": adv, "cost_adv": cost_adv,
+                "factor": torch.exp(0.3 * r(n)), "active": active}
+
+    def bad_rows(p):
+        region, sign, near = actor_decisions(dict(p, log_std=log_std), form)
+        if cls is not None:
+            want = {"below": -1, "inside": 0, "above": 1}[cls[0]]
+            if f["clip"] != UNCLIPPED:                                 # without a clip range every ratio is inside: the sign alone
+                near = near | (region != want).any(-1)
+            near = near | (sign != cls[1])
+        return near
+    p, again = _redraw_until_clear(draw, bad_rows, rows, f"actor {form} {A} {rows}")
+    if rows > 1 and p["active"].sum() == 0:
+        p["active"][0] = 1.0
+    p["log_std"] = log_std
+    p["drawn_again"] = again
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def actor_oracle(form, masks, A, rows, cls, dtype_name, variant=None):
+    """MAPPO_L_Trainer.ppo_update / _ppo_update_unconstrained of oracle/ma_restatement.py from the network outputs on: `mean`
+    and a per-row copy of log_std are leaves, (policy_loss - dist_entropy * entropy_coef).backward().  -> float64 numpy:
+    dmean [rows, A], dlogstd [A] (the per-row gradients summed, which is what autograd's expand does) with dlogstd_scale = the
+    sum of their absolute values, scalars [5] = {policy_loss, dist_entropy, mean(imp), mean(imp * cost_adv), sum(active)} with
+    scalar_scales = the float64 sum / mean of the absolute values of the summed terms."""
+    dtype = getattr(torch, dtype_name)
+    f, p = FORMS[form], actor_problem(form, masks, A, rows, cls)
+    t = {k: v.to(dtype) for k, v in p.items() if torch.is_tensor(v)}
+    if variant == "stale_last_row":
+        t["act"] = t["act"].clone()
+        t["act"][-1] += 0.05
+    mean = t["mean"].clone().requires_grad_(True)
+    ls_rows = t["log_std"].expand(rows, A).clone().requires_grad_(True)
+    std = _std(ls_rows)
+    active, adv, cost_adv, factor = (t[k][:, None] for k in ("active", "adv", "cost_adv", "factor"))
+    logp = MR.log_probs(mean, std, t["act"])
+    ent = torch.distributions.Normal(mean, std).entropy()
+    if masks and variant != "entropy_ignores_mask":
+        dist_entropy = (ent * active).sum() / active.sum()
+    else:
+        dist_entropy = ent.mean()
+    imp = torch.exp(logp - t["old_logp"])
+    if not f["per_dim"]:
+        imp = torch.prod(imp, dim=-1, keepdim=True)
+    adv_h = adv - torch.tensor(f["lamda"], dtype=dtype) * cost_adv
+    surr1 = imp * adv_h
+    surr2 = torch.clamp(imp, 1.0 - f["clip"], 1.0 + f["clip"]) * adv_h
+    inner = torch.min(surr1, surr2)
+    if not f["per_dim"] or variant == "factor_in_per_dim":
+        inner = factor * inner
+    m = torch.sum(inner, dim=-1, keepdim=True)
+    w = active / active.sum() if masks else torch.full_like(active, 1.0 / rows)
+    policy_loss = (-m * active).sum() / active.sum() if masks else -m.mean()
+    (policy_loss - dist_entropy * f["ent"]).backward()
+    imp_mean = imp.mean() * (2.0 if variant == "rows_for_rows_global" else 1.0)
+    cost_terms = imp * cost_adv if not f["per_dim"] else torch.zeros_like(cost_adv)
+    with torch.no_grad():
+        scalars = [policy_loss, dist_entropy, imp_mean, cost_terms.mean(), t["active"].sum()]
+        # the entropy of a dimension, 0.5 + log sqrt(2 pi) + log sigma, cancels (sigma ~ 0.25: 0.03): its terms in absolute value
+        ent_abs = 0.5 + 0.5 * float(np.log(2 * np.pi)) + torch.log(std).abs()
+        ent_scale = (ent_abs * active).sum() / active.sum() if masks else ent_abs.mean()
+        scales = [(m * w).abs().sum(), ent_scale, imp.abs().mean(), cost_terms.abs().mean(), t["active"].sum()]
+    n64 = lambda x: x.detach().double().numpy().copy()
+    return {"dmean": n64(mean.grad), "dlogstd": n64(ls_rows.grad.sum(0)), "dlogstd_scale": n64(ls_rows.grad.abs().sum(0)),
+            "scalars": np.array([float(x.detach()) for x in scalars]), "scalar_scales": np.array([float(x.detach()) for x in scales])}
+
+
+def actor_populations(form, masks, A, rows, cls=None):
+    """Shares of rows (elements in the per-dimension form) per region, shares of rows per advantage sign, rows still near a
+    discontinuity, and whether float32 takes the float64 branch everywhere."""
+    p = actor_problem(form, masks, A, rows, cls)
+    r64, s64, near = actor_decisions(p, form)
+    r32, s32, _ = actor_decisions(p, form, torch.float32)
+    return {"below": float((r64 == -1).double().mean()), "inside": float((r64 == 0).double().mean()), "above": float((r64 == 1).double().mean()),
+            "adv_pos": float((s64 > 0).double().mean()), "adv_neg": float((s64 < 0).double().mean()), "near": int(near.sum()),
+            "same_branch": bool(torch.equal(r32, r64) and torch.equal(s32.double(), s64))}
+
+
+# ------------------------------------------------------------------------------------------------------- spo_ma_value_loss
+def _huber(e, d, variant=None):
+    if variant == "symmetric_huber":                                 # the e < -d branch "repaired"
+        a = (e.abs() <= d).to(e.dtype)
+        return a * e ** 2 / 2 + (1 - a) * d * (e.abs() - d / 2)
+    return MR.huber_loss(e, d)
+
+
+def value_decisions(p, dtype=torch.float64):
+    """in_range [rows] (|values - value_preds| <= clip_param, inclusive), the Huber branch -1 / 0 / +1 of the original and of the
+    clipped error, pick 0 / 1 / 2 = max takes the original / the clipped error / a tie (both exactly zero), and `near`."""
+    t = {k: v.to(dtype) for k, v in p.items() if torch.is_tensor(v)}
+    dv = t["values"] - t["value_preds"]
+    in_range = (dv >= -CLIP) & (dv <= CLIP)
+    e_c, e_o = t["ret_c"] - (t["value_preds"] + dv.clamp(-CLIP, CLIP)), t["ret_o"] - t["values"]
+    branch = lambda e: (e > HUBER_DELTA).long() - (e < -HUBER_DELTA).long()
+    ho, hc = MR.huber_loss(e_o, HUBER_DELTA), MR.huber_loss(e_c, HUBER_DELTA)
+    pick = torch.where(ho > hc, 0, torch.where(ho < hc, 1, 2))
+    d_clip = (dv.abs() - CLIP).abs()
+    near = ((d_clip <= MARGIN * CLIP) & (d_clip != 0)) | ((e_o.abs() - HUBER_DELTA).abs() <= MARGIN * HUBER_DELTA) | \
+        ((e_c.abs() - HUBER_DELTA).abs() <= MARGIN * HUBER_DELTA) | (((ho - hc).abs() <= MARGIN * torch.maximum(ho, hc)) & ((ho > 0) | (hc > 0)))
+    return in_range, branch(e_o), branch(e_c), pick, near
+
+
+_VALUE_CLASS = {
+    "quad": lambda i, bo, bc, pk: (bo == 0) & (bc == 0), "pos": lambda i, bo, bc, pk: (bo == 1) & (bc == 1),
+    "neg": lambda i, bo, bc, pk: (bo == -1) & (bc == -1), "clipped": lambda i, bo, bc, pk: ~i & (pk == 1),
+    "unclipped": lambda i, bo, bc, pk: i & (pk != 2), "max_orig": lambda i, bo, bc, pk: pk == 0, "max_clip": lambda i, bo, bc, pk: i & (pk == 1),
+}
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def value_problem(active, rows, cls=None):
+    """float32 inputs of spo_ma_value_loss at clip_param 0.2, huber_delta 0.7: values - value_preds ~ N(0, 0.25) (42 % clipped),
+    the normalised returns 0.3 + N(0, 1.5) around value_preds (the second PopArt call's differ from the first's by N(0, 0.05)).
+    cls: every row satisfies _VALUE_CLASS[cls]; "on_bound": every fourth row has value_preds = 0 and values = +-clip_param."""
+    g = torch.Generator().manual_seed(_seed("value", active, rows, str(cls)))
+
+    def draw(n):
+        r = lambda: torch.randn(n, generator=g)
+        vp = 0.5 * r()
+        v = vp + 0.25 * r()
+        ret_c = vp + 0.3 + 1.5 * r()
+        return {"values": v, "value_preds": vp, "ret_c": ret_c, "ret_o": ret_c + 0.05 * r(),
+                "active": (torch.rand(n, generator=g) > 0.2).float() if rows > 1 else torch.ones(n)}
+
+    def bad_rows(p):
+        i, bo, bc, pk, near = value_decisions(p)
+        if cls in _VALUE_CLASS:
+            near = near | ~_VALUE_CLASS[cls](i, bo, bc, pk)
+        elif p["active"][-1] == 0 or pk[-1] == 2:                    # the last row carries a loss, so that a stale tail shows
+            p["active"][-1] = 1.0
+            near[-1] = near[-1] | (pk[-1] == 2)
+        return near
+    p, again = _redraw_until_clear(draw, bad_rows, rows, f"value {active} {rows} {cls}")
+    if cls == "on_bound":
+        for k in range(0, rows, 4):
+            for _ in range(1000):
+                q = draw(1)
+                q["value_preds"][0], q["values"][0] = 0.0, CLIP if k % 8 == 0 else -CLIP
+                i, bo, bc, pk, near = value_decisions(q)
+                if not bool(near[0]) and bool(i[0]) and (rows > 1 or (int(pk[0]) == 1 and int(bc[0]) != -1)):
+                    break
+            else:
+                raise AssertionError("on_bound: no row found")
+            for key in p:
+                p[key][k] = q[key][0]
+    if rows > 1 and p["active"].sum() == 0:
+        p["active"][0] = 1.0
+    p["drawn_again"] = again
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def value_oracle(active, rows, cls, dtype_name, variant=None):
+    """OracleMATrainer.value_loss (mappolag.py:126-138, happo.py:117-120) on given normalised returns; `values` is a leaf and
+    (loss * value_loss_coef).backward().  -> dvalues [rows], loss, loss_scale (the Huber terms are >= 0: the loss itself)."""
+    dtype = getattr(torch, dtype_name)
+    t = {k: v.to(dtype) for k, v in value_problem(active, rows, cls).items() if torch.is_tensor(v)}
+    if variant == "stale_last_row":                                  # the last row reads zeros: no loss, no gradient
+        for key in ("values", "value_preds", "ret_c", "ret_o"):
+            t[key] = t[key].clone()
+            t[key][-1] = 0.0
+    values = t["values"].clone().requires_grad_(True)
+    dv = values - t["value_preds"]
+    if variant == "exclusive_clip":
+        vpc = t["value_preds"] + torch.where((dv > -CLIP) & (dv < CLIP), dv, dv.detach().clamp(-CLIP, CLIP))
+    else:
+        vpc = t["value_preds"] + dv.clamp(-CLIP, CLIP)
+    e_c, e_o = t["ret_c"] - vpc, t["ret_o"] - values
+    vl = torch.max(_huber(e_o, HUBER_DELTA, variant), _huber(e_c, HUBER_DELTA, variant))
+    loss = (vl * t["active"]).sum() / t["active"].sum() if active else vl.mean()
+    if variant == "rows_for_rows_global":
+        loss = loss * 2.0
+    (loss * VALUE_LOSS_COEF).backward()
+    return {"dvalues": values.grad.double().numpy().copy(), "loss": float(loss.detach()), "loss_scale": abs(float(loss.detach()))}
+
+
+def value_populations(active, rows, cls=None):
+    p = value_problem(active, rows, cls)
+    i, bo, bc, pk, near = value_decisions(p)
+    d32 = value_decisions(p, torch.float32)
+    share = lambda m: float(m.double().mean())
+    out = {"clipped": share(~i), "unclipped": share(i), "max_orig": share(pk == 0), "max_clip": share(pk == 1), "near": int(near.sum()),
+           "same_branch": all(bool(torch.equal(a, b)) for a, b in zip((i, bo, bc, pk), d32[:4]))}
+    for nm, b in (("orig", bo), ("clip", bc)):
+        out.update({f"quad_{nm}": share(b == 0), f"pos_{nm}": share(b == 1), f"neg_{nm}": share(b == -1)})
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ spo_ma_popart_*
+@functools.lru_cache(maxsize=None)
+def popart_problem(cfg, rows):
+    train, state, inp, beta = cfg
+    g = torch.Generator().manual_seed(_seed("popart", popart_name(cfg), rows))
+    mu, sd = (0.3, 0.02) if inp == "narrow" else (0.3, 1.5)           # variance 4e-4 (under the 1e-2 clamp) / 2.25
+    x = mu + sd * torch.randn(rows, generator=g)
+    deb = 0.6
+    state3 = torch.zeros(3) if state == "fresh" else torch.tensor([mu * deb, (mu * mu + sd * sd) * deb, deb])
+    return {"x": x, "state3": state3}
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def popart_oracle(cfg, rows, dtype_name, variant=None):
+    """OraclePopArt(beta, epsilon)(x, train) from `state3` -> normalised rows, the three state floats, their scales (the absolute
+    values of the two summed terms of each running statistic), the batch sums in this dtype, var before the 1e-2 clamp."""
+    dtype = getattr(torch, dtype_name)
+    train, _, _, beta = cfg
+    p = popart_problem(cfg, rows)
+    x, s = p["x"].to(dtype)[:, None], p["state3"].to(dtype)
+    if variant == "stale_last_row":
+        x = x.clone()
+        x[-1] += 0.05
+    o = MR.OraclePopArt(beta, POPART_EPS)
+    o.running_mean, o.running_mean_sq, o.debiasing_term = s[0:1].clone(), s[1:2].clone(), s[2].clone()
+    out = o(x, train=bool(train))
+    deb = o.debiasing_term.clamp(min=POPART_EPS)
+    var_raw = float(o.running_mean_sq / deb - (o.running_mean / deb) ** 2)
+    s64, x64 = p["state3"].double(), p["x"].double()
+    scales = [beta * abs(float(s64[0])) + (1 - beta) * float(x64.abs().mean()), beta * float(s64[1]) + (1 - beta) * float((x64 ** 2).mean()),
+              float(o.debiasing_term)] if train else [1.0, 1.0, 1.0]
+    return {"out": out[:, 0].double().numpy().copy(), "state3": np.array([float(o.running_mean), float(o.running_mean_sq), float(o.debiasing_term)]),
+            "state_scales": np.array(scales), "sums": np.array([float(x.sum()), float((x ** 2).sum())]), "var_raw": var_raw}
+
+
+# ------------------------------------------------------------------------------------------------------------ spo_ma_clip_adam
+@functools.lru_cache(maxsize=None)
+def adam_problem(n, name):
+    cfg = next(c for c in ADAM_CONFIGS if adam_name(c) == name)
+    g = torch.Generator().manual_seed(_seed("adam", n, name))
+    r = lambda: torch.randn(n, generator=g)
+    theta, grad = r(), 0.1 * r()
+    if cfg["clip"] == "just_over":
+        grad = (grad.double() * (1.0005e-3 / float(grad.double().norm()))).float()
+    m0, v0 = 0.05 * r(), (0.05 * r()) ** 2 + 1e-4
+    if cfg["clip"] == "just_over":                                    # moments of the gradient's size: a coefficient 1e-3 off shows in them
+        gs = 1e-3 / n ** 0.5
+        m0, v0 = m0 * (10 * gs), v0 * (10 * gs) ** 2
+    if cfg.get("fresh"):
+        m0, v0 = torch.zeros(n), torch.zeros(n)
+    norm64 = float(grad.double().norm())
+    max_norm = {"off": 10.0, "below": f32v(3 * norm64), "above3": f32v(norm64 / 3), "just_over": f32v(1e-3)}[cfg["clip"]]
+    return {"theta": theta, "grad": grad, "m": m0, "v": v0, "max_norm": max_norm, "use_clip": int(cfg["clip"] != "off"), "wd": cfg["wd"],
+            "step": cfg["step"], "norm64": norm64}
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def adam_oracle(n, name, dtype_name, variant=None):
+    """torch.nn.utils.clip_grad_norm_ + torch.optim.Adam(lr, eps, weight_decay) step number `step` + 1 from the given moments
+    -> norm (pre-clip), m, v, update = theta_after - theta_before."""
+    dtype = getattr(torch, dtype_name)
+    p = adam_problem(n, name)
+    theta = torch.nn.Parameter(p["theta"].to(dtype).clone())
+    theta.grad = p["grad"].to(dtype).clone()
+    if variant == "stale_last_row":
+        theta.grad[-1] *= 1.5
+    m, v = p["m"].to(dtype).clone(), p["v"].to(dtype).clone()
+    if p["use_clip"] and variant != "clip_without_1e_6":
+        norm = torch.nn.utils.clip_grad_norm_([theta], p["max_norm"])
+    else:
+        norm = theta.grad.norm()
+        if p["use_clip"]:
+            theta.grad.mul_(torch.clamp(p["max_norm"] / norm, max=1.0))
+    before = theta.detach().clone()
+    if variant in ("no_bias_correction", "one_minus_beta_in_float32"):
+        # the step written out.  one_minus_beta_in_float32: 1.f - 0.999f = 0.99998713e-3 in place of torch's float(1 - 0.999), what
+        # ma_adam_kernel computed before it took both differences from the host
+        t = p["step"] + 1
+        bc1, bc2 = (1.0, 1.0) if variant == "no_bias_correction" else (1 - 0.9 ** t, 1 - 0.999 ** t)
+        one = np.float32(1)
+        o1, o2 = (1 - 0.9, 1 - 0.999) if variant == "no_bias_correction" else (float(one - np.float32(0.9)), float(one - np.float32(0.999)))
+        with torch.no_grad():
+            gr = theta.grad + p["wd"] * theta
+            m.lerp_(gr, o1)
+            v.mul_(0.999).addcmul_(gr, gr, value=o2)
+            theta.addcdiv_(m, v.sqrt() / bc2 ** 0.5 + ADAM_EPS, value=-ADAM_LR / bc1)
+    else:
+        opt = torch.optim.Adam([theta], lr=ADAM_LR, eps=ADAM_EPS, weight_decay=p["wd"])
+        opt.state[theta] = {"step": torch.tensor(float(p["step"]), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+        opt.step()
+        assert float(opt.state[theta]["step"]) == p["step"] + 1
+    n64 = lambda x: x.detach().double().numpy().copy()
+    return {"norm": float(norm), "m": n64(m), "v": n64(v), "update": n64(theta) - n64(before)}
+
+
+def adam_update_floor(n, name):
+    """Half an ulp of max|theta|: the rounding of the stored parameter, which the kernel and the float32 oracle share."""
+    return float(np.spacing(np.float32(adam_problem(n, name)["theta"].abs().max()))) / 2
+
+
+# --------------------------------------------------------------------------------------------------------- spo_ma_lamda_update
+GAMMA32 = f32v(0.99)
+# (lamda, mean(imp * cost_adv), aver_episode_cost, cost_limit, rate): delta = -((aver - limit) * (1 - gamma) + s3), relu(lamda - delta * rate)
+LAMDA_CASES = [(f32v(0.7), f32v(0.31), 31.0, 25.0, f32v(0.78)), (f32v(0.7), f32v(-0.9), 20.0, 25.0, f32v(0.78)),
+               (f32v(0.01), f32v(-0.2), 24.0, 25.0, f32v(0.5)), (0.0, f32v(0.05), 25.5, 25.0, f32v(0.1))]
+
+
+def lamda_oracle(case, dtype_name):
+    """-> (new multiplier, scale = |lamda| + |delta * rate|, lamda - delta * rate before the relu)."""
+    dtype = getattr(torch, dtype_name)
+    lam, s3, aver, limit, rate = (torch.tensor(v, dtype=dtype) for v in case)
+    delta = -((aver - limit) * (1 - torch.tensor(GAMMA32, dtype=dtype)) + s3)
+    pre = lam - delta * rate
+    return float(torch.relu(pre)), float(lam.abs() + (delta * rate).abs()), float(pre)
+
+
+# ------------------------------------------------------------------------------------------- spo_ma_sample / spo_ma_log_probs
+@functools.lru_cache(maxsize=None)
+def sample_problem(rows, A, coefs):
+    g = torch.Generator().manual_seed(_seed("sample", rows, A, int(coefs[0] * 8), int(coefs[1] * 8)))
+    log_std = torch.linspace(-4.0, 4.0, A) if A > 1 else torch.tensor([-4.0 if rows % 2 else 4.0])
+    mean = 0.5 * torch.randn(rows, A, generator=g)
+    eps = torch.randn(rows, A, generator=g)
+    act = (mean.double() + _std(log_std.double(), coefs) * torch.randn(rows, A, generator=g).double()).float()
+    return {"mean": mean, "log_std": log_std, "eps": eps, "act": act}
+
+
+@functools.lru_cache(maxsize=None)
+@_on_oracle_threads
+def sample_oracle(rows, A, coefs, dtype_name, variant=None):
+    """-> the sampled action mean + std * eps and its per-dimension log-probabilities, the log-probabilities of the mean
+    (deterministic) and of the given action (spo_ma_log_probs)."""
+    dtype = getattr(torch, dtype_name)
+    t = {k: v.to(dtype) for k, v in sample_problem(rows, A, coefs).items()}
+    if variant == "stale_last_row":
+        t["eps"], t["act"] = t["eps"].clone(), t["act"].clone()
+        t["eps"][-1] += 0.05
+        t["act"][-1] += 0.05
+    std = _std(t["log_std"], coefs)
+    act = t["mean"] + std * t["eps"]
+    n64 = lambda x: x.double().numpy().copy()
+    return {"act": n64(act), "logp": n64(MR.log_probs(t["mean"], std, act)), "logp_det": n64(MR.log_probs(t["mean"], std, t["mean"])),
+            "logp_given": n64(MR.log_probs(t["mean"], std, t["act"]))}
+
+
+# ------------------------------------------------------------------------------------------------------------------ spo_ma_gae
+@functools.lru_cache(maxsize=None)
+def gae_problem(T, N):
+    """Time-major inputs with random masks, two PopArt states (reward side, cost side) and the float32 returns of
+    MR.masked_gae.  -> dict; sd / mu: float(sqrt(var)), float(mean) of each side, as PopArt.denorm_scalars hands them over."""
+    g = torch.Generator().manual_seed(_seed("gae", T, N))
+    p = {"rewards": torch.randn(T, N, 1, generator=g), "costs": (torch.rand(T, N, 1, generator=g) < 0.3).float(),
+         "masks": (torch.rand(T + 1, N, 1, generator=g) > 0.25).float(), "value_preds": 0.7 * torch.randn(T + 1, N, 1, generator=g),
+         "cost_preds": 0.4 * torch.randn(T + 1, N, 1, generator=g).abs(), "gamma": 0.99, "gae_lambda": 0.95}
+    for side, st, src, preds in (("r", (0.013, 0.071, 0.019), "rewards", "value_preds"), ("c", (0.2, 0.9, 0.5), "costs", "cost_preds")):
+        o = MR.OraclePopArt()
+        o.running_mean, o.running_mean_sq, o.debiasing_term = torch.tensor([st[0]]), torch.tensor([st[1]]), torch.tensor(st[2])
+        m, v = o.mean_var()
+        p["sd_" + side], p["mu_" + side] = float(torch.sqrt(v).reshape(-1)[0]), float(m.reshape(-1)[0])
+        p["want_" + side] = MR.masked_gae(p[src], p[preds], p["masks"], o, p["gamma"], p["gae_lambda"])
+    return p
+
+
+# ----------------------------------------------------------------------------------------------------------------------- gates
+# |hip - f64| <= 3 |f32 - f64| + floor in max-norm and L2 (tests/ma_yardstick.gate), floor = 1e-6 of the quantity's scale: these are
+# single evaluations from identical state.  Scale: max|f64| of a vector; for a sum with cancellation the float64 sum / mean of the
+# absolute values of its terms (as test_wide_cpo_primitives_vs_oracle uses mean|adv|); for the Adam update the floor is half an ulp
+# of max|theta| instead.  Every gate prints both deviations and the floor before it asserts, and notes its ratio
+# |hip - f64| / (3 |f32 - f64| + floor) under (entry point, form, act_dim, rows) in RATIOS.
+REL_FLOOR, FACTOR = 1e-6, Y.C
+RATIOS = {}
+
+
+def _note(entry, form, A, rows, ratio):
+    key = (entry, str(form), A, rows)
+    RATIOS[key] = max(RATIOS.get(key, 0.0), float(ratio))
+
+
+def gate(entry, form, A, rows, hip, f32, f64, what, scale=None, floor=None):
+    """One array (or scalar) of one case.  scale: None -> max|f64|; a number; or an array of per-element scales (each element is
+    divided by its own and the vector gated with scale 1).  floor: an absolute floor in place of REL_FLOOR * scale."""
+    hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
+    if np.ndim(scale) > 0:
+        s = np.maximum(np.asarray(scale, np.float64).reshape(-1), 1e-30)
+        hip, f32, f64, scale = hip / s, f32 / s, f64 / s, 1.0
+    sc = max(float(np.abs(f64).max()) if scale is None else float(scale), 1e-30)
+    fl = REL_FLOOR * sc if floor is None else float(floor)
+    dh, d32, n = np.abs(hip - f64), np.abs(f32 - f64), np.sqrt(f64.size)
+    print(f"{what}: max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {fl:.3e};  L2 |hip-f64| {np.linalg.norm(dh):.3e}  "
+          f"|f32-f64| {np.linalg.norm(d32):.3e}  floor {fl * n:.3e}")
+    ratio = max(dh.max() / (FACTOR * d32.max() + fl), np.linalg.norm(dh) / (FACTOR * np.linalg.norm(d32) + fl * n))
+    _note(entry, form, A, rows, ratio)
+    if floor is None:
+        Y.gate(hip, f32, f64, REL_FLOOR, what, scale=sc)
+    else:
+        Y.gate(hip, f32, f64, 1.0, what, scale=fl)
+    return ratio
+
+
+def gate_group(entry, members, what):
+    """Scalars of ONE kind over several cases (a single scalar's |f32 - f64| is one draw of rounding noise and can be 0 by
+    chance): members = [(form, A, rows, hip, f32, f64, scale)], each divided by its own scale, the vector gated with scale 1 --
+    the yardstick is the float32 oracle's largest (max-norm) and root-mean-square (L2) deviation in the group.  Returns the
+    yardstick's max-norm."""
+    s = np.array([max(abs(m[6]), 1e-30) for m in members])
+    hip, f32, f64 = (np.array([m[k] for m in members], np.float64) / s for k in (3, 4, 5))
+    dh, d32 = np.abs(hip - f64), np.abs(f32 - f64)
+    print(f"{what} ({len(members)} cases): max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {REL_FLOOR:.1e} (of each case's scale)")
+    for m, d in zip(members, dh):
+        _note(entry, m[0], m[1], m[2], d / (FACTOR * d32.max() + REL_FLOOR))
+    Y.gate(hip, f32, f64, REL_FLOOR, what, scale=1.0)
+    return float(d32.max())
+
+
+SCALAR_NAMES = ("policy_loss", "dist_entropy", "mean(imp)", "mean(imp * cost_adv)", "sum(active)")
+
+
+def _group_or_now(entry, groups, name, member, what):
+    if groups is None:
+        gate_group(entry, [member], f"{what}: {name}")
+    else:
+        groups.setdefault(name, []).append(member)
+
+
+def gate_actor(label, A, rows, hip, o32, o64, groups=None, vectors=True, entry="spo_ma_actor_loss"):
+    """Every gate of one spo_ma_actor_loss case; hip / o32 / o64: dicts laid out like actor_oracle's.  dmean per element and dlogstd
+    against the sum of its absolute per-row terms (vectors=False: the caller gates them, several one-row cases as one vector);
+    the five scalars go to `groups` (name -> members, gated per kind by the caller) or, without one, are gated here."""
+    tag = f"{label} A {A} rows {rows}"
+    if vectors:
+        gate(entry, label, A, rows, hip["dmean"], o32["dmean"], o64["dmean"], f"dmean {tag}")
+        gate(entry, label, A, rows, hip["dlogstd"], o32["dlogstd"], o64["dlogstd"], f"dlogstd {tag}", scale=o64["dlogstd_scale"])
+    for k, name in enumerate(SCALAR_NAMES):
+        _group_or_now(entry, groups, name, (label, A, rows, hip["scalars"][k], o32["scalars"][k], o64["scalars"][k], o64["scalar_scales"][k]), tag)
+
+
+def gate_value(label, rows, hip, o32, o64, losses=None, vector=True, entry="spo_ma_value_loss"):
+    """dvalues per row and the loss of one spo_ma_value_loss case (as gate_actor)."""
+    if vector:
+        gate(entry, label, None, rows, hip["dvalues"], o32["dvalues"], o64["dvalues"], f"dvalues {label} rows {rows}")
+    member = (label, None, rows, hip["loss"], o32["loss"], o64["loss"], o64["loss_scale"])
+    if losses is None:
+        gate_group(entry, [member], f"value loss {label} rows {rows}")
+    else:
+        losses.append(member)
+
+
+def gate_adam(name, n, hip, o32, o64, norms=None, entry="spo_ma_clip_adam"):
+    """Both moments (max|f64|), the update theta_after - theta_before (3 |f32 - f64| + half an ulp of max|theta|) and the returned
+    norm of one spo_ma_clip_adam case."""
+    for key in ("m", "v"):
+        gate(entry, name, None, n, hip[key], o32[key], o64[key], f"adam_{key} {name} n {n}")
+    gate(entry, name, None, n, hip["update"], o32["update"], o64["update"], f"update {name} n {n}", floor=adam_update_floor(n, name))
+    member = (name, None, n, hip["norm"], o32["norm"], o64["norm"], o64["norm"])
+    if norms is None:
+        gate_group(entry, [member], f"gradient norm {name} n {n}")
+    else:
+        norms.append(member)
+
+
+def ratio_table():
+    """RATIOS as text: one line per (entry point, form, act_dim, rows), then the worst ratio per entry point."""
+    lines = [f"{'entry point':<24} {'form':<28} {'act':>3} {'rows':>7}  worst |hip-f64| / (3 |f32-f64| + floor)"]
+    worst = {}
+    for (entry, form, A, rows), r in sorted(RATIOS.items(), key=lambda kv: (kv[0][0], kv[0][1], int(kv[0][2] or 0), kv[0][3])):
+        lines.append(f"{entry:<24} {form:<28} {A or '-':>3} {rows:>7}  {r:.3f}")
+        if r >= worst.get(entry, (-1.0,))[0]:
+            worst[entry] = (r, form, A, rows)
+    head = [f"worst of {e}: {r:.3f} at form {f}, act_dim {a or '-'}, rows {n}" for e, (r, f, a, n) in sorted(worst.items())]
+    return "\n".join(head + [""] + lines)
