@@ -9,14 +9,22 @@ namespace spo {
 // square root and the two divisions done by v_sqrt_f32 / v_rcp_f32 (1 ulp) instead of IEEE
 // sequences: the parameter step changes by <= 3e-7 relative, i.e. < 1e-10 absolute per step.
 struct AdamOut { float p, m, v; };
-__device__ __forceinline__ AdamOut adam1(float p, float g, float m, float v, float b1, float b2, float eps,
+// w1 = 1 - beta1, w2 = 1 - beta2 as the caller formed them.  The wide-network path forms them on the host in double from the
+// decimal the caller meant and rounds once (csrc/adam_host.h): torch's exp_avg_sq weight is float(1 - 0.999) = 1.00000005e-3,
+// while 1.f - 0.999f is 0.99998713e-3, 1.3e-5 relative off in every v.
+__device__ __forceinline__ AdamOut adam1(float p, float g, float m, float v, float b2, float w1, float w2, float eps,
                                          float step_size, float inv_bc2_sqrt) {
   AdamOut o;
-  o.m = fmaf(1.f - b1, g - m, m);
-  o.v = fmaf(v, b2, ((1.f - b2) * g) * g);
+  o.m = fmaf(w1, g - m, m);
+  o.v = fmaf(v, b2, (w2 * g) * g);
   const float denom = fmaf(__builtin_amdgcn_sqrtf(o.v), inv_bc2_sqrt, eps);
   o.p = fmaf(-step_size, o.m * __builtin_amdgcn_rcpf(denom), p);
   return o;
+}
+// The persistent update kernels' form: both weights from the float32 betas (their follow-up: DESIGN.md).
+__device__ __forceinline__ AdamOut adam1(float p, float g, float m, float v, float b1, float b2, float eps,
+                                         float step_size, float inv_bc2_sqrt) {
+  return adam1(p, g, m, v, b2, 1.f - b1, 1.f - b2, eps, step_size, inv_bc2_sqrt);
 }
 // The two per-step scalars of Adam's bias correction: step_size = lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t).  The powers are
 // carried in double (one v_mul_f64 each per step); rounds 1-2 also formed the quotient and the square root in double -- ~40

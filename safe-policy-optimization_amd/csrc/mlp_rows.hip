@@ -39,6 +39,7 @@
 #include "common.h"
 #include "mlp_mfma.h"
 #include "adam.h"
+#include "adam_host.h"
 #include <cstdlib>
 #include <vector>
 #include "../../include/safepo_hip.h"
@@ -90,6 +91,8 @@ struct MrOptArgs {
   const float* parts; int R; int64_t stride;
   float* theta; float* grad; float* m; float* v; int64_t P, r_end, c_end, actor_begin; int64_t rows;
   float l2, vcoef_r, max_norm, lr_actor, lr_critic, b1, b2, eps;
+  float w1, w2;                      // 1 - beta1, 1 - beta2 formed on the host in double (csrc/adam_host.h), as wide_adam_kernel takes them
+  double b1d, b2d;                   // the betas the caller meant: the optimiser clocks are their powers (as wide_coef_kernel's)
   double* partial; float* scal; float* losses3; double* pow4;
   float* loss_log; int64_t* cursor; int64_t cursor_step; int nblocks;
 };
@@ -682,7 +685,7 @@ __global__ __launch_bounds__(256) void mlp_rows_prep_kernel(typename MrKernArg<M
   // the optimiser clocks and the cursor advance HERE (one lane): nobody in this launch reads them, the gradient launch that did is
   // over, and the Adam pass behind this one reads the advanced clocks as wide_adam_dev_kernel does -- no counter, no atomics
   if (blockIdx.x == 0 && tid == 128) {
-    a.pow4[0] *= (double)a.b1; a.pow4[1] *= (double)a.b2; a.pow4[2] *= (double)a.b1; a.pow4[3] *= (double)a.b2;
+    a.pow4[0] *= a.b1d; a.pow4[1] *= a.b2d; a.pow4[2] *= a.b1d; a.pow4[3] *= a.b2d;
     if (a.cursor) a.cursor[0] += a.cursor_step;
   }
 }
@@ -714,7 +717,7 @@ __global__ __launch_bounds__(256) void mlp_rows_adam_kernel(typename MrKernArg<M
   adam_scalars(lr_c, a.pow4[0], a.pow4[1], ss_c, bc2s_c);
   for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < a.P; i += (int64_t)gridDim.x * 256) {
     const bool act = i >= a.actor_begin;
-    const AdamOut o = adam1(a.theta[i], a.grad[i] * coef, a.m[i], a.v[i], a.b1, a.b2, a.eps, act ? ss_a : ss_c, act ? bc2s_a : bc2s_c);
+    const AdamOut o = adam1(a.theta[i], a.grad[i] * coef, a.m[i], a.v[i], a.b2, a.w1, a.w2, a.eps, act ? ss_a : ss_c, act ? bc2s_a : bc2s_c);
     a.theta[i] = o.p; a.m[i] = o.m; a.v[i] = o.v;
   }
   // what wide_coef_kernel's single lane wrote besides the clocks: nobody else in this launch reads any of it
@@ -824,16 +827,21 @@ int mr_check_partial(const char* who, int64_t n_params, int partial_capacity) {
   SPO_REQUIRE((int64_t)partial_capacity >= mr_opt_blocks(n_params) * 3, "%s: partial workspace too small", who);
   return 0;
 }
-void mr_fill_opt(float* parts, int64_t rows, float* theta, float* grad, float* adam_m, float* adam_v, int64_t n_params,
+int mr_fill_opt(const char* who, float* parts, int64_t rows, float* theta, float* grad, float* adam_m, float* adam_v, int64_t n_params,
                  int64_t reward_critic_end, int64_t cost_critic_end, int64_t actor_begin, const spo_ppo_cfg* cfg, double* pow4_dev,
                  float* losses3_out, float* scalars4_out, double* partial_ws, float* loss_log_dev, int64_t* cursor_dev,
                  int64_t cursor_step, MrOptArgs* out) {
   const int R = (int)((rows + 15) / 16);
   const int64_t stride = mr_stride(n_params);
+  float w1, w2;
+  double b1d = 0.0, b2d = 0.0;
+  SPO_REQUIRE(adam_beta_host(cfg->beta1, &b1d, &w1) && adam_beta_host(cfg->beta2, &b2d, &w2), "%s: betas (%g, %g) outside [0, 1)", who,
+              (double)cfg->beta1, (double)cfg->beta2);
   *out = MrOptArgs{parts, R, stride, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, rows,
                    cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
-                   cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, partial_ws, scalars4_out, losses3_out, pow4_dev, loss_log_dev,
+                   cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, w1, w2, b1d, b2d, partial_ws, scalars4_out, losses3_out, pow4_dev, loss_log_dev,
                    cursor_dev, cursor_step, (int)mr_opt_blocks(n_params)};
+  return 0;
 }
 }  // namespace
 
@@ -912,8 +920,9 @@ extern "C" int spo_wide_rows_clip_adam_dev_log(float* parts, int64_t rows, float
   if (int rc = mr_check_partial("wide_rows_clip_adam", n_params, partial_capacity)) return rc;
   const int64_t blocks = mr_opt_blocks(n_params);
   MrOptArgs a;
-  mr_fill_opt(parts, rows, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, cfg, pow4_dev,
-              losses3_out, scalars4_out, partial_ws, loss_log_dev, cursor_dev, cursor_step, &a);
+  if (int rc = mr_fill_opt("wide_rows_clip_adam", parts, rows, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end,
+                           actor_begin, cfg, pow4_dev, losses3_out, scalars4_out, partial_ws, loss_log_dev, cursor_dev, cursor_step, &a))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mlp_rows_prep_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
   hipLaunchKernelGGL(mlp_rows_adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
@@ -973,8 +982,9 @@ extern "C" int spo_wide_rows_multi_upload(void* table_dev, const spo_wide_rows_r
     bool vec;
     mr_fill_grad(p.theta, critic, actor, p.obs, p.act, p.logp_old, p.target_r, p.target_c, p.adv, p.perm, p.cursor_dev, rows,
                  p.cfg.clip, p.parts, &e.g, &sh, &vec);
-    mr_fill_opt(p.parts, rows, p.theta, p.grad, p.adam_m, p.adam_v, P, Pc, 2 * Pc, 2 * Pc, &p.cfg, p.pow4_dev, p.losses3_out,
-                p.scalars4_out, p.partial_ws, p.loss_log_dev, p.cursor_dev, cursor_step, &e.o);
+    if (int rc = mr_fill_opt("wide_rows_multi_upload", p.parts, rows, p.theta, p.grad, p.adam_m, p.adam_v, P, Pc, 2 * Pc, 2 * Pc, &p.cfg,
+                             p.pow4_dev, p.losses3_out, p.scalars4_out, p.partial_ws, p.loss_log_dev, p.cursor_dev, cursor_step, &e.o))
+      return rc;
     e.active = 1;
   }
   hipStream_t st = (hipStream_t)stream;

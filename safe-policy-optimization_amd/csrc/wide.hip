@@ -28,6 +28,7 @@
 #include <cmath>
 #include "common.h"
 #include "adam.h"
+#include "adam_host.h"
 #include "mlp_mfma.h"
 #include "mlp_small.h"
 #include "gemm_f32.h"
@@ -647,6 +648,8 @@ __global__ void wide_sum3_kernel(const double* __restrict__ partial, int n, doub
 struct WideAdamArgs {
   float* theta; float* grad; float* m; float* v; int64_t P, r_end, c_end, actor_begin;
   float l2, vcoef_r, max_norm, lr_actor, lr_critic, b1, b2, eps;
+  float w1, w2;                      // 1 - beta1, 1 - beta2 formed on the host in double (csrc/adam_host.h)
+  double b1d, b2d;                   // the betas the caller meant: the optimiser clocks are their powers
   double pow_b1, pow_b2;
   double* partial; float* scal;      // scal: {coef, l2 * sum p^2 (reward critic), l2 * sum p^2 (cost critic), ||g||}
   float* losses3;
@@ -683,8 +686,8 @@ __global__ __launch_bounds__(64) void wide_coef_kernel(WideAdamArgs a, int nbloc
   gs = wave_sum_d(gs); pr = wave_sum_d(pr); pc = wave_sum_d(pc);
   if (threadIdx.x != 0) return;
   if (pow4) {
-    if (adv_critics) { pow4[0] *= (double)a.b1; pow4[1] *= (double)a.b2; }
-    if (adv_actor) { pow4[2] *= (double)a.b1; pow4[3] *= (double)a.b2; }
+    if (adv_critics) { pow4[0] *= a.b1d; pow4[1] *= a.b2d; }
+    if (adv_actor) { pow4[2] *= a.b1d; pow4[3] *= a.b2d; }
   }
   const float norm = sqrtf((float)gs);
   float coef = a.max_norm / (norm + 1e-6f);                   // clip_grad_norm_ (torch): eps 1e-6
@@ -736,13 +739,13 @@ __global__ __launch_bounds__(256) void wide_adam_kernel(WideAdamExArgs x, const 
     adam_scalars(lr_a, pow4[2], pow4[3], ss_a, bc2s_a);                 // pow4 already advanced: beta^(t+1)
     adam_scalars(lr_c, pow4[0], pow4[1], ss_c, bc2s_c);
   } else {
-    adam_scalars(a.lr_actor, x.pow_b1_a * (double)a.b1, x.pow_b2_a * (double)a.b2, ss_a, bc2s_a);
-    adam_scalars(a.lr_critic, a.pow_b1 * (double)a.b1, a.pow_b2 * (double)a.b2, ss_c, bc2s_c);
+    adam_scalars(a.lr_actor, x.pow_b1_a * a.b1d, x.pow_b2_a * a.b2d, ss_a, bc2s_a);
+    adam_scalars(a.lr_critic, a.pow_b1 * a.b1d, a.pow_b2 * a.b2d, ss_c, bc2s_c);
   }
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.P; i += (int64_t)gridDim.x * 256) {
     if (i >= x.adam_begin && i < x.adam_end) {
       const bool act = i >= a.actor_begin;
-      const AdamOut o = adam1(a.theta[i], a.grad[i] * coef, a.m[i], a.v[i], a.b1, a.b2, a.eps, act ? ss_a : ss_c, act ? bc2s_a : bc2s_c);
+      const AdamOut o = adam1(a.theta[i], a.grad[i] * coef, a.m[i], a.v[i], a.b2, a.w1, a.w2, a.eps, act ? ss_a : ss_c, act ? bc2s_a : bc2s_c);
       a.theta[i] = o.p; a.m[i] = o.m; a.v[i] = o.v;
     } else if (x.scale_rest) {
       a.grad[i] = a.grad[i] * coef;
@@ -768,10 +771,13 @@ int wide_clip_adam(const char* entry, float* theta, float* grad, float* adam_m, 
   int64_t blocks = (n_params + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   SPO_REQUIRE((int64_t)partial_capacity >= blocks * 3, "%s: partial workspace too small", who);
-  const double b1 = (double)cfg->beta1, b2 = (double)cfg->beta2;
+  double b1 = 0.0, b2 = 0.0;          // the betas the caller meant (csrc/adam_host.h): clocks and weights both come from them
+  float w1, w2;
+  SPO_REQUIRE(adam_beta_host(cfg->beta1, &b1, &w1) && adam_beta_host(cfg->beta2, &b2, &w2), "%s: betas (%g, %g) outside [0, 1)", who,
+              (double)cfg->beta1, (double)cfg->beta2);
   WideAdamArgs a{theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin,
                  cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
-                 cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, dev_clocks ? 1.0 : pow(b1, (double)step_critics),
+                 cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, w1, w2, b1, b2, dev_clocks ? 1.0 : pow(b1, (double)step_critics),
                  dev_clocks ? 1.0 : pow(b2, (double)step_critics), partial_ws, scalars4_out, losses3_inout};
   WideAdamExArgs x{a, adam_begin, adam_end, scale_rest, dev_clocks ? 1.0 : pow(b1, (double)step_actor),
                    dev_clocks ? 1.0 : pow(b2, (double)step_actor)};

@@ -729,9 +729,10 @@ class _WideOps:
     # ------------------------------------------------------------------ graph-replayed minibatch steps
     def _sync_pow4(self) -> None:
         """Device clocks from the host step counts (start of a pass, after an eager step)."""
-        b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
         tc, ta = self.adam_step, self.adam_step + self.adam_step_actor_extra
         c = self._cfg_struct()                    # (c_float fields: the float32 values the host-clock kernels receive)
+        # the betas the caller meant, as the library recovers them (csrc/adam_host.h): the shortest decimal of the float32 value
+        b1, b2 = float(str(np.float32(c.beta1))), float(str(np.float32(c.beta2)))
         self.pow4.copy_(torch.tensor([b1 ** tc, b2 ** tc, b1 ** ta, b2 ** ta, float(c.lr_actor), float(c.lr_critic)], dtype=torch.float64))
 
     @staticmethod

@@ -955,7 +955,7 @@ def test_wide_clip_adam_forms_agree_bitwise(dev):
     t = 7
     cfg = _abi.PpoCfg(obs_dim=60, act_dim=8, batch=64, use_critic_norm=1, use_value_coefficient=0, clip=0.2, max_grad_norm=40.0,
                       lr_actor=2e-4, lr_critic=3e-4, beta1=0.9, beta2=0.999, adam_eps=1e-8, l2_coef=0.001)
-    b1, b2 = float(cfg.beta1), float(cfg.beta2)                    # the betas as the library sees them: rounded to fp32
+    b1, b2 = 0.9, 0.999                        # the betas as the library's clocks see them: the decimals the float32 cfg fields stand for
     for P, r_end, c_end in ((700, 200, 400), (262144 + 77, 100003, 200006)):
         ab = c_end
         g = torch.Generator(device=dev).manual_seed(11)
