@@ -20,6 +20,8 @@ for _p in (ROOT, os.path.join(ROOT, "safe-policy-optimization_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import fp64_gate as G  # noqa: E402
+from fp64_gate import ORACLE_THREADS  # noqa: E402  (the float32 yardstick and the float64 reference of the GPU test)
 from oracle import restatement as R  # noqa: E402
 from test_gpu_parity import _synthetic_update_problem  # noqa: E402  (its tests carry the gpu marker; the builder needs no GPU)
 
@@ -33,7 +35,6 @@ ROWS_THREE_CHUNKS = 3 * 256 * 64 + 5          # 49 157: every workgroup accumula
 #                                               (surrogate gradient and Fisher-vector product only)
 CASES = [(D, A, M) for D, A in SHAPES for M in ROWS] + [HUMANOID + (ROWS_CROSS_CHUNK,), HUMANOID + (ROWS_THREE_CHUNKS,)]
 MOVE = 0.02                                   # line search: theta_actor += MOVE * randn (test_cpo128_primitives_vs_oracle)
-ORACLE_THREADS = 4                            # the float32 yardstick and the float64 reference of the GPU test
 
 
 def seed_of(D):
@@ -79,9 +80,7 @@ def oracle(D, A, M, dtype_name, threads=ORACLE_THREADS):
     """What CPOEngine's three primitives return for case (D, A, M), by the oracle in `dtype_name` on `threads` torch threads:
     float64 numpy vectors and python floats."""
     dtype = getattr(torch, dtype_name)
-    before = torch.get_num_threads()
-    torch.set_num_threads(threads)
-    try:
+    with G.on_oracle_threads(threads):
         p = problem(D, A, M)
         ref = oracle_policy(D, A, M, dtype)
         data = {k: v.to(dtype) for k, v in p["data"].items()}
@@ -104,21 +103,10 @@ def oracle(D, A, M, dtype_name, threads=ORACLE_THREADS):
                 out["moved_loss_r"] = float(R.cpo_surrogate(ref, data, "r"))
                 out["moved_loss_c"] = float(R.cpo_surrogate(ref, data, "c"))
         return out
-    finally:
-        torch.set_num_threads(before)
-
-
-def gate(hip, f32, f64, floor, what=""):
-    """fp64 yardstick of tests/test_gpu_cpo_obs128.py::_gate."""
-    d_hip, d_32 = abs(float(hip) - float(f64)), abs(float(f32) - float(f64))
-    print(f"{what}: |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  floor {floor:.3e}")
-    assert d_hip <= 3.0 * d_32 + floor, (what, float(hip), float(f32), float(f64), d_hip, d_32, floor)
 
 
 def gate_fvp(hv, hv32, hv64, what=""):
-    """test_cpo128_primitives_vs_oracle's two Fisher-vector gates: 3 d_32 + 1e-6 scale in the max-norm, and the float32 allclose."""
-    scale = np.abs(hv64).max()
-    d_hip, d_32 = np.abs(hv - hv64).max(), np.abs(hv32 - hv64).max()
-    print(f"fvp {what}: |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  scale {scale:.3e}")
-    assert d_hip <= 3.0 * d_32 + 1e-6 * scale, (d_hip, d_32, scale)
-    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * scale)
+    """test_cpo128_primitives_vs_oracle's two Fisher-vector gates: fp64_gate.gate at 1e-6 max|f64| in the max-norm, and the
+    float32 allclose."""
+    G.gate(hv, hv32, hv64, f"fvp {what}", norms=G.MAX)
+    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * np.abs(hv64).max())

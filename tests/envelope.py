@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+import fp64_gate as G
 from oracle import restatement as R
 
 
@@ -92,7 +93,7 @@ def adam_noise_directions(dh, d32, frac=1e-4, factor=30.0, slack=10.0):
 def theta_envelope(hip, f32, f64, c=3.0, floor_abs=2e-7, floor_abs_max=None, noise_directions=False):
     """L2 and max-abs distance of the parameter vector from the fp64 trajectory against c x the fp32 reference's own
     distance (+ floor_abs per element: half an fp32 ulp of an O(1) parameter; floor_abs_max: a separate floor for the max-norm
-    gate, see tests/test_gpu_wide_dims.py::_theta_floor).  noise_directions: adam_noise_directions() first.  Returns the worse
+    gate, see theta_floor).  noise_directions: adam_noise_directions() first.  Returns the worse
     of the two ratios."""
     hip, f32, f64 = (np.asarray(x, np.float64).reshape(-1) for x in (hip, f32, f64))
     info = {}
@@ -207,59 +208,44 @@ def replay_ppo_lag_trace(z, dtype=torch.float64):
 # Round 5: the remaining trace replays under the same yardstick
 # ------------------------------------------------------------------------------------------------------------------------
 def theta_floor(lr, nsteps):
-    """Max-norm floor for parameter gates after `nsteps` Adam steps at wide input layers (tests/test_gpu_wide_dims.py::_theta_floor:
-    half an ulp of an O(1) parameter + 0.3 % of the distance Adam can move an element in that many steps; the L2 gate keeps the
-    plain floor)."""
+    """Max-norm floor for parameter gates after `nsteps` Adam steps at wide input layers: half an ulp of an O(1) parameter + 0.3 %
+    of the distance Adam can move an element in that many steps.  The L2 gate (typical elements) keeps the plain floor; the max
+    over ~25 000 elements finds the few whose gradient is ~1e-3 of the typical size (1 in 10^3 of a Gaussian): rounding noise of
+    relative size 1e-6 on the gradient scale is 1e-3 of THEIR gradient, and Adam's normalised step moves them lr x that per step
+    on either side.  With a 376-wide first layer an MFMA accumulator chains 94 sequential products where the reference's blocked
+    sgemm sums 16-wide partials, so the HIP maximum sits ~5x above the fp32 oracle's (5.2e-6 against 1.0e-6 after 6 steps at lr
+    3e-4) while its L2 distance stays inside 3x."""
     return 2e-7 + 3e-3 * lr * nsteps
 
 
-def gate_array(hip, f32, f64, what, rel_floor=1e-6, c=3.0, noise_directions=False):
-    """|hip - f64| <= c |f32 - f64| + rel_floor * max|f64| in max-norm and in L2 (per sqrt(n)); noise_directions:
-    adam_noise_directions() first (parameters after Adam steps at wide input layers)."""
+def gate_array(hip, f32, f64, what, rel_floor=1e-6, c=G.C, noise_directions=False):
+    """fp64_gate.gate at rel_floor * max|f64| in max-norm and in L2; noise_directions: adam_noise_directions() first (parameters
+    after Adam steps at wide input layers).  Returns (worst hip, reference) deviations relative to max|f64|."""
     hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
-    assert hip.shape == f32.shape == f64.shape, (what, hip.shape, f32.shape, f64.shape)
-    assert np.isfinite(hip).all(), f"{what}: non-finite HIP values"
     if noise_directions:
-        # round 6 (VERDICT r05): first the gate WITHOUT the exemption and at the narrow kernels' floor (1e-6); the exemption and the
-        # wider floor are taken only where that fails, with the measured numbers in the test log
-        sc0 = max(float(np.abs(f64).max()), 1e-30)
+        # first the gate WITHOUT the exemption and at the narrow kernels' floor (1e-6); the exemption and the wider floor are
+        # taken only where that fails, with the measured numbers in the test log
+        g = G.gate(hip, f32, f64, what, c=c, rel_floor=1e-6, enforce=False)
+        if g.ratio <= 1.0:
+            return g.d_hip / g.scale, g.d_32 / g.scale
         dh0, d320 = np.abs(hip - f64), np.abs(f32 - f64)
-        n0 = np.sqrt(hip.size)
-        strict = max(dh0.max() / (c * d320.max() + 1e-6 * sc0), np.linalg.norm(dh0) / (c * np.linalg.norm(d320) + 1e-6 * sc0 * n0))
-        if strict <= 1.0:
-            return float(dh0.max() / sc0), float(d320.max() / sc0)
         mask, ok = adam_noise_directions(dh0, d320)
         worst = float((dh0[mask] / d320[mask]).max()) if mask.any() else 0.0
-        print(f"[envelope] {what}: exemption IN USE (rel_floor {rel_floor:g}): ratio without it at 1e-6 {strict:.2f}; {int(mask.sum())} of "
+        print(f"[envelope] {what}: exemption IN USE (rel_floor {rel_floor:g}): ratio without it at 1e-6 {g.ratio:.2f}; {int(mask.sum())} of "
               f"{hip.size} elements singled out by the reference's own distance, worst |hip-f64| / |f32-f64| on them {worst:.2f} (gate 10)")
         assert ok, f"{what}: an Adam noise direction of the reference is more than 10 x further from float64 on the HIP path"
         hip, f32, f64 = hip[~mask], f32[~mask], f64[~mask]
-    sc = max(float(np.abs(f64).max()), 1e-30)
-    dh, d32 = np.abs(hip - f64), np.abs(f32 - f64)
-    assert dh.max() <= c * d32.max() + rel_floor * sc, \
-        f"{what}: max |hip - f64| {dh.max():.3e} > {c} x |f32 - f64| {d32.max():.3e} + {rel_floor:g} x {sc:.3e}"
-    n = np.sqrt(hip.size)
-    assert np.linalg.norm(dh) <= c * np.linalg.norm(d32) + rel_floor * sc * n, \
-        f"{what}: L2 |hip - f64| {np.linalg.norm(dh):.3e} > {c} x |f32 - f64| {np.linalg.norm(d32):.3e} + floor"
-    return float(dh.max() / sc), float(d32.max() / sc)
+    g = G.gate(hip, f32, f64, what, c=c, rel_floor=rel_floor)
+    return g.d_hip / g.scale, g.d_32 / g.scale
 
 
-def gate_scalars(rows, what, rel_floor=1e-6, c=3.0, scale=None):
-    """rows: [(name, hip, f32, f64)] of scalars of ONE kind of quantity (e.g. the curvature x^T H x of every epoch of a trace).
-    A single scalar's |f32 - f64| is one draw of the reference's rounding noise -- it can be 0 by chance --, so the yardstick is
-    the largest RELATIVE deviation the reference shows over the group: |hip - f64| / |f64| <= c * max_i(|f32_i - f64_i| / |f64_i|)
-    + rel_floor for every member.  `scale`: measure the deviations against this magnitude instead of |f64| -- for a quantity
+def gate_scalars(rows, what, rel_floor=1e-6, c=G.C, scale=None):
+    """fp64_gate.gate_group in max-norm over rows = [(name, hip, f32, f64)], scalars of ONE kind of quantity (e.g. the curvature
+    x^T H x of every epoch of a trace).  `scale`: measure the deviations against this magnitude instead of |f64| -- for a quantity
     that is a cancelling sum (a surrogate loss -mean(ratio * adv) over standardised advantages is ~0 +- rounding: relative to
     itself every evaluation is 100 % off).  Returns (worst hip, yardstick) deviations."""
-    rel = lambda a, b: abs(a - b) / (max(abs(b), 1e-30) if scale is None else scale)
-    yard = max(rel(f32, f64) for _, _, f32, f64 in rows)
-    worst = 0.0
-    for name, hip, f32, f64 in rows:
-        d = rel(hip, f64)
-        assert np.isfinite(hip) and d <= c * yard + rel_floor, \
-            f"{what} / {name}: |hip - f64| / |f64| = {d:.3e} > {c} x {yard:.3e} (largest deviation of the reference's fp32 in the group) + {rel_floor:g}; hip {hip!r} f32 {f32!r} f64 {f64!r}"
-        worst = max(worst, d)
-    return worst, yard
+    g = G.gate_group([(hip, f32, f64, scale) for _, hip, f32, f64 in rows], what, c=c, rel_floor=rel_floor, l2=False)
+    return g.d_hip, g.d_32
 
 
 def _policy_in(z, prefix, dtype, only=None):

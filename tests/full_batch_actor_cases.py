@@ -5,7 +5,7 @@ of csrc/policy.hip at KIN 16 / 32 / 64 / 128), every problem built on the CPU fr
 tests/test_full_batch_actor_cases_host.py checks on the CPU that the problems keep the gates of the GPU test meaningful.
 
 Every oracle result is computed once per process (functools.lru_cache) and shared; callers do not modify what they get.  The
-oracles run on ORACLE_THREADS torch threads whatever the host offers (blocked sums round differently with the thread count, and
+oracles run on fp64_gate.ORACLE_THREADS torch threads whatever the host offers (blocked sums round differently with the thread count, and
 the float32 oracle's rounding is the yardstick), and put the count back."""
 import functools
 import os
@@ -19,6 +19,7 @@ for _p in (ROOT, os.path.join(ROOT, "safe-policy-optimization_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import fp64_gate as G  # noqa: E402
 from oracle import restatement as R  # noqa: E402
 from test_gpu_parity import _synthetic_update_problem  # noqa: E402  (its tests carry the gpu marker; the builder needs no GPU)
 
@@ -45,19 +46,6 @@ KL_CAPPED = [1, 2]                                                # kl_partials_
 
 # the CPU companion leaves out the two largest row counts
 HOST_CPO_ROWS = [CPO_ROWS_ALL, 1, 63]
-ORACLE_THREADS = 4
-
-
-def _on_oracle_threads(fn):
-    @functools.wraps(fn)
-    def run(*a):
-        threads = torch.get_num_threads()
-        torch.set_num_threads(ORACLE_THREADS)
-        try:
-            return fn(*a)
-        finally:
-            torch.set_num_threads(threads)
-    return run
 
 
 def kin(D):
@@ -86,7 +74,7 @@ def oracle_policy(state_dict, D, A, dtype):
 
 # ------------------------------------------------------------------------------------------------------------- csrc/cpo.hip
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def cpo_problem(D, A, M):
     """Parameters, batch and directions of case (D, A, M), all float32 on the CPU.  The batch is _synthetic_update_problem's with
     one change: that builder's log_prob assumes a standard-normal policy, and against an initialised actor with log_std != 0 its
@@ -106,7 +94,7 @@ def cpo_problem(D, A, M):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def cpo_oracle(D, A, M, dtype_name):
     """Everything CPOEngine's three primitives return for case (D, A, M), from the oracle in `dtype_name`: float64 numpy vectors
     and python floats."""
@@ -156,7 +144,7 @@ def actor_problem(D, A, rows):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def actor_oracle(D, A, rows, dtype_name):
     """-> {"mean": [rows, A] float64 numpy, "kl": KL(old || moved).sum(-1).mean() with old = this dtype's own forward}."""
     dtype = getattr(torch, dtype_name)
@@ -180,51 +168,28 @@ def actor_oracle(D, A, rows, dtype_name):
 # 1e-6 * mean|adv_r| (surrogate means, line-search sums), 1e-6 * max|f64| (vectors), 1e-6 * kl64 (KL).  Every gate prints both
 # deviations and the floor before it asserts, and notes its ratio |hip - f64| / (3 |f32 - f64| + floor) under
 # (entry point, KIN form, rows) in RATIOS.
-REL_FLOOR, FACTOR = 1e-6, 3.0
-RATIOS = {}
-
-
-def _note(entry, D, rows, ratio):
-    key = (entry, kin(D), rows)
-    RATIOS[key] = max(RATIOS.get(key, 0.0), float(ratio))
+RATIOS = G.Ratios()
 
 
 def gate_vector(entry, D, rows, hip, f32, f64, what):
-    """envelope.gate_array (max-norm and L2 / sqrt(n), floor 1e-6 * max|f64|)."""
-    import envelope as E
-    hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
-    sc, n = max(float(np.abs(f64).max()), 1e-30), np.sqrt(f64.size)
-    dh, d32 = np.abs(hip - f64), np.abs(f32 - f64)
-    print(f"{what}: max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {REL_FLOOR * sc:.3e};  L2 |hip-f64| {np.linalg.norm(dh):.3e}  "
-          f"|f32-f64| {np.linalg.norm(d32):.3e}  floor {REL_FLOOR * sc * n:.3e}")
-    _note(entry, D, rows, max(dh.max() / (FACTOR * d32.max() + REL_FLOOR * sc),
-                              np.linalg.norm(dh) / (FACTOR * np.linalg.norm(d32) + REL_FLOOR * sc * n)))
-    E.gate_array(hip, f32, f64, what, rel_floor=REL_FLOOR, c=FACTOR)
+    """fp64_gate.gate (max-norm and L2, floor 1e-6 * max|f64|)."""
+    G.gate(hip, f32, f64, what, note=lambda g: RATIOS.note((entry, kin(D), rows), g.ratio, what))
 
 
 def gate_group(entry, rows, members, what):
-    """envelope.gate_scalars over the scalars of ONE kind of all shapes of one row count.  members: [(name, D, hip, f32, f64,
-    scale)]; scale = the case's mean|adv_r| for a surrogate loss (each member is measured against ITS OWN case's scale: it is
-    divided by it and the group gated with scale = 1), None for a KL (measured against |f64|).  The yardstick is the largest
-    such deviation of the float32 oracle in the group.  Returns it."""
-    import envelope as E
-    unit = lambda f64, s: max(abs(f64), 1e-30) if s is None else s
-    yard = max(abs(f32 - f64) / unit(f64, s) for _, _, _, f32, f64, s in members)
-    for name, D, hip, f32, f64, s in members:
-        u = unit(f64, s)
-        print(f"{what} / {name}: |hip-f64| {abs(hip - f64):.3e}  |f32-f64| {abs(f32 - f64):.3e} (largest of the group: {yard * u:.3e})  "
-              f"floor {REL_FLOOR * u:.3e}")
-        _note(entry, D, rows, abs(hip - f64) / u / (FACTOR * yard + REL_FLOOR))
-    if all(s is None for *_, s in members):
-        E.gate_scalars([(n, h, a, b) for n, _, h, a, b, _ in members], what, rel_floor=REL_FLOOR, c=FACTOR)
-    else:
-        E.gate_scalars([(n, h / s, a / s, b / s) for n, _, h, a, b, s in members], what, rel_floor=REL_FLOOR, c=FACTOR, scale=1.0)
-    return yard
+    """fp64_gate.gate_group (max-norm) over the scalars of ONE kind of all shapes of one row count.  members: [(name, D, hip, f32,
+    f64, scale)]; scale = the case's mean|adv_r| for a surrogate loss (each member is measured against ITS OWN case's scale),
+    None for a KL (measured against |f64|).  The yardstick is the largest such deviation of the float32 oracle in the group.
+    Returns it."""
+    def note(g):
+        for (name, D, *_), ratio in zip(members, g.ratios):
+            RATIOS.note((entry, kin(D), rows), ratio, f"{what} / {name}")
+    return G.gate_group([m[2:] for m in members], what, l2=False, note=note).d_32
 
 
 def ratio_table():
     """RATIOS as text: one line per (entry point, KIN form, rows)."""
     lines = [f"{'entry point':<28} {'KIN':>4} {'rows':>6}  worst |hip-f64| / (3 |f32-f64| + floor)"]
-    for (entry, k, rows), r in sorted(RATIOS.items()):
+    for (entry, k, rows), (r, _) in sorted(RATIOS.items()):
         lines.append(f"{entry:<28} {k:>4} {rows:>6}  {r:.3f}")
     return "\n".join(lines)

@@ -14,7 +14,7 @@ the "on_bound" value-loss rows have value_preds = 0 and values = +-clip_param, w
 arithmetic and sits ON the inclusive bound (torch.clamp's gradient passes there, and so must the kernel's).
 
 Every oracle result is computed once per process (functools.lru_cache) and shared; callers do not modify what they get.  The
-oracles run on ORACLE_THREADS torch threads whatever the host offers (blocked sums round differently with the thread count, and
+oracles run on fp64_gate.ORACLE_THREADS torch threads whatever the host offers (blocked sums round differently with the thread count, and
 the float32 oracle's rounding is the yardstick), and put the count back."""
 import functools
 import os
@@ -29,7 +29,7 @@ for _p in (ROOT, os.path.join(ROOT, "safe-policy-optimization_amd")):
         sys.path.insert(0, _p)
 
 from oracle import ma_restatement as MR  # noqa: E402
-import ma_yardstick as Y  # noqa: E402
+import fp64_gate as G  # noqa: E402
 
 f32v = lambda x: float(np.float32(x))                            # the float32 value of a constant, as the C ABI receives it
 
@@ -46,7 +46,6 @@ VALUE_PARTIAL_DOUBLES, POPART_PARTIAL_DOUBLES, ADAM_PARTIAL_DOUBLES = WG_CAP, 2 
 SHARD_ROWS = 257                                                  # two-shard cases: rows_global = 2 x 257
 MARGIN = 1e-4                                                     # tests/test_gpu_ma_full_size.py's margin around a clip boundary
 MIN_SHARE = 0.10                                                  # every branch class holds at least this share of the rows
-ORACLE_THREADS = 4
 STD_COEFS = (1.0, 0.5)                                            # std_x_coef, std_y_coef of the reference's configs
 CLIP, HUBER_DELTA, VALUE_LOSS_COEF = f32v(0.2), f32v(0.7), 0.5
 UNCLIPPED = f32v(3e38)                                            # MACPO's clip_param
@@ -89,18 +88,6 @@ popart_name = lambda c: f"train{c[0]}/{c[1]}/{c[2]}/beta{c[3]}"
 SAMPLE_SHAPES = [(51, 5), (16, 16), (257, 1)] + [(r, a) for r in ROWS for a in (1, 5, 16) if (r, a) != (257, 1)]
 SAMPLE_COEFS = [STD_COEFS, (2.0, 1.5)]
 GAE_T, GAE_N = [1, 7, 9], [1, 255, 257]                           # below, around and past UNROLL = 8; one and two workgroups
-
-
-def _on_oracle_threads(fn):
-    @functools.wraps(fn)
-    def run(*a, **k):
-        threads = torch.get_num_threads()
-        torch.set_num_threads(ORACLE_THREADS)
-        try:
-            return fn(*a, **k)
-        finally:
-            torch.set_num_threads(threads)
-    return run
 
 
 def _seed(*parts):
@@ -148,7 +135,7 @@ def actor_decisions(p, form, dtype=torch.float64):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def actor_problem(form, masks, A, rows, cls=None):
     """float32 inputs of spo_ma_actor_loss.  old_logp = the float64 log-probability of the actions, rounded once, minus a log
     ratio: N(0, LOG_RATIO_STD) per row (split over the dimensions) or per element (per-dimension form); with cls = (region, sign)
@@ -199,7 +186,7 @@ def actor_problem(form, masks, A, rows, cls=None):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def actor_oracle(form, masks, A, rows, cls, dtype_name, variant=None):
     """MAPPO_L_Trainer.ppo_update / _ppo_update_unconstrained of oracle/ma_restatement.py from the network outputs on: `mean`
     and a per-row copy of log_std are leaves, (policy_loss - dist_entropy * entropy_coef).backward().  -> float64 numpy:
@@ -291,7 +278,7 @@ _VALUE_CLASS = {
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def value_problem(active, rows, cls=None):
     """float32 inputs of spo_ma_value_loss at clip_param 0.2, huber_delta 0.7: values - value_preds ~ N(0, 0.25) (42 % clipped),
     the normalised returns 0.3 + N(0, 1.5) around value_preds (the second PopArt call's differ from the first's by N(0, 0.05)).
@@ -334,7 +321,7 @@ def value_problem(active, rows, cls=None):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def value_oracle(active, rows, cls, dtype_name, variant=None):
     """OracleMATrainer.value_loss (mappolag.py:126-138, happo.py:117-120) on given normalised returns; `values` is a leaf and
     (loss * value_loss_coef).backward().  -> dvalues [rows], loss, loss_scale (the Huber terms are >= 0: the loss itself)."""
@@ -384,7 +371,7 @@ def popart_problem(cfg, rows):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def popart_oracle(cfg, rows, dtype_name, variant=None):
     """OraclePopArt(beta, epsilon)(x, train) from `state3` -> normalised rows, the three state floats, their scales (the absolute
     values of the two summed terms of each running statistic), the batch sums in this dtype, var before the 1e-2 clamp."""
@@ -429,7 +416,7 @@ def adam_problem(n, name):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def adam_oracle(n, name, dtype_name, variant=None):
     """torch.nn.utils.clip_grad_norm_ + torch.optim.Adam(lr, eps, weight_decay) step number `step` + 1 from the given moments
     -> norm (pre-clip), m, v, update = theta_after - theta_before."""
@@ -501,7 +488,7 @@ def sample_problem(rows, A, coefs):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def sample_oracle(rows, A, coefs, dtype_name, variant=None):
     """-> the sampled action mean + std * eps and its per-dimension log-probabilities, the log-probabilities of the mean
     (deterministic) and of the given action (spo_ma_log_probs)."""
@@ -537,54 +524,27 @@ def gae_problem(T, N):
 
 
 # ----------------------------------------------------------------------------------------------------------------------- gates
-# |hip - f64| <= 3 |f32 - f64| + floor in max-norm and L2 (tests/ma_yardstick.gate), floor = 1e-6 of the quantity's scale: these are
+# |hip - f64| <= 3 |f32 - f64| + floor in max-norm and L2 (tests/fp64_gate.py), floor = 1e-6 of the quantity's scale: these are
 # single evaluations from identical state.  Scale: max|f64| of a vector; for a sum with cancellation the float64 sum / mean of the
 # absolute values of its terms (as test_wide_cpo_primitives_vs_oracle uses mean|adv|); for the Adam update the floor is half an ulp
 # of max|theta| instead.  Every gate prints both deviations and the floor before it asserts, and notes its ratio
 # |hip - f64| / (3 |f32 - f64| + floor) under (entry point, form, act_dim, rows) in RATIOS.
-REL_FLOOR, FACTOR = 1e-6, Y.C
-RATIOS = {}
-
-
-def _note(entry, form, A, rows, ratio):
-    key = (entry, str(form), A, rows)
-    RATIOS[key] = max(RATIOS.get(key, 0.0), float(ratio))
+RATIOS = G.Ratios()
 
 
 def gate(entry, form, A, rows, hip, f32, f64, what, scale=None, floor=None):
-    """One array (or scalar) of one case.  scale: None -> max|f64|; a number; or an array of per-element scales (each element is
-    divided by its own and the vector gated with scale 1).  floor: an absolute floor in place of REL_FLOOR * scale."""
-    hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
-    if np.ndim(scale) > 0:
-        s = np.maximum(np.asarray(scale, np.float64).reshape(-1), 1e-30)
-        hip, f32, f64, scale = hip / s, f32 / s, f64 / s, 1.0
-    sc = max(float(np.abs(f64).max()) if scale is None else float(scale), 1e-30)
-    fl = REL_FLOOR * sc if floor is None else float(floor)
-    dh, d32, n = np.abs(hip - f64), np.abs(f32 - f64), np.sqrt(f64.size)
-    print(f"{what}: max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {fl:.3e};  L2 |hip-f64| {np.linalg.norm(dh):.3e}  "
-          f"|f32-f64| {np.linalg.norm(d32):.3e}  floor {fl * n:.3e}")
-    ratio = max(dh.max() / (FACTOR * d32.max() + fl), np.linalg.norm(dh) / (FACTOR * np.linalg.norm(d32) + fl * n))
-    _note(entry, form, A, rows, ratio)
-    if floor is None:
-        Y.gate(hip, f32, f64, REL_FLOOR, what, scale=sc)
-    else:
-        Y.gate(hip, f32, f64, 1.0, what, scale=fl)
-    return ratio
+    """fp64_gate.gate on one array (or scalar) of one case.  scale: None -> max|f64|; a number; or an array of per-element
+    scales.  floor: an absolute floor in place of 1e-6 x scale.  -> the ratio."""
+    return G.gate(hip, f32, f64, what, scale=scale, floor=floor, note=lambda g: RATIOS.note((entry, str(form), A, rows), g.ratio, what)).ratio
 
 
 def gate_group(entry, members, what):
-    """Scalars of ONE kind over several cases (a single scalar's |f32 - f64| is one draw of rounding noise and can be 0 by
-    chance): members = [(form, A, rows, hip, f32, f64, scale)], each divided by its own scale, the vector gated with scale 1 --
-    the yardstick is the float32 oracle's largest (max-norm) and root-mean-square (L2) deviation in the group.  Returns the
-    yardstick's max-norm."""
-    s = np.array([max(abs(m[6]), 1e-30) for m in members])
-    hip, f32, f64 = (np.array([m[k] for m in members], np.float64) / s for k in (3, 4, 5))
-    dh, d32 = np.abs(hip - f64), np.abs(f32 - f64)
-    print(f"{what} ({len(members)} cases): max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {REL_FLOOR:.1e} (of each case's scale)")
-    for m, d in zip(members, dh):
-        _note(entry, m[0], m[1], m[2], d / (FACTOR * d32.max() + REL_FLOOR))
-    Y.gate(hip, f32, f64, REL_FLOOR, what, scale=1.0)
-    return float(d32.max())
+    """fp64_gate.gate_group (max-norm and L2) on scalars of ONE kind over several cases: members = [(form, A, rows, hip, f32, f64,
+    scale)].  Returns the yardstick's max-norm."""
+    def note(g):
+        for m, ratio in zip(members, g.ratios):
+            RATIOS.note((entry, str(m[0]), m[1], m[2]), ratio, what)
+    return G.gate_group([m[3:] for m in members], what, note=note).d_32
 
 
 SCALAR_NAMES = ("policy_loss", "dist_entropy", "mean(imp)", "mean(imp * cost_adv)", "sum(active)")
@@ -637,7 +597,7 @@ def ratio_table():
     """RATIOS as text: one line per (entry point, form, act_dim, rows), then the worst ratio per entry point."""
     lines = [f"{'entry point':<24} {'form':<28} {'act':>3} {'rows':>7}  worst |hip-f64| / (3 |f32-f64| + floor)"]
     worst = {}
-    for (entry, form, A, rows), r in sorted(RATIOS.items(), key=lambda kv: (kv[0][0], kv[0][1], int(kv[0][2] or 0), kv[0][3])):
+    for (entry, form, A, rows), (r, _) in sorted(RATIOS.items(), key=lambda kv: (kv[0][0], kv[0][1], int(kv[0][2] or 0), kv[0][3])):
         lines.append(f"{entry:<24} {form:<28} {A or '-':>3} {rows:>7}  {r:.3f}")
         if r >= worst.get(entry, (-1.0,))[0]:
             worst[entry] = (r, form, A, rows)

@@ -17,34 +17,21 @@ import copy
 import numpy as np
 import torch
 
+import fp64_gate as G
 from oracle import ma_restatement as MR
 
-C = 3.0
+C = G.C
 
 
 def gate(hip, f32, f64, rel_floor=1e-6, what="", scale=None):
-    """Array gate in max-norm and L2.  Returns (d_hip_max, d_32_max) for reporting."""
-    hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
-    assert hip.shape == f32.shape == f64.shape, (what, hip.shape, f32.shape, f64.shape)
-    assert np.isfinite(hip).all(), f"{what}: non-finite HIP values"
-    sc = float(np.abs(f64).max()) if scale is None else float(scale)
-    sc = max(sc, 1e-30)
-    d_hip, d_32 = np.abs(hip - f64), np.abs(f32 - f64)
-    assert d_hip.max() <= C * d_32.max() + rel_floor * sc, \
-        f"{what}: max |hip - f64| {d_hip.max():.3e} > {C} x |f32 - f64| {d_32.max():.3e} + {rel_floor:g} x scale {sc:.3e}"
-    n = np.sqrt(hip.size)
-    assert np.linalg.norm(d_hip) <= C * np.linalg.norm(d_32) + rel_floor * sc * n, \
-        f"{what}: L2 |hip - f64| {np.linalg.norm(d_hip):.3e} > {C} x |f32 - f64| {np.linalg.norm(d_32):.3e} + floor"
-    return float(d_hip.max()), float(d_32.max())
+    """fp64_gate.gate in max-norm and L2.  Returns (d_hip_max, d_32_max) for reporting."""
+    g = G.gate(hip, f32, f64, what, scale=scale, rel_floor=rel_floor)
+    return g.d_hip, g.d_32
 
 
 def gate_rows(hip_rows, f32_rows, f64_rows, rel_floor=1e-5, what="", names=None):
-    """Logged scalars of several steps ([steps, columns]): every COLUMN (a loss, a norm, ...) is gated over the steps with
-    its own scale, so a small column is not hidden behind a large one."""
-    hip_rows, f32_rows, f64_rows = (np.asarray(t, np.float64) for t in (hip_rows, f32_rows, f64_rows))
-    assert hip_rows.shape == f32_rows.shape == f64_rows.shape, (what, hip_rows.shape, f32_rows.shape, f64_rows.shape)
-    for c in range(hip_rows.shape[1]):
-        gate(hip_rows[:, c], f32_rows[:, c], f64_rows[:, c], rel_floor, f"{what} column {names[c] if names else c}")
+    """fp64_gate.gate_rows: every COLUMN of [steps, columns] gated over the steps with its own scale."""
+    G.gate_rows(hip_rows, f32_rows, f64_rows, what, names, rel_floor=rel_floor)
 
 
 def to_dtype(obj, dtype):

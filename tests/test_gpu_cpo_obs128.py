@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import fp64_gate as G  # noqa: E402
 from oracle import restatement as R  # noqa: E402  (checker only)
 from test_gpu_parity import _synthetic_update_problem, _wide_pair  # noqa: E402
 
@@ -32,13 +33,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda:0")
-
-
-def _gate(hip, f32, f64, floor, what=""):
-    """fp64 yardstick of tests/test_gpu_wide_dims.py::_gate."""
-    d_hip, d_32 = abs(float(hip) - float(f64)), abs(float(f32) - float(f64))
-    print(f"{what}: |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  floor {floor:.3e}")
-    assert d_hip <= 3.0 * d_32 + floor, (what, float(hip), float(f32), float(f64), d_hip, d_32, floor)
 
 
 def _cpo_problem(D, A, hidden, N, T, dev, seed, expect_new_path=True):
@@ -130,17 +124,14 @@ def test_cpo128_primitives_vs_oracle(dev, D, A, M):
         g_ref = R.actor_flat_grads(ref.actor).numpy()
         g, mean = eng.surrogate_grad(b.data[key], sign)
         np.testing.assert_allclose(g.cpu().numpy(), g_ref, rtol=1e-4, atol=1e-5 * np.abs(g_ref).max())
-        _gate(sign * mean, loss.detach(), R.cpo_surrogate(ref64, data64, which).detach(), floor, f"surrogate {which}")
+        G.gate(sign * mean, loss.detach(), R.cpo_surrogate(ref64, data64, which).detach(), f"surrogate {which}", floor=floor, norms=G.MAX)
     v = torch.randn(eng.Pa, generator=torch.Generator().manual_seed(3))
     hv32 = R.cpo_fvp(v, ref, data["obs"]).double().numpy()
     hv64 = R.cpo_fvp(v.double(), ref64, data64["obs"]).numpy()
     hv_t = eng.fvp(v.to(dev))
     hv = hv_t.double().cpu().numpy()
-    scale = np.abs(hv64).max()
-    d_hip, d_32 = np.abs(hv - hv64).max(), np.abs(hv32 - hv64).max()
-    print(f"fvp ({D}, {A}, M {M}): |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  scale {scale:.3e}")
-    assert d_hip <= 3.0 * d_32 + 1e-6 * scale, (d_hip, d_32, scale)
-    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * scale)
+    G.gate(hv, hv32, hv64, f"fvp ({D}, {A}, M {M})", norms=G.MAX)
+    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * np.abs(hv64).max())
     # call-to-call consistency: bit-identical repeats, linear in the direction
     assert torch.equal(hv_t, eng.fvp(v.to(dev)))
     h2 = eng.fvp((2 * v).to(dev))
@@ -154,8 +145,8 @@ def test_cpo128_primitives_vs_oracle(dev, D, A, M):
     assert kl == 0.0
     assert (l_r, l_c, kl) == eng.linesearch_eval()
     with torch.no_grad():
-        _gate(l_r, R.cpo_surrogate(ref, data, "r"), R.cpo_surrogate(ref64, data64, "r"), floor, "line search r at theta_old")
-        _gate(l_c, R.cpo_surrogate(ref, data, "c"), R.cpo_surrogate(ref64, data64, "c"), floor, "line search c at theta_old")
+        G.gate(l_r, R.cpo_surrogate(ref, data, "r"), R.cpo_surrogate(ref64, data64, "r"), "line search r at theta_old", floor=floor, norms=G.MAX)
+        G.gate(l_c, R.cpo_surrogate(ref, data, "c"), R.cpo_surrogate(ref64, data64, "c"), "line search c at theta_old", floor=floor, norms=G.MAX)
 
         def moved(rf, dt):
             old = rf.actor(dt["obs"])
@@ -169,9 +160,9 @@ def test_cpo128_primitives_vs_oracle(dev, D, A, M):
         kl64, r64, c64 = moved(ref64, data64)
     l_r, l_c, kl = eng.linesearch_eval()
     assert kl == pytest.approx(kl32, rel=1e-4)
-    _gate(kl, kl32, kl64, 1e-6 * kl64, "KL at moved parameters")
-    _gate(l_r, r32, r64, floor, "line search r at moved parameters")
-    _gate(l_c, c32, c64, floor, "line search c at moved parameters")
+    G.gate(kl, kl32, kl64, "KL at moved parameters", floor=1e-6 * kl64, norms=G.MAX)
+    G.gate(l_r, r32, r64, "line search r at moved parameters", floor=floor, norms=G.MAX)
+    G.gate(l_c, c32, c64, "line search c at moved parameters", floor=floor, norms=G.MAX)
 
 
 @pytest.mark.parametrize("D,A", [(72, 2), (128, 16)])
@@ -187,13 +178,8 @@ def test_cpo128_full_size_surrogate_gradients_and_fvp_fp64_yardstick(dev, D, A):
     data64 = {k: v.double() for k, v in data32.items()}
 
     def gate(name, hip, v32, v64, floor_rel=2e-7):
-        hip, v32, v64 = (np.asarray(x, np.float64).reshape(-1) for x in (hip, v32, v64))
-        d_hip, d_32 = np.linalg.norm(hip - v64), np.linalg.norm(v32 - v64)
-        floor = floor_rel * np.abs(v64).max() * np.sqrt(v64.size)
-        print(f"cpo128 full size ({D}, {A}) {name}: |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  floor {floor:.3e}  |f64| {np.linalg.norm(v64):.3e}"
-              f"  max: hip {np.abs(hip - v64).max():.3e} f32 {np.abs(v32 - v64).max():.3e}")
-        assert d_hip <= 3.0 * d_32 + floor, (name, d_hip, d_32, floor)
-        assert np.abs(hip - v64).max() <= 3.0 * np.abs(v32 - v64).max() + floor_rel * np.abs(v64).max() * 8, name
+        G.gate(hip, v32, v64, f"cpo128 full size ({D}, {A}) {name}", rel_floor=floor_rel, norms=G.L2)
+        G.gate(hip, v32, v64, f"cpo128 full size ({D}, {A}) {name}", floor=floor_rel * np.abs(v64).max() * 8, norms=G.MAX)
 
     for which, key, sign in (("r", "adv_r", -1.0), ("c", "adv_c", 1.0)):
         outs = []
@@ -204,12 +190,10 @@ def test_cpo128_full_size_surrogate_gradients_and_fvp_fp64_yardstick(dev, D, A):
             outs.append((R.actor_flat_grads(ref.actor).double().numpy().copy(), float(loss.detach())))
         g, mean = eng.surrogate_grad(b.data[key], sign)
         gate(f"surrogate gradient {which}", g.cpu().numpy(), outs[0][0], outs[1][0])
-        d_h, d_32 = abs(sign * mean - outs[1][1]), abs(outs[0][1] - outs[1][1])
         with torch.no_grad():
             lp64 = ref64.actor(data64["obs"]).log_prob(data64["act"]).sum(-1)
             term_scale = float((torch.exp(lp64 - data64["log_prob"]) * data64[key]).abs().mean())
-        print(f"cpo128 full size ({D}, {A}) surrogate value {which}: |hip-f64| {d_h:.3e} |f32-f64| {d_32:.3e} term scale {term_scale:.3e}")
-        assert d_h <= 3.0 * d_32 + 1e-7 * term_scale, (which, sign * mean, outs[0][1], outs[1][1], term_scale)
+        G.gate(sign * mean, outs[0][1], outs[1][1], f"cpo128 full size ({D}, {A}) surrogate value {which}", scale=term_scale, rel_floor=1e-7, norms=G.MAX)
     v = torch.randn(eng.Pa, generator=torch.Generator().manual_seed(5))
     hv32 = R.cpo_fvp(v, ref32, data32["obs"]).double().numpy()
     hv64 = R.cpo_fvp(v.double(), ref64, data64["obs"]).numpy()
@@ -236,14 +220,9 @@ def _actor_step_check(dev, D, A, ep_costs, expect_new_path):
     assert out["acceptance_step"] == o32["accept"] == o64["accept"]
     for name, hip, v32, v64 in (("xHx", out["xHx"], float(o32["xHx"]), float(o64["xHx"])),
                                 ("alpha", out["alpha"], float(o32["alpha"]), float(o64["alpha"]))):
-        print(f"step ({D}, {A}, {ep_costs}) {name}: hip {hip!r} f32 {v32!r} f64 {v64!r}")
-        assert abs(hip - v64) <= 3.0 * abs(v32 - v64) + 2e-6 * abs(v64), (name, hip, v32, v64)
-    d_hip, d_32 = np.abs(th_hip - th64), np.abs(th32 - th64)
-    scale = np.abs(th64).max()
-    print(f"step ({D}, {A}, {ep_costs}) theta: L2 hip {np.linalg.norm(d_hip):.3e} f32 {np.linalg.norm(d_32):.3e}  max hip {d_hip.max():.3e} "
-          f"f32 {d_32.max():.3e}  scale {scale:.3e}")
-    assert np.linalg.norm(d_hip) <= 3.0 * np.linalg.norm(d_32) + 1e-7 * scale * np.sqrt(th64.size), (np.linalg.norm(d_hip), np.linalg.norm(d_32))
-    assert d_hip.max() <= 3.0 * d_32.max() + 1e-6 * scale, (d_hip.max(), d_32.max())
+        G.gate(hip, v32, v64, f"step ({D}, {A}, {ep_costs}) {name}", rel_floor=2e-6, norms=G.MAX)
+    G.gate(th_hip, th32, th64, f"step ({D}, {A}, {ep_costs}) theta", rel_floor=1e-7, norms=G.L2)
+    G.gate(th_hip, th32, th64, f"step ({D}, {A}, {ep_costs}) theta", norms=G.MAX)
     np.testing.assert_allclose(eng.flat_grad[eng.ls_off:].cpu().numpy(), out["b"].cpu().numpy())
 
 

@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import cpo_obs512_cases as C  # noqa: E402
+import fp64_gate as G  # noqa: E402
 from test_gpu_cpo_obs128 import _actor_step_check  # noqa: E402
 
 
@@ -118,7 +119,7 @@ def test_cpo512_primitives_vs_oracle(dev, D, A, M, monkeypatch):
         g_ref = o32["grad_" + which]
         g, mean = eng.surrogate_grad(b.data[key], sign)
         np.testing.assert_allclose(g.cpu().numpy(), g_ref, rtol=1e-4, atol=1e-5 * np.abs(g_ref).max())
-        C.gate(sign * mean, o32["loss_" + which], o64["loss_" + which], floor, f"surrogate {which}")
+        G.gate(sign * mean, o32["loss_" + which], o64["loss_" + which], f"surrogate {which}", floor=floor, norms=G.MAX)
     v = p["v"]
     hv_t = eng.fvp(v.to(dev))
     C.gate_fvp(hv_t.double().cpu().numpy(), o32["Fv"], o64["Fv"], f"({D}, {A}, M {M})")
@@ -136,14 +137,14 @@ def test_cpo512_primitives_vs_oracle(dev, D, A, M, monkeypatch):
     l_r, l_c, kl = eng.linesearch_eval()
     assert kl == 0.0
     assert (l_r, l_c, kl) == eng.linesearch_eval()
-    C.gate(l_r, o32["loss_r"], o64["loss_r"], floor, "line search r at theta_old")
-    C.gate(l_c, o32["loss_c"], o64["loss_c"], floor, "line search c at theta_old")
+    G.gate(l_r, o32["loss_r"], o64["loss_r"], "line search r at theta_old", floor=floor, norms=G.MAX)
+    G.gate(l_c, o32["loss_c"], o64["loss_c"], "line search c at theta_old", floor=floor, norms=G.MAX)
     eng.theta_actor.add_(p["delta"].to(dev))
     l_r, l_c, kl = eng.linesearch_eval()
     assert kl == pytest.approx(o32["moved_kl"], rel=1e-4)
-    C.gate(kl, o32["moved_kl"], o64["moved_kl"], 1e-6 * o64["moved_kl"], "KL at moved parameters")
-    C.gate(l_r, o32["moved_loss_r"], o64["moved_loss_r"], floor, "line search r at moved parameters")
-    C.gate(l_c, o32["moved_loss_c"], o64["moved_loss_c"], floor, "line search c at moved parameters")
+    G.gate(kl, o32["moved_kl"], o64["moved_kl"], "KL at moved parameters", floor=1e-6 * o64["moved_kl"], norms=G.MAX)
+    G.gate(l_r, o32["moved_loss_r"], o64["moved_loss_r"], "line search r at moved parameters", floor=floor, norms=G.MAX)
+    G.gate(l_c, o32["moved_loss_c"], o64["moved_loss_c"], "line search c at moved parameters", floor=floor, norms=G.MAX)
 
 
 def test_snapshot_means_match_the_oracle(dev, monkeypatch):
@@ -158,10 +159,7 @@ def test_snapshot_means_match_the_oracle(dev, monkeypatch):
         m32 = C.oracle_policy(D, A, M).actor(p["data"]["obs"]).mean.double().numpy()
         m64 = C.oracle_policy(D, A, M, torch.float64).actor(p["data"]["obs"].double()).mean.numpy()
     hip = eng.mean_old.view(M, A).double().cpu().numpy()
-    scale = np.abs(m64).max()
-    d_hip, d_32 = np.abs(hip - m64).max(), np.abs(m32 - m64).max()
-    print(f"means: |hip-f64| {d_hip:.3e}  |f32-f64| {d_32:.3e}  scale {scale:.3e}")
-    assert np.isfinite(hip).all() and d_hip <= 3.0 * d_32 + 1e-6 * scale
+    G.gate(hip, m32, m64, "means", norms=G.MAX)
     ls = p["state_dict"]["actor.log_std"] if "actor.log_std" in p["state_dict"] else eng.policy.actor.log_std.detach().cpu()
     assert torch.equal(eng.logstd_old.cpu(), ls.reshape(-1)) and torch.equal(eng.std_old, torch.exp(eng.logstd_old))
 

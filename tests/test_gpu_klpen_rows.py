@@ -16,7 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 from oracle import restatement as R  # noqa: E402  (checker only)
 from test_gpu_parity import _synthetic_update_problem, _wide_pair  # noqa: E402
-from test_gpu_wide_dims import _theta_floor  # noqa: E402
 
 CUP_COEF = (1 - 0.99 * 0.95) / (1 - 0.99)
 
@@ -264,7 +263,7 @@ def test_klpen_row_group_minibatch_steps_vs_oracle(dev, D, A, hidden, actor_only
     E.assert_loss_envelope(got[:, cols], ref_losses[:, cols], l64[:, cols], "KL-penalty pass on the row groups: losses", window=n_steps,
                            floor_rel=3e-6)
     E.assert_theta_envelope(pol.theta.cpu().numpy(), th32, th64, "KL-penalty pass on the row groups: theta",
-                            floor_abs_max=_theta_floor(3e-4, n_steps))
+                            floor_abs_max=E.theta_floor(3e-4, n_steps))
     if actor_only:
         off = pol.log_std_offset
         assert torch.equal(pol.theta[:off], theta0[:off])
@@ -317,7 +316,7 @@ def test_cup_first_stage_on_the_row_groups_vs_oracle(dev):
     np.testing.assert_allclose(got[0], ref_losses[0], rtol=1e-5, atol=2e-6)
     E.assert_loss_envelope(got, ref_losses, l64, "CUP first stage on the row groups: losses", window=n_steps, floor_rel=3e-6)
     E.assert_theta_envelope(pol.theta.cpu().numpy(), th32, th64, "CUP first stage on the row groups: theta",
-                            floor_abs_max=_theta_floor(3e-4, n_steps))
+                            floor_abs_max=E.theta_floor(3e-4, n_steps))
     assert eng.adam_step == n_steps and eng.adam_step_actor_extra == 5
 
 

@@ -15,19 +15,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import fp64_gate as G  # noqa: E402
 from oracle import restatement as R  # noqa: E402  (checker only)
 from test_gpu_parity import _synthetic_update_problem, _wide_pair  # noqa: E402
 
-
-def _theta_floor(lr, nsteps):
-    """Max-norm floor of the parameter gates in this file: half an ulp of an O(1) parameter + 0.3 % of the distance Adam can move
-    an element in `nsteps` steps.  The L2 gate (typical elements) keeps the plain floor; the max over ~25 000 elements finds the
-    few whose gradient is ~1e-3 of the typical size (1 in 10^3 of a Gaussian): rounding noise of relative size 1e-6 on the
-    gradient scale is 1e-3 of THEIR gradient, and Adam's normalised step moves them lr x that per step on either side.  With a
-    376-wide first layer an MFMA accumulator chains 94 sequential products where the reference's blocked sgemm sums 16-wide
-    partials, so the HIP maximum sits ~5x above the fp32 oracle's (5.2e-6 against 1.0e-6 after 6 steps at lr 3e-4) while its L2
-    distance stays inside 3x.  (Rounds 1-4 exempted 0.1 % of the parameters up to 2 x lr x nsteps: 600x this.)"""
-    return 2e-7 + 3e-3 * lr * nsteps
 
 def _floor_users(hip, f32, f64):
     """WHICH elements need the widened max-norm floor -- those further from float64 than 3 x the fp32 oracle's maximum
@@ -99,13 +90,6 @@ def test_wide_dims_policy_step_vs_oracle(dev, D, A, hidden):
     np.testing.assert_allclose(v_c.cpu().numpy(), vc_ref.numpy(), **tol)
 
 
-def _gate(hip, f32, f64, floor, what=""):
-    """fp64 yardstick: the HIP value may be at most 3x as far from the float64 evaluation as the reference's own float32
-    arithmetic is, plus a floor (sums with cancellation: a relative tolerance on the result would test the luck of the draw)."""
-    d_hip, d_32 = abs(float(hip) - float(f64)), abs(float(f32) - float(f64))
-    assert d_hip <= 3.0 * d_32 + floor, (what, float(hip), float(f32), float(f64), d_hip, d_32, floor)
-
-
 def _cpo_problem(D, A, hidden, M, dev, seed, chunk):
     from safepo.single_agent import cpo
     pol, ref = _wide_pair(D, A, hidden, dev, seed=seed)
@@ -145,22 +129,20 @@ def test_wide_cpo_primitives_vs_oracle(dev, D, A, hidden):
         g_ref = R.actor_flat_grads(ref.actor).numpy()
         g, mean = eng.surrogate_grad(b.data[key], sign)
         np.testing.assert_allclose(g.cpu().numpy(), g_ref, rtol=1e-4, atol=1e-5 * np.abs(g_ref).max())
-        _gate(sign * mean, loss.detach(), R.cpo_surrogate(ref64, data64, which).detach(), floor, f"surrogate {which}")
+        G.gate(sign * mean, loss.detach(), R.cpo_surrogate(ref64, data64, which).detach(), f"surrogate {which}", floor=floor, norms=G.MAX)
     v = torch.randn(eng.Pa, generator=torch.Generator().manual_seed(3))
     hv32 = R.cpo_fvp(v, ref, data["obs"]).double().numpy()
     hv64 = R.cpo_fvp(v.double(), ref64, data64["obs"]).numpy()
     hv = eng.fvp(v.to(dev)).double().cpu().numpy()
-    scale = np.abs(hv64).max()
-    d_hip, d_32 = np.abs(hv - hv64).max(), np.abs(hv32 - hv64).max()
-    assert d_hip <= 3.0 * d_32 + 1e-6 * scale, (d_hip, d_32, scale)      # fp64 yardstick: as close as the reference's own fp32
-    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * scale)
+    G.gate(hv, hv32, hv64, "fvp", norms=G.MAX)                           # fp64 yardstick: as close as the reference's own fp32
+    np.testing.assert_allclose(hv, hv32, rtol=1e-4, atol=1e-5 * np.abs(hv64).max())
     # line search: unchanged parameters -> KL == 0 and the two surrogates; moved parameters -> the oracle's values
     eng.snapshot_old_distribution()
     l_r, l_c, kl = eng.linesearch_eval()
     assert kl == pytest.approx(0.0, abs=1e-9)
     with torch.no_grad():
-        _gate(l_r, R.cpo_surrogate(ref, data, "r"), R.cpo_surrogate(ref64, data64, "r"), floor, "line search r at theta_old")
-        _gate(l_c, R.cpo_surrogate(ref, data, "c"), R.cpo_surrogate(ref64, data64, "c"), floor, "line search c at theta_old")
+        G.gate(l_r, R.cpo_surrogate(ref, data, "r"), R.cpo_surrogate(ref64, data64, "r"), "line search r at theta_old", floor=floor, norms=G.MAX)
+        G.gate(l_c, R.cpo_surrogate(ref, data, "c"), R.cpo_surrogate(ref64, data64, "c"), "line search c at theta_old", floor=floor, norms=G.MAX)
 
         def moved(rf, dt):
             old = rf.actor(dt["obs"])
@@ -174,9 +156,9 @@ def test_wide_cpo_primitives_vs_oracle(dev, D, A, hidden):
         kl64, r64, c64 = moved(ref64, data64)
     l_r, l_c, kl = eng.linesearch_eval()
     assert kl == pytest.approx(kl32, rel=1e-4)
-    _gate(kl, kl32, kl64, 1e-6 * kl64, "KL at moved parameters")
-    _gate(l_r, r32, r64, floor, "line search r at moved parameters")
-    _gate(l_c, c32, c64, floor, "line search c at moved parameters")
+    G.gate(kl, kl32, kl64, "KL at moved parameters", floor=1e-6 * kl64, norms=G.MAX)
+    G.gate(l_r, r32, r64, "line search r at moved parameters", floor=floor, norms=G.MAX)
+    G.gate(l_c, c32, c64, "line search c at moved parameters", floor=floor, norms=G.MAX)
 
 
 @pytest.mark.parametrize("D,A,hidden,ep_costs", [(72, 2, [64, 64], -1.0), (376, 17, [64, 64], 0.3), (376, 17, [64, 64], -1.0)])
@@ -199,11 +181,9 @@ def test_wide_cpo_actor_step_drift_envelope(dev, D, A, hidden, ep_costs):
     assert out["acceptance_step"] == o32["accept"] == o64["accept"]
     for name, hip, v32, v64 in (("xHx", out["xHx"], float(o32["xHx"]), float(o64["xHx"])),
                                 ("alpha", out["alpha"], float(o32["alpha"]), float(o64["alpha"]))):
-        assert abs(hip - v64) <= 3.0 * abs(v32 - v64) + 2e-6 * abs(v64), (name, hip, v32, v64)
-    d_hip, d_32 = np.abs(th_hip - th64), np.abs(th32 - th64)
-    scale = np.abs(th64).max()
-    assert np.linalg.norm(d_hip) <= 3.0 * np.linalg.norm(d_32) + 1e-7 * scale * np.sqrt(th64.size), (np.linalg.norm(d_hip), np.linalg.norm(d_32))
-    assert d_hip.max() <= 3.0 * d_32.max() + 1e-6 * scale, (d_hip.max(), d_32.max())
+        G.gate(hip, v32, v64, name, rel_floor=2e-6, norms=G.MAX)
+    G.gate(th_hip, th32, th64, "theta", rel_floor=1e-7, norms=G.L2)
+    G.gate(th_hip, th32, th64, "theta", norms=G.MAX)
     # the stale actor gradient the critic fit's joint clip will see (cpo.py:557) is the cost gradient b
     np.testing.assert_allclose(eng.flat_grad[eng.ls_off:].cpu().numpy(), out["b"].cpu().numpy())
 
@@ -266,7 +246,7 @@ def _critic_fit_check(dev, D, A, hidden, persistent, monkeypatch, M, iters, batc
     n_crit = want_th.size - n_act
     E.assert_loss_envelope(got, want, l64, "wide critic fit: losses", window=len(want))
     E.assert_theta_envelope(pol.theta.cpu().numpy()[:n_crit], want_th[:n_crit], th64[:n_crit], "wide critic fit: critics",
-                            floor_abs_max=_theta_floor(1e-3, iters * ((M + batch - 1) // batch)))
+                            floor_abs_max=E.theta_floor(1e-3, iters * ((M + batch - 1) // batch)))
     want_th = want_th.astype(np.float32)
     # the actor's parameters are untouched by the critic fit; its stale gradient shrank exactly like the oracle's .grad
     np.testing.assert_array_equal(pol.theta.cpu().numpy()[n_crit:], want_th[n_crit:])
@@ -348,7 +328,7 @@ def test_wide_kl_penalty_minibatch_steps_vs_oracle(dev, D, A, hidden, actor_only
     import envelope as E
     cols = [2] if actor_only else [0, 1, 2]
     E.assert_loss_envelope(got[:, cols], ref_losses[:, cols], l64[:, cols], "wide KL-penalty pass: losses", window=n_steps, floor_rel=3e-6)
-    E.assert_theta_envelope(pol.theta.cpu().numpy(), th32, th64, "wide KL-penalty pass: theta", floor_abs_max=_theta_floor(3e-4, n_steps))
+    E.assert_theta_envelope(pol.theta.cpu().numpy(), th32, th64, "wide KL-penalty pass: theta", floor_abs_max=E.theta_floor(3e-4, n_steps))
     if actor_only:
         off = pol.log_std_offset
         assert torch.equal(pol.theta[:off], theta0[:off])
@@ -377,7 +357,7 @@ def test_wide_dims_ppo_minibatch_steps_vs_oracle(dev, D, A, batch, steps):
     import envelope as E
     _, t64 = E.oracle_trajectory(ref0, problem, perm, batch, steps, torch.float64, [steps], hidden_sizes=hidden)
     E.assert_theta_envelope(pol.theta.cpu().numpy(), R.flat_params(ref).numpy(), t64[steps], f"wide dims {D}x{A}: theta after {steps} steps",
-                            floor_abs_max=_theta_floor(3e-4, steps))
+                            floor_abs_max=E.theta_floor(3e-4, steps))
 
 
 @pytest.mark.parametrize("D,A", [(376, 17), (130, 8), (512, 32), (129, 1), (200, 20)])
@@ -546,7 +526,7 @@ def test_feature_split_kernel_full_size_drift_envelope_at_humanoid_dims(dev):
     for k in ks:
         assert np.array_equal(runs[k][1], lh[:k]), f"the {k}-step launch is not a prefix of the {kmax}-step launch"
         rep[k] = E.assert_theta_envelope(runs[k][0], t32[k], t64[k], f"feature-split full size: theta after {k} steps",
-                                         floor_abs_max=_theta_floor(3e-4, k))
+                                         floor_abs_max=E.theta_floor(3e-4, k))
         users[k], frac = _floor_users(runs[k][0], t32[k], t64[k])
         #  the widened floor must be serving a handful of Adam-amplified elements, not a systematic offset: at most
         # 0.1 % of the vector may need it at any checkpoint
@@ -614,7 +594,7 @@ def test_feature_split_critic_fit_full_size_drift_envelope_at_humanoid_dims(dev,
     for k in ks:
         assert np.array_equal(hip[k][1], lh[:k]), f"the {k}-step launch is not a prefix of the {kmax}-step launch"
         rep[k] = E.assert_theta_envelope(hip[k][0], t32[k], t64[k], f"feature-split critic fit: critics after {k} steps",
-                                         floor_abs_max=_theta_floor(1e-3, k))
+                                         floor_abs_max=E.theta_floor(1e-3, k))
     print("critic_fit_ks_kernel, 376 / 17, 524 288 rows, drift envelope (ratio <= 1 passes):",
           {k: (round(v[0], 3), f"max |hip-f64| {v[1]['max_hip']:.2e} vs f32 {v[1]['max_f32']:.2e}") if k != "loss" else round(v, 3)
            for k, v in rep.items()})
@@ -708,7 +688,7 @@ def test_feature_split_kl_penalty_full_size_drift_envelope_at_humanoid_dims(dev,
     rep = {"loss": E.assert_loss_envelope(lh[:, cols], l32[:, cols], l64[:, cols], what, floor_rel=3e-6)}
     for k in ks:
         assert np.array_equal(hip[k][1], lh[:k], equal_nan=True), f"the {k}-step launch is not a prefix of the {kmax}-step launch"
-        rep[k] = E.assert_theta_envelope(hip[k][0], t32[k], t64[k], f"{what}: theta after {k} steps", floor_abs_max=_theta_floor(3e-4, k))
+        rep[k] = E.assert_theta_envelope(hip[k][0], t32[k], t64[k], f"{what}: theta after {k} steps", floor_abs_max=E.theta_floor(3e-4, k))
     if actor_only:
         off = pol.log_std_offset
         assert torch.equal(pol.theta[:off], theta0[:off])            # the critics are not touched by CUP's second stage
@@ -767,7 +747,7 @@ def test_feature_split_kernels_three_consecutive_launches_on_one_stream(dev, mon
     np.testing.assert_allclose(lh[:4], l32[:4], rtol=1e-5, atol=2e-6)
     E.assert_loss_envelope(lh, l32, l64, "three KL-penalty launches: losses", window=nst, floor_rel=3e-6)
     E.assert_theta_envelope(pol.theta.double().cpu().numpy(), t32, t64, "three KL-penalty launches: theta",
-                            floor_abs_max=_theta_floor(3e-4, passes * nst))
+                            floor_abs_max=E.theta_floor(3e-4, passes * nst))
 
 
 def test_two_feature_split_engines_update_concurrently_on_two_streams(dev):

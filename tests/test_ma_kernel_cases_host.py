@@ -73,7 +73,7 @@ def test_actor_cases_keep_the_gates_meaningful(rows):
         yard = C.gate_group("host", members, name)
         assert yard > 0 or name in ("sum(active)", "mean(imp * cost_adv)"), name
     assert any(m[6] > 0 for m in groups["mean(imp * cost_adv)"])
-    _third(max(r for (e, *_), r in C.RATIOS.items() if e == "host"))
+    _third(max(r for (e, *_), (r, _) in C.RATIOS.items() if e == "host"))
 
 
 @pytest.mark.parametrize("form,masks", C.ACTOR_FORMS)
@@ -117,7 +117,7 @@ def test_value_cases_keep_the_gates_meaningful(rows):
                 assert int(on.sum()) == (rows + 3) // 4 and bool((p["value_preds"][on] == 0).all())
             C.gate_value(f"active{active}/{cls}", rows, o32, o32, o64, losses, entry="host")
     assert C.gate_group("host", losses, "value loss") > 0 or rows == 2
-    _third(max(r for (e, *_), r in C.RATIOS.items() if e == "host"))
+    _third(max(r for (e, *_), (r, _) in C.RATIOS.items() if e == "host"))
 
 
 @pytest.mark.parametrize("active", C.VALUE_FORMS)
@@ -173,7 +173,7 @@ def test_adam_cases_keep_the_gates_meaningful(n):
         assert C.adam_update_floor(n, name) < 1e-3 * C.ADAM_LR                                     # the floor hides no step of size lr
         C.gate_adam(name, n, o32, o32, o64, norms, entry="host")
     assert C.gate_group("host", norms, "norm") >= 0
-    _third(max(r for (e, *_), r in C.RATIOS.items() if e == "host"))
+    _third(max(r for (e, *_), (r, _) in C.RATIOS.items() if e == "host"))
 
 
 def test_lamda_sample_and_gae_cases():

@@ -12,15 +12,15 @@ the same branch in every row.  One tie on purpose: rows with adv == 0 (`tie`), w
 is exactly zero.
 
 Every oracle result is computed once per process (functools.lru_cache) and shared; callers do not modify what they get.  The
-oracles run on ORACLE_THREADS torch threads whatever the host offers and put the count back."""
+oracles run on fp64_gate.ORACLE_THREADS torch threads whatever the host offers and put the count back."""
 import functools
 import os
 
 import numpy as np
 import torch
 
-from ma_kernel_cases import _on_oracle_threads, _redraw_until_clear, _seed, f32v, MARGIN, MIN_SHARE, ORACLE_THREADS  # noqa: F401  (sets sys.path)
-import ma_yardstick as Y
+from ma_kernel_cases import _redraw_until_clear, _seed, f32v, MARGIN, MIN_SHARE  # noqa: F401  (sets sys.path)
+import fp64_gate as G
 
 Normal = torch.distributions.Normal
 kl_divergence = torch.distributions.kl_divergence
@@ -93,7 +93,7 @@ def actor_decisions(p, dtype=torch.float64):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def actor_problem(A, rows, cls=None, tie=False, bound="mid"):
     """float32 inputs of every actor-side loss kernel on ONE draw: mean, log_std, act, adv (adv_b: the line search's second
     advantage), logp_old = the float64 log-probability of the actions minus a log ratio ~ N(0, LOG_RATIO_STD), rounded once (cls =
@@ -172,7 +172,7 @@ def _grads(loss, mean, ls_rows):
 
 # ------------------------------------------------------------------------------------------- spo_wide_actor_loss, mode 0 and 1
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def clip_oracle(A, rows, cls, tie, dtype_name, variant=None, rows_total=None):
     """-mean(min(ratio * adv, clamp(ratio, 1 - clip, 1 + clip) * adv)) (ppo_lag.py:316-319) over rows_total rows (the problem's
     own when None) -> d_mean, d_log_std (+ the sum of its absolute per-row terms), term_sum = sum of the min terms, loss,
@@ -195,7 +195,7 @@ def clip_oracle(A, rows, cls, tie, dtype_name, variant=None, rows_total=None):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def surr_oracle(A, rows, sign, dtype_name, variant=None):
     """sign * mean(ratio * adv) (cpo.py:356-381) -> as clip_oracle; term_sum = sum ratio * adv, loss = its plain mean (what the
     kernel's loss_out holds: the caller applies the sign)."""
@@ -210,7 +210,7 @@ def surr_oracle(A, rows, sign, dtype_name, variant=None):
 
 # ------------------------------------------------------------- spo_wide_actor_loss mode 2, spo_wide_kl_penalty_split / _combine
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def klpen_oracle(A, rows, bound, dtype_name, variant=None, pg_coef=PG_COEF):
     """The KL-penalty loss of FOCOPS / CUP's second stage as the reference writes it (focops.py:326-333): temp_kl [rows, 1] and
     ratio * adv [rows] broadcast to [rows, rows], so the loss is mean(ind * kl) - pg_coef * mean(ind) * mean(ratio * adv).  ->
@@ -261,7 +261,7 @@ def linesearch_problem(A, rows, moved):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def linesearch_oracle(A, rows, moved, dtype_name, variant=None):
     """cpo.py:473-491 -> sums [3] = {sum ratio * adv_a, sum ratio * adv_b, sum over rows and dims of KL(old || new)}, scales [3]."""
     t = {k: v.to(getattr(torch, dtype_name)) for k, v in linesearch_problem(A, rows, moved).items()}
@@ -281,7 +281,7 @@ def critic_problem(rows, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def critic_oracle(rows, dtype_name, seed=0):
     """F.mse_loss of both critics and the gradients at their outputs -> d_vr, d_vc [rows], losses [2]."""
     t = {k: v.to(getattr(torch, dtype_name)) for k, v in critic_problem(rows, seed).items()}
@@ -299,7 +299,7 @@ def fvp_problem(A, rows):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def fvp_oracle(A, rows, rows_total, dtype_name, variant=None):
     """The cotangent of the Fisher-vector product: the gradient at `mean` of mean over rows_total rows AND act_dim dims of
     KL(old || new) has the Jacobian-vector product (J t) / sigma^2 / (rows_total * act_dim) (cpo.py:132-157, differentiated twice
@@ -326,7 +326,7 @@ def sample_problem(rows, A):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def sample_oracle(rows, A, dtype_name):
     """model.py:149-170: act = mean + std * eps (rsample), logp = Normal.log_prob(act).sum(-1); logp_det: of the mean itself."""
     t = {k: v.to(getattr(torch, dtype_name)) for k, v in sample_problem(rows, A).items()}
@@ -349,7 +349,7 @@ def kl_problem(rows, A, moved):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def kl_oracle(rows, A, moved, dtype_name, variant=None):
     t = {k: v.to(getattr(torch, dtype_name)) for k, v in kl_problem(rows, A, moved).items()}
     old, new = Normal(t["mean_old"], torch.exp(t["log_std_old"])), Normal(t["mean_new"], torch.exp(t["log_std_new"]))
@@ -408,7 +408,7 @@ def _split(flat, dims):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def mlp_oracle(dims, rows, dtype_name, variant=None):
     """The tanh MLP of model.py:30-48 -> every layer's activations, the flat gradient of sum(out * d_out) (autograd), the
     forward-mode tangent of the output along `tangent` (torch.func.jvp) and its per-element scale."""
@@ -496,7 +496,7 @@ def _adam1_numpy(p, g, m, v, w1, w2, b2, eps, step_size, inv_bc2_sqrt):
 
 
 @functools.lru_cache(maxsize=None)
-@_on_oracle_threads
+@G.on_oracle_threads()
 def adam_oracle(n, name, dtype_name, variant=None, rng="all", layout=None, steps=None, lr_override=None):
     """ppo_lag.py:310-329 on given gradients: the critics' L2 term l2 * sum p^2 added to their losses (autograd: 2 * l2 * p), the
     reward critic's loss doubled under use_value_coefficient, clip_grad_norm_ over [norm_begin, P), one torch.optim.Adam step per
@@ -584,60 +584,33 @@ def adam_update_floor(n, name, layout=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------- gates
-# |hip - f64| <= 3 |f32 - f64| + floor in max-norm and L2 (tests/ma_yardstick.gate), floor = 1e-6 of the quantity's scale: single
+# |hip - f64| <= 3 |f32 - f64| + floor in max-norm and L2 (tests/fp64_gate.py), floor = 1e-6 of the quantity's scale: single
 # evaluations from identical state.  Scale: max|f64| of a vector; for a sum with cancellation the float64 sum / mean of the absolute
-# values of its terms (surrogate means: mean |adv|, as tests/test_gpu_wide_dims.py::_gate takes it).  Every gate prints both
+# values of its terms (surrogate means: mean |adv|, as tests/test_gpu_wide_dims.py takes it).  Every gate prints both
 # deviations and the floor before it asserts and notes its ratio |hip - f64| / (3 |f32 - f64| + floor) under the running test.
-REL_FLOOR, FACTOR = 1e-6, Y.C
-RATIOS = {}
+RATIOS = G.Ratios()
 
 
-def _test_name():
-    return os.environ.get("PYTEST_CURRENT_TEST", "?").split("::")[-1].split(" (")[0]
-
-
-def _note(ratio, what):
-    key = _test_name()
-    if ratio >= RATIOS.get(key, (-1.0, ""))[0]:
-        RATIOS[key] = (float(ratio), what)
+def _note(g):
+    """Notes a fp64_gate.Gate under the running test."""
+    RATIOS.note(os.environ.get("PYTEST_CURRENT_TEST", "?").split("::")[-1].split(" (")[0], g.ratio, g.what)
 
 
 def gate(hip, f32, f64, what, scale=None, floor=None):
-    """One array (or scalar).  scale: None -> max|f64|; a number; or an array of per-element scales (each element is divided by
-    its own and the vector gated with scale 1).  floor: an absolute floor in place of REL_FLOOR * scale.  -> the ratio."""
-    hip, f32, f64 = (np.asarray(t, np.float64).reshape(-1) for t in (hip, f32, f64))
-    if np.ndim(scale) > 0:
-        s = np.maximum(np.asarray(scale, np.float64).reshape(-1), 1e-30)
-        hip, f32, f64, scale = hip / s, f32 / s, f64 / s, 1.0
-    sc = max(float(np.abs(f64).max()) if scale is None else float(scale), 1e-30)
-    fl = REL_FLOOR * sc if floor is None else float(floor)
-    dh, d32, n = np.abs(hip - f64), np.abs(f32 - f64), np.sqrt(f64.size)
-    print(f"{what}: max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {fl:.3e};  L2 |hip-f64| {np.linalg.norm(dh):.3e}  "
-          f"|f32-f64| {np.linalg.norm(d32):.3e}  floor {fl * n:.3e}")
-    ratio = max(dh.max() / (FACTOR * d32.max() + fl), np.linalg.norm(dh) / (FACTOR * np.linalg.norm(d32) + fl * n))
-    _note(ratio, what)
-    if floor is None:
-        Y.gate(hip, f32, f64, REL_FLOOR, what, scale=sc)
-    else:
-        Y.gate(hip, f32, f64, 1.0, what, scale=fl)
-    return ratio
+    """fp64_gate.gate on one array (or scalar).  scale: None -> max|f64|; a number; or an array of per-element scales.  floor: an
+    absolute floor in place of 1e-6 x scale.  -> the ratio."""
+    return G.gate(hip, f32, f64, what, scale=scale, floor=floor, note=_note).ratio
 
 
 def gate_group(members, what):
-    """Scalars of ONE kind over several cases (a single scalar's |f32 - f64| is one draw of rounding noise and can be 0 by chance):
-    members = [(hip, f32, f64, scale)], each divided by its own scale, the vector gated with scale 1.  -> the yardstick's max."""
-    s = np.array([max(abs(m[3]), 1e-30) for m in members])
-    hip, f32, f64 = (np.array([m[k] for m in members], np.float64) / s for k in (0, 1, 2))
-    dh, d32 = np.abs(hip - f64), np.abs(f32 - f64)
-    print(f"{what} ({len(members)} cases): max |hip-f64| {dh.max():.3e}  |f32-f64| {d32.max():.3e}  floor {REL_FLOOR:.1e} (of each case's scale)")
-    _note(max(dh.max() / (FACTOR * d32.max() + REL_FLOOR), np.linalg.norm(dh) / (FACTOR * np.linalg.norm(d32) + REL_FLOOR * np.sqrt(len(members)))), what)
-    Y.gate(hip, f32, f64, REL_FLOOR, what, scale=1.0)
-    return float(d32.max())
+    """fp64_gate.gate_group (max-norm and L2) on scalars of ONE kind over several cases: members = [(hip, f32, f64, scale)].
+    -> the yardstick's max."""
+    return G.gate_group(members, what, note=_note).d_32
 
 
 def gate_blocks(hip, f32, f64, blocks, what):
-    """A flat parameter vector, every block (offset, count) with its own scale.  -> the worst ratio."""
-    return max(gate(hip[o:o + c], f32[o:o + c], f64[o:o + c], f"{what} block [{o}, {o + c})") for o, c in blocks if c > 0)
+    """fp64_gate.gate_blocks: a flat parameter vector, every block (offset, count) with its own scale.  -> the worst ratio."""
+    return G.gate_blocks(hip, f32, f64, blocks, what, note=_note)
 
 
 def gate_actor_vectors(hip, o32, o64, what, sfx=""):
