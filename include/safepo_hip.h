@@ -1115,6 +1115,61 @@ int spo_wide_kl_penalty_grad_rows(const float* theta, const spo_mlp_net* critic,
 int spo_wide_kl_penalty_reduce_parts(const float* parts, int64_t rows, int64_t n_params, int64_t actor_begin, int actor_only,
                                      int combine, float pg_coef, float* grad, float* pg_grad, float* sums, float* losses_out,
                                      void* stream);
+/* Seed-batched form of the row-group step of FOCOPS and CUP: S independent runs of ONE shape (critic, actor, rows) in the
+ * stand-alone step's FIVE launches, run r on the grid slice blockIdx.y == r of each (the coefficient launch: one wave per run, grid
+ * (1, S)).  actor_loss / actor_only are launch-wide, as in spo_update_iter_ex_multi, and select the step's kind:
+ *   SPO_ACTOR_LOSS_KL_PENALTY, actor_only = 0 (FOCOPS):  spo_wide_kl_penalty_grad_rows, spo_wide_kl_penalty_reduce_parts(combine = 1),
+ *     spo_wide_clip_adam_dev_log(adam range [0, n_params), norm_begin 0, losses3_inout = log_src = losses3_out);
+ *   SPO_ACTOR_LOSS_KL_PENALTY, actor_only = 1 (CUP's second stage): the same two with actor_only = 1, then
+ *     spo_wide_clip_adam_dev_log(adam range [actor_begin, n_params), norm_begin = actor_begin, losses3_inout = NULL): the norm over the
+ *     actor's range, the actor's clock only; the critics' parameters, moments and clocks are not touched;
+ *   SPO_ACTOR_LOSS_CLIP, actor_only = 0 (CUP's first stage, the clipped surrogate on `adv`): spo_wide_ppo_grad_rows,
+ *     spo_wide_reduce_parts(3 losses), spo_wide_clip_adam_dev_log as for FOCOPS.
+ * Each run's blocks read the arguments its stand-alone launches would receive from a device table and run the same kernel bodies on
+ * the same blockIdx.x / gridDim.x, so per run the step is bit for bit its own stand-alone sequence.  No workgroup waits for
+ * another: no exchange, no placement census, no per-XCD budget, no timeout path -- the cap of SPO_WIDE_ROWS_MAX_REPLICAS runs bounds
+ * the table only.  A run with active == 0 is skipped: its blocks return before they touch memory; its pointers may be NULL.
+ * spo_wide_rows_ex_replica -- spo_wide_rows_replica's fields plus the old distribution and the loss options of the run.  parts:
+ *   float[spo_wide_kl_penalty_rows_part_floats(n_params, actor_begin, rows)] with the KL-penalty loss (the reduce's pg_grad / sums
+ *   are the buffer's tail behind the row groups), float[spo_wide_grad_rows_part_floats(n_params, rows)] with the clipped surrogate.
+ *   losses3_out is also the row the step logs (log_src); with actor_only only losses3_out[2] is written.  target_r / target_c may be
+ *   NULL with actor_only, old_mean / old_std with the clipped surrogate (kl_bound / pg_coef are then unused).
+ * spo_wide_rows_ex_multi_supported -- 1 where the kind exists (actor_only needs the KL-penalty loss), 1 <= n_replicas <=
+ *   SPO_WIDE_ROWS_MAX_REPLICAS and spo_wide_kl_penalty_grad_rows_supported (KL penalty) / spo_wide_grad_rows_supported (clipped
+ *   surrogate) holds with an actor.  Host only.
+ * spo_wide_rows_ex_multi_table_bytes -- bytes of the device table for n_replicas runs (-1 outside the cap).
+ * spo_wide_rows_ex_multi_upload -- validates reps_host[n_replicas] (a HOST array), fills every active run's kernel arguments through
+ *   the code the stand-alone entries use and copies the table to table_dev (stream-ordered; returns when the copy is done).  Refused
+ *   before any HIP call, in this order: a null table, n_replicas outside the cap, an unknown actor_loss, actor_only with the clipped
+ *   surrogate, an unsupported shape, a null pointer of an active run, two active runs sharing theta, parts or cursor_dev,
+ *   cursor_step <= 0, then per active run parameter ranges out of order, a partial workspace too small, betas outside [0, 1); then a
+ *   stream under capture.
+ * spo_wide_rows_ex_step_multi -- the five launches for all runs of an uploaded table (same n_replicas / shape / kind as the upload):
+ *   no allocation, no copy, no host read, so the call can be captured into a HIP graph and replayed. */
+typedef struct {
+  float *theta, *adam_m, *adam_v;          /* the run's own parameters and moments */
+  float *grad, *parts;                     /* float[n_params]; the row groups' parts (see above) */
+  const float *obs, *act, *logp_old, *target_r, *target_c, *adv;   /* the FULL arrays of the run's buffer */
+  const int64_t* perm;                     /* the run's shuffle (device) */
+  int64_t* cursor_dev;                     /* position in perm, advanced by cursor_step per step */
+  double* pow4_dev;                        /* double[6]: beta powers of both optimiser clocks, the two learning rates */
+  float *losses3_out, *scalars4_out;       /* the step's losses; {clip coefficient, L2 terms, gradient norm} */
+  double* partial_ws;
+  int partial_capacity;
+  float* loss_log_dev;                     /* [steps of a pass][3], or NULL */
+  spo_ppo_cfg cfg;
+  int active;
+  const float *old_mean, *old_std;         /* old_mean [M, act_dim] (read through perm), old_std [act_dim] */
+  float kl_bound, pg_coef;
+} spo_wide_rows_ex_replica;
+int spo_wide_rows_ex_multi_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int actor_loss, int actor_only,
+                                     int n_replicas);
+int64_t spo_wide_rows_ex_multi_table_bytes(int n_replicas);
+int spo_wide_rows_ex_multi_upload(void* table_dev, const spo_wide_rows_ex_replica* reps_host, int n_replicas, const spo_mlp_net* critic,
+                                  const spo_mlp_net* actor, int64_t rows, int64_t cursor_step, int actor_loss, int actor_only,
+                                  void* stream);
+int spo_wide_rows_ex_step_multi(const void* table_dev, int n_replicas, const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows,
+                                int actor_loss, int actor_only, void* stream);
 /* dsts[k][i, :] = srcs[k][idx[i], :] for k < count (<= SPO_GATHER_MAX) row-major arrays of widths[k] floats per row: the
  * minibatch gather of a step (the reference's DataLoader, ppo_lag.py:298-305) in one launch. */
 #define SPO_GATHER_MAX 8

@@ -25,6 +25,14 @@
 //     parts sums over rows, so the actor runs in two kinds of workgroup -- one cotangent each, see mlp_rows_grad_kernel -- and the
 //     group sum (spo_wide_kl_penalty_reduce_parts) combines them, or leaves them apart for a data-parallel all-reduce.  Measured
 //     (profiles/klpen_rows/): the launch 1.06 x the PPO launch's time, the FOCOPS step at [128, 128] 84 -> 36 us.
+//   * several independent runs of one shape share the step's launches (the seed-batched forms, `--seeds`): run r is the grid slice
+//     blockIdx.y == r, reads what its stand-alone launch receives as kernel arguments from its entry of a device table (uniform
+//     index: scalar loads) and runs the same body on the stand-alone blockIdx.x / gridDim.x -- bit for bit its own step; a run with
+//     active == 0 returns at once.  No workgroup waits for another, so nothing caps the runs but the table (32).  The fused
+//     PPO-Lagrangian step in three launches: spo_wide_rows_step_multi.  The FOCOPS / CUP step (KL penalty with or without the
+//     critics, and CUP's first stage with the clipped surrogate) in its five -- the gradient launch and the group sum here, the
+//     three optimiser launches of csrc/wide.hip through csrc/wide_opt.h: spo_wide_rows_ex_step_multi; its table is
+//     [S x MrMultiEntry | S x MrRedEntry | S x the optimiser's entry].
 // fp32 v_mfma_f32_16x16x4_f32 throughout (bitwise an fmaf chain); results differ from the launch-per-layer path in summation
 // order only.
 // Measured (hidden [128, 128], 60 / 8, 64 rows, one MI355X, profiles/r06/wide_step.txt, wide_rows_phase_cycles.txt): the kernel
@@ -42,6 +50,7 @@
 #include "adam_host.h"
 #include <cstdlib>
 #include <vector>
+#include "wide_opt.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -587,18 +596,23 @@ __global__ __launch_bounds__(512) void mlp_rows_grad_kernel(typename MrKernArg<M
 }
 
 // grad[i] = sum over the row groups of parts[g][i] (group order), losses3 = the three data losses of the minibatch
+// (the body as text, on the names parts / R / stride / P / rows / n_loss / grad / losses: the stand-alone kernel has them as its
+//  eight scalar parameters, the table-driven one below as locals read from its run's entry.  A shared device function, inlined,
+//  reordered two operands of the stand-alone kernel's instructions; this way its code is what it was.)
+#define MR_REDUCE_BODY                                                                                                  \
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256) {                     \
+    float s = parts[i];                                                                                                 \
+    for (int g = 1; g < R; ++g) s += parts[(int64_t)g * stride + i];                                                    \
+    grad[i] = s;                                                                                                        \
+  }                                                                                                                     \
+  if (blockIdx.x == 0 && threadIdx.x < n_loss && losses) {                                                              \
+    double s = 0.0;                                                                                                     \
+    for (int g = 0; g < R; ++g) s += (double)parts[(int64_t)g * stride + P + threadIdx.x];                              \
+    losses[threadIdx.x] = (float)((threadIdx.x == 2 ? -s : s) / (double)rows);                                          \
+  }
 __global__ __launch_bounds__(256) void mlp_rows_reduce_kernel(const float* __restrict__ parts, int R, int64_t stride, int64_t P, int64_t rows,
                                                               int n_loss, float* __restrict__ grad, float* __restrict__ losses) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256) {
-    float s = parts[i];
-    for (int g = 1; g < R; ++g) s += parts[(int64_t)g * stride + i];
-    grad[i] = s;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < n_loss && losses) {
-    double s = 0.0;
-    for (int g = 0; g < R; ++g) s += (double)parts[(int64_t)g * stride + P + threadIdx.x];
-    losses[threadIdx.x] = (float)((threadIdx.x == 2 ? -s : s) / (double)rows);
-  }
+  MR_REDUCE_BODY
 }
 
 // The group sum behind the KL-penalty launch (spo_wide_kl_penalty_reduce_parts).  A group's part: [0, P) the critics' gradients and
@@ -610,7 +624,23 @@ struct MrKlReduceArgs {
   int n_loss, combine; float pg_coef;
   float* grad; float* pg_grad; float* sums; float* losses;
 };
-__global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(MrKlReduceArgs a) {
+// MULTI (spo_wide_rows_ex_step_multi): run blockIdx.y's arguments from its entry of a device table (MrRedEntry, below)
+struct MrRedEntry;
+template <bool MULTI> struct MrRedArg {
+  typedef MrKlReduceArgs Kl;
+  static __device__ __forceinline__ const MrKlReduceArgs& kl(const MrKlReduceArgs& x) { return x; }
+};
+template <> struct MrRedArg<true> {
+  typedef const MrRedEntry* __restrict__ Kl;
+  static __device__ __forceinline__ const MrKlReduceArgs& kl(const MrRedEntry* __restrict__ t);
+  static __device__ __forceinline__ bool active(const MrRedEntry* __restrict__ t);
+};
+template <bool MULTI = false>
+__global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(typename MrRedArg<MULTI>::Kl arg) {
+  if constexpr (MULTI) {
+    if (!MrRedArg<true>::active(arg)) return;
+  }
+  const MrKlReduceArgs a = MrRedArg<MULTI>::kl(arg);     // (a copy: the stand-alone kernel's code is then what it was with `a` its parameter)
   double c = 0.0, k = 0.0, ra = 0.0;
   for (int g = 0; g < a.R; ++g) {
     const float* __restrict__ sp = a.parts + (int64_t)g * a.stride + a.P;
@@ -641,6 +671,32 @@ __global__ __launch_bounds__(256) void mlp_rows_klpen_reduce_kernel(MrKlReduceAr
     a.losses[q] = (float)(s / (double)a.rows);
   }
 }
+
+// The group sums of the seed-batched FOCOPS / CUP step (spo_wide_rows_ex_step_multi): run blockIdx.y's arguments of
+// spo_wide_kl_penalty_reduce_parts (kr) or of spo_wide_reduce_parts (r: CUP's first stage) from its entry of a device table, the
+// stand-alone body on the stand-alone blockIdx.x / gridDim.x.  (An entry type of its own: MrMultiEntry keeps its layout, and with it
+// the load offsets of the kernels that read it.)
+struct MrReduceArgs {
+  const float* parts; int R; int64_t stride, P, rows; int n_loss; float* grad; float* losses;
+};
+struct MrRedEntry {
+  MrKlReduceArgs kr;
+  MrReduceArgs r;
+  int active;
+};
+__device__ __forceinline__ const MrKlReduceArgs& MrRedArg<true>::kl(const MrRedEntry* __restrict__ t) { return t[blockIdx.y].kr; }
+__device__ __forceinline__ bool MrRedArg<true>::active(const MrRedEntry* __restrict__ t) { return t[blockIdx.y].active != 0; }
+__global__ __launch_bounds__(256) void mlp_rows_reduce_multi_kernel(const MrRedEntry* __restrict__ tab) {
+  if (!tab[blockIdx.y].active) return;
+  const MrReduceArgs a = tab[blockIdx.y].r;
+  const float* __restrict__ parts = a.parts;
+  float* __restrict__ grad = a.grad;
+  float* __restrict__ losses = a.losses;
+  const int R = a.R, n_loss = a.n_loss;
+  const int64_t stride = a.stride, P = a.P, rows = a.rows;
+  MR_REDUCE_BODY
+}
+#undef MR_REDUCE_BODY
 
 // ---- the optimiser behind the row groups in TWO launches (world size 1, device-resident clocks: the replayed step).
 // The launch-per-network step ended in wide_prep_kernel -> wide_coef_kernel -> wide_adam_kernel<true> (csrc/wide.hip): with the
@@ -813,6 +869,70 @@ int mr_grad_attr_once() {
   }
   return 0;
 }
+// ---- the same for the KL-penalty step's gradient launch and both group sums: the stand-alone entries
+// (spo_wide_kl_penalty_grad_rows, spo_wide_kl_penalty_reduce_parts, spo_wide_reduce_parts) and every run of a seed-batched table
+// (spo_wide_rows_ex_multi_upload) get their kernel arguments here.  No checks: the callers made them.
+void mr_fill_klgrad(const float* theta, const spo_mlp_net* critic, const spo_mlp_net* actor, const float* obs, const float* act,
+                    const float* logp_old, const float* target_r, const float* target_c, const float* adv, const float* old_mean,
+                    const float* old_std, const int64_t* idx, const int64_t* cursor_dev, int64_t rows, float kl_bound, float pg_coef,
+                    int actor_only, float* parts, MrArgs* out, size_t* lds_bytes, bool* vec_out) {
+  MrArgs& a = *out;
+  a = MrArgs{};
+  a.theta = theta; a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
+  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef;
+  a.idx = idx; a.cursor = cursor_dev; a.rows = (int)rows; a.R = (int)((rows + 15) / 16);
+  const int64_t Pc = spo_mlp_param_count(critic);
+  a.A = actor->dims[actor->n_layers];
+  a.ls_off = 2 * Pc;
+  a.P = 2 * Pc + a.A + spo_mlp_param_count(actor);
+  a.parts = parts; a.stride = mr_kl_stride(a.P, a.ls_off);
+  int k = 0;
+  if (!actor_only) {
+    mr_fill_net(critic, 0, 0, &a.net[k++]);
+    mr_fill_net(critic, Pc, 1, &a.net[k++]);
+  }
+  mr_fill_net(actor, 2 * Pc + a.A, 2, &a.net[k++]);
+  mr_fill_net(actor, 2 * Pc + a.A, 3, &a.net[k]);
+  a.net[k].poff = mr_kl_pgoff(a.P) - a.ls_off;         // g_PG[i - actor_begin] behind the group's gradient and row sums
+  a.n_nets = k + 1;
+  MrNet c0;
+  mr_fill_net(critic, 0, 0, &c0);
+  *lds_bytes = mr_kl_lds_floats(c0, a.net[k], a.A) * sizeof(float);
+  bool vec = true;
+  for (int i = 0; i < a.n_nets; ++i)
+    for (int l = 0; l < a.net[i].n; ++l) vec = vec && (a.net[i].d[l] & 3) == 0;
+  *vec_out = vec;
+}
+// the dynamic-LDS limit of the four KL-penalty gradient kernels (stand-alone and table-driven), raised once per device
+int mr_klgrad_attr_once() {
+  static bool done_dev[SPO_MAX_DEVICES] = {};
+  bool& done = done_dev[spo::current_device_slot()];
+  if (!done) {
+    for (const void* f : {reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true, MR_KLPEN>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false, MR_KLPEN>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true, MR_KLPEN, true>),
+                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false, MR_KLPEN, true>)})
+      if (int rc = spo::hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MR_MAX_LDS),
+                                  "hipFuncSetAttribute(mlp_rows, KL penalty)"))
+        return rc;
+    done = true;
+  }
+  return 0;
+}
+// (both return the launch's workgroups)
+int64_t mr_fill_klreduce(const float* parts, int64_t rows, int64_t n_params, int64_t actor_begin, int actor_only, int combine, float pg_coef,
+                         float* grad, float* pg_grad, float* sums, float* losses_out, MrKlReduceArgs* out) {
+  const int64_t lo = actor_only ? actor_begin : 0;
+  *out = MrKlReduceArgs{parts, (int)((rows + 15) / 16), mr_kl_stride(n_params, actor_begin), n_params, actor_begin, lo, mr_kl_pgoff(n_params),
+                        rows, actor_only ? 0 : 2, combine, pg_coef, grad, pg_grad, sums, losses_out};
+  const int64_t blocks = (n_params - lo + 255) / 256;
+  return blocks > 512 ? 512 : (blocks < 1 ? 1 : blocks);
+}
+int64_t mr_fill_reduce(const float* parts, int64_t rows, int64_t n_params, int n_losses, float* grad, float* losses_out, MrReduceArgs* out) {
+  *out = MrReduceArgs{parts, (int)((rows + 15) / 16), mr_stride(n_params), n_params, rows, n_losses, grad, losses_out};
+  const int64_t blocks = (n_params + 255) / 256;
+  return blocks > 512 ? 512 : blocks;
+}
 int64_t mr_opt_blocks(int64_t n_params) {
   const int64_t blocks = (n_params + 255) / 256;
   return blocks > 1024 ? 1024 : blocks;
@@ -895,11 +1015,10 @@ extern "C" int spo_wide_reduce_parts(const float* parts, int64_t rows, int64_t n
                                      void* stream) {
   SPO_REQUIRE(parts && grad && rows >= 1 && rows <= 16 * MR_MAX_GROUPS && n_params >= 1 && n_losses >= 0 && n_losses <= 3,
               "wide_reduce_parts: bad args");
-  const int R = (int)((rows + 15) / 16);
-  int64_t blocks = (n_params + 255) / 256;
-  blocks = blocks > 512 ? 512 : blocks;
-  hipLaunchKernelGGL(mlp_rows_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, parts, R, mr_stride(n_params),
-                     n_params, rows, n_losses, grad, losses_out);
+  MrReduceArgs a;
+  const int64_t blocks = mr_fill_reduce(parts, rows, n_params, n_losses, grad, losses_out, &a);
+  hipLaunchKernelGGL(mlp_rows_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.parts, a.R, a.stride, a.P, a.rows,
+                     a.n_loss, a.grad, a.losses);
   SPO_LAUNCH_CHECK("spo_wide_reduce_parts");
   return 0;
 }
@@ -1054,40 +1173,12 @@ extern "C" int spo_wide_kl_penalty_grad_rows(const float* theta, const spo_mlp_n
   SPO_REQUIRE(spo_wide_kl_penalty_grad_rows_supported(critic, actor, rows),
               "wide_kl_penalty_grad_rows: shape outside the row-group kernel (rows %lld)", (long long)rows);
   MrArgs a{};
-  a.theta = theta; a.obs = obs; a.act = act; a.logp_old = logp_old; a.tgt_r = target_r; a.tgt_c = target_c; a.adv = adv;
-  a.old_mean = old_mean; a.old_std = old_std; a.kl_bound = kl_bound; a.pg_coef = pg_coef;
-  a.idx = idx; a.cursor = cursor_dev; a.rows = (int)rows; a.R = (int)((rows + 15) / 16);
-  const int64_t Pc = spo_mlp_param_count(critic);
-  a.A = actor->dims[actor->n_layers];
-  a.ls_off = 2 * Pc;
-  a.P = 2 * Pc + a.A + spo_mlp_param_count(actor);
-  a.parts = parts; a.stride = mr_kl_stride(a.P, a.ls_off);
-  int k = 0;
-  if (!actor_only) {
-    mr_fill_net(critic, 0, 0, &a.net[k++]);
-    mr_fill_net(critic, Pc, 1, &a.net[k++]);
-  }
-  mr_fill_net(actor, 2 * Pc + a.A, 2, &a.net[k++]);
-  mr_fill_net(actor, 2 * Pc + a.A, 3, &a.net[k]);
-  a.net[k].poff = mr_kl_pgoff(a.P) - a.ls_off;         // g_PG[i - actor_begin] behind the group's gradient and row sums
-  a.n_nets = k + 1;
-  MrNet c0;
-  mr_fill_net(critic, 0, 0, &c0);
-  const size_t sh = mr_kl_lds_floats(c0, a.net[k], a.A) * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
+  size_t sh = 0;
   bool vec = true;
-  for (int i = 0; i < a.n_nets; ++i)
-    for (int l = 0; l < a.net[i].n; ++l) vec = vec && (a.net[i].d[l] & 3) == 0;
-  static bool done_dev[SPO_MAX_DEVICES] = {};
-  bool& done = done_dev[spo::current_device_slot()];
-  if (!done) {
-    for (const void* f : {reinterpret_cast<const void*>(&mlp_rows_grad_kernel<true, MR_KLPEN>),
-                          reinterpret_cast<const void*>(&mlp_rows_grad_kernel<false, MR_KLPEN>)})
-      if (int rc = spo::hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MR_MAX_LDS),
-                                  "hipFuncSetAttribute(mlp_rows, KL penalty)"))
-        return rc;
-    done = true;
-  }
+  mr_fill_klgrad(theta, critic, actor, obs, act, logp_old, target_r, target_c, adv, old_mean, old_std, idx, cursor_dev, rows, kl_bound,
+                 pg_coef, actor_only, parts, &a, &sh, &vec);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mr_klgrad_attr_once()) return rc;
   if (vec) hipLaunchKernelGGL((mlp_rows_grad_kernel<true, MR_KLPEN>), dim3(a.n_nets * a.R), dim3(512), sh, st, a);
   else hipLaunchKernelGGL((mlp_rows_grad_kernel<false, MR_KLPEN>), dim3(a.n_nets * a.R), dim3(512), sh, st, a);
   SPO_LAUNCH_CHECK("spo_wide_kl_penalty_grad_rows");
@@ -1101,12 +1192,163 @@ extern "C" int spo_wide_kl_penalty_reduce_parts(const float* parts, int64_t rows
   SPO_REQUIRE(rows >= 1 && rows <= 16 * MR_MAX_GROUPS && n_params >= 1 && actor_begin >= 0 && actor_begin <= n_params,
               "wide_kl_penalty_reduce_parts: bad args (rows %lld, n_params %lld, actor_begin %lld)", (long long)rows, (long long)n_params,
               (long long)actor_begin);
-  const int64_t lo = actor_only ? actor_begin : 0;
-  MrKlReduceArgs a{parts, (int)((rows + 15) / 16), mr_kl_stride(n_params, actor_begin), n_params, actor_begin, lo, mr_kl_pgoff(n_params),
-                   rows, actor_only ? 0 : 2, combine, pg_coef, grad, pg_grad, sums, losses_out};
-  int64_t blocks = (n_params - lo + 255) / 256;
-  blocks = blocks > 512 ? 512 : (blocks < 1 ? 1 : blocks);
-  hipLaunchKernelGGL(mlp_rows_klpen_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  MrKlReduceArgs a;
+  const int64_t blocks = mr_fill_klreduce(parts, rows, n_params, actor_begin, actor_only, combine, pg_coef, grad, pg_grad, sums, losses_out, &a);
+  hipLaunchKernelGGL(mlp_rows_klpen_reduce_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   SPO_LAUNCH_CHECK("spo_wide_kl_penalty_reduce_parts");
+  return 0;
+}
+
+// ---- the seed-batched FOCOPS / CUP step: S runs of one shape in the stand-alone step's five launches (include/safepo_hip.h).
+// The device table: [S x MrMultiEntry] (the gradient launch: g and active; o stays zero) | [S x MrRedEntry] (the group sum) |
+// [S x csrc/wide_opt.h's entry] (prep, coefficient, Adam), each block 16-byte aligned.
+namespace {
+struct MrExLayout { size_t off_red, off_opt, bytes; };
+MrExLayout mr_ex_layout(int S) {
+  const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  MrExLayout L;
+  L.off_red = up16((size_t)S * sizeof(MrMultiEntry));
+  L.off_opt = L.off_red + up16((size_t)S * sizeof(MrRedEntry));
+  L.bytes = L.off_opt + (size_t)S * spo::wide_opt_entry_bytes();
+  return L;
+}
+bool mr_ex_kind_ok(int actor_loss, int actor_only) {
+  return (actor_loss == SPO_ACTOR_LOSS_CLIP && !actor_only) || actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
+}
+}  // namespace
+
+extern "C" int spo_wide_rows_ex_multi_supported(const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int actor_loss,
+                                                int actor_only, int n_replicas) {
+  if (!actor || n_replicas < 1 || n_replicas > SPO_WIDE_ROWS_MAX_REPLICAS || !mr_ex_kind_ok(actor_loss, actor_only)) return 0;
+  return actor_loss == SPO_ACTOR_LOSS_KL_PENALTY ? spo_wide_kl_penalty_grad_rows_supported(critic, actor, rows)
+                                                 : spo_wide_grad_rows_supported(critic, actor, rows);
+}
+
+extern "C" int64_t spo_wide_rows_ex_multi_table_bytes(int n_replicas) {
+  if (n_replicas < 1 || n_replicas > SPO_WIDE_ROWS_MAX_REPLICAS) return -1;
+  return (int64_t)mr_ex_layout(n_replicas).bytes;
+}
+
+extern "C" int spo_wide_rows_ex_multi_upload(void* table_dev, const spo_wide_rows_ex_replica* reps_host, int n_replicas,
+                                             const spo_mlp_net* critic, const spo_mlp_net* actor, int64_t rows, int64_t cursor_step,
+                                             int actor_loss, int actor_only, void* stream) {
+  const bool klpen = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
+  SPO_REQUIRE(table_dev && reps_host, "wide_rows_ex_multi_upload: null table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_WIDE_ROWS_MAX_REPLICAS, "wide_rows_ex_multi_upload: n_replicas %d outside [1,%d]",
+              n_replicas, SPO_WIDE_ROWS_MAX_REPLICAS);
+  SPO_REQUIRE(actor_loss == SPO_ACTOR_LOSS_CLIP || klpen, "wide_rows_ex_multi_upload: actor_loss %d is neither SPO_ACTOR_LOSS_CLIP nor "
+              "SPO_ACTOR_LOSS_KL_PENALTY", actor_loss);
+  SPO_REQUIRE(mr_ex_kind_ok(actor_loss, actor_only), "wide_rows_ex_multi_upload: actor_only needs the KL-penalty loss (the clipped "
+              "surrogate's step takes the critics along)");
+  SPO_REQUIRE(spo_wide_rows_ex_multi_supported(critic, actor, rows, actor_loss, actor_only, n_replicas),
+              "wide_rows_ex_multi_upload: shape outside the row-group kernel's %s form (rows %lld)", klpen ? "KL-penalty" : "clipped-surrogate",
+              (long long)rows);
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_wide_rows_ex_replica& p = reps_host[r];
+    SPO_REQUIRE(!p.active || (p.theta && p.adam_m && p.adam_v && p.grad && p.parts && p.obs && p.act && p.logp_old && p.adv && p.perm &&
+                              p.cursor_dev && p.pow4_dev && p.losses3_out && p.scalars4_out && p.partial_ws),
+                "wide_rows_ex_multi_upload: replica %d: null pointer", r);
+    SPO_REQUIRE(!p.active || actor_only || (p.target_r && p.target_c), "wide_rows_ex_multi_upload: replica %d: critic targets are NULL", r);
+    SPO_REQUIRE(!p.active || !klpen || (p.old_mean && p.old_std), "wide_rows_ex_multi_upload: replica %d: the KL-penalty loss needs "
+                "old_mean / old_std", r);
+  }
+  for (int r = 0; r < n_replicas; ++r)
+    for (int q = 0; q < r; ++q) {
+      const spo_wide_rows_ex_replica &x = reps_host[q], &y = reps_host[r];
+      if (!x.active || !y.active) continue;
+      SPO_REQUIRE(x.theta != y.theta, "wide_rows_ex_multi_upload: replicas %d and %d share theta", q, r);
+      SPO_REQUIRE(x.parts != y.parts, "wide_rows_ex_multi_upload: replicas %d and %d share parts", q, r);
+      SPO_REQUIRE(x.cursor_dev != y.cursor_dev, "wide_rows_ex_multi_upload: replicas %d and %d share cursor_dev", q, r);
+    }
+  SPO_REQUIRE(cursor_step > 0, "wide_rows_ex_multi_upload: cursor_step must be > 0");
+  const int64_t Pc = spo_mlp_param_count(critic);
+  const int64_t off_ls = 2 * Pc, P = off_ls + actor->dims[actor->n_layers] + spo_mlp_param_count(actor);
+  const int64_t lo = actor_only ? off_ls : 0;                      // CUP's second stage: the actor's range in the norm and in Adam
+  const int R = (int)((rows + 15) / 16);
+  // (the entries of inactive runs stay zero: their blocks read `active` and nothing else)
+  const MrExLayout L = mr_ex_layout(n_replicas);
+  static thread_local std::vector<unsigned char> tab;
+  tab.assign(L.bytes, 0);
+  MrMultiEntry* const tg = reinterpret_cast<MrMultiEntry*>(tab.data());
+  MrRedEntry* const tr = reinterpret_cast<MrRedEntry*>(tab.data() + L.off_red);
+  for (int r = 0; r < n_replicas; ++r) {
+    const spo_wide_rows_ex_replica& p = reps_host[r];
+    if (!p.active) continue;
+    size_t sh;
+    bool vec;
+    if (klpen) {
+      mr_fill_klgrad(p.theta, critic, actor, p.obs, p.act, p.logp_old, p.target_r, p.target_c, p.adv, p.old_mean, p.old_std, p.perm,
+                     p.cursor_dev, rows, p.kl_bound, p.pg_coef, actor_only, p.parts, &tg[r].g, &sh, &vec);
+      // pg_grad / sums: the tail of `parts` behind the row groups (spo_wide_kl_penalty_rows_part_floats)
+      float* const pg = p.parts + (int64_t)R * mr_kl_stride(P, off_ls);
+      mr_fill_klreduce(p.parts, rows, P, off_ls, actor_only, 1, p.pg_coef, p.grad, pg, pg + ((P + 3) & ~(int64_t)3), p.losses3_out, &tr[r].kr);
+    } else {
+      mr_fill_grad(p.theta, critic, actor, p.obs, p.act, p.logp_old, p.target_r, p.target_c, p.adv, p.perm, p.cursor_dev, rows,
+                   p.cfg.clip, p.parts, &tg[r].g, &sh, &vec);
+      mr_fill_reduce(p.parts, rows, P, 3, p.grad, p.losses3_out, &tr[r].r);
+    }
+    if (int rc = spo::wide_opt_fill("wide_rows_ex_multi_upload", tab.data() + L.off_opt + (size_t)r * spo::wide_opt_entry_bytes(), p.theta,
+                                    p.grad, p.adam_m, p.adam_v, P, Pc, off_ls, off_ls, &p.cfg, p.pow4_dev, lo, P, lo, 0,
+                                    actor_only ? nullptr : p.losses3_out, p.scalars4_out, p.partial_ws, p.partial_capacity,
+                                    p.loss_log_dev, p.losses3_out, p.cursor_dev, cursor_step))
+      return rc;
+    tg[r].active = 1;
+    tr[r].active = 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    return spo::fail(-1, "wide_rows_ex_multi_upload: the stream is under capture (the argument table is copied from host memory: "
+                         "upload outside the capture, capture spo_wide_rows_ex_step_multi)");
+  // stream-ordered behind the replays that still read the previous table; the host table is reused by the next call: wait
+  if (int rc = spo::hip_check(hipMemcpyAsync(table_dev, tab.data(), L.bytes, hipMemcpyHostToDevice, st),
+                              "hipMemcpyAsync(wide_rows_ex_multi table)"))
+    return rc;
+  return spo::hip_check(hipStreamSynchronize(st), "hipStreamSynchronize(wide_rows_ex_multi table)");
+}
+
+extern "C" int spo_wide_rows_ex_step_multi(const void* table_dev, int n_replicas, const spo_mlp_net* critic, const spo_mlp_net* actor,
+                                           int64_t rows, int actor_loss, int actor_only, void* stream) {
+  const bool klpen = actor_loss == SPO_ACTOR_LOSS_KL_PENALTY;
+  SPO_REQUIRE(table_dev, "wide_rows_ex_step_multi: null table");
+  SPO_REQUIRE(n_replicas >= 1 && n_replicas <= SPO_WIDE_ROWS_MAX_REPLICAS, "wide_rows_ex_step_multi: n_replicas %d outside [1,%d]",
+              n_replicas, SPO_WIDE_ROWS_MAX_REPLICAS);
+  SPO_REQUIRE(spo_wide_rows_ex_multi_supported(critic, actor, rows, actor_loss, actor_only, n_replicas),
+              "wide_rows_ex_step_multi: shape or loss outside the row-group kernel (rows %lld, actor_loss %d, actor_only %d)", (long long)rows,
+              actor_loss, actor_only);
+  // the launch shape of a run: what the fillers give its stand-alone launches (pointers play no part in it)
+  MrArgs a;
+  MrKlReduceArgs kr;
+  MrReduceArgs rr;
+  size_t sh;
+  bool vec;
+  int64_t rblocks;
+  if (klpen) {
+    mr_fill_klgrad(nullptr, critic, actor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows,
+                   0.f, 0.f, actor_only, nullptr, &a, &sh, &vec);
+    rblocks = mr_fill_klreduce(nullptr, rows, a.P, a.ls_off, actor_only, 1, 0.f, nullptr, nullptr, nullptr, nullptr, &kr);
+  } else {
+    mr_fill_grad(nullptr, critic, actor, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rows, 0.f, nullptr, &a, &sh,
+                 &vec);
+    rblocks = mr_fill_reduce(nullptr, rows, a.P, 3, nullptr, nullptr, &rr);
+  }
+  const MrExLayout L = mr_ex_layout(n_replicas);
+  const unsigned char* base = static_cast<const unsigned char*>(table_dev);
+  const MrMultiEntry* tg = reinterpret_cast<const MrMultiEntry*>(base);
+  const MrRedEntry* tr = reinterpret_cast<const MrRedEntry*>(base + L.off_red);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = klpen ? mr_klgrad_attr_once() : mr_grad_attr_once()) return rc;
+  const dim3 ggrid((unsigned)(a.n_nets * a.R), (unsigned)n_replicas), rgrid((unsigned)rblocks, (unsigned)n_replicas);
+  if (klpen) {
+    if (vec) hipLaunchKernelGGL((mlp_rows_grad_kernel<true, MR_KLPEN, true>), ggrid, dim3(512), sh, st, tg);
+    else hipLaunchKernelGGL((mlp_rows_grad_kernel<false, MR_KLPEN, true>), ggrid, dim3(512), sh, st, tg);
+    hipLaunchKernelGGL(mlp_rows_klpen_reduce_kernel<true>, rgrid, dim3(256), 0, st, tr);
+  } else {
+    if (vec) hipLaunchKernelGGL((mlp_rows_grad_kernel<true, MR_PPO, true>), ggrid, dim3(512), sh, st, tg);
+    else hipLaunchKernelGGL((mlp_rows_grad_kernel<false, MR_PPO, true>), ggrid, dim3(512), sh, st, tg);
+    hipLaunchKernelGGL(mlp_rows_reduce_multi_kernel, rgrid, dim3(256), 0, st, tr);
+  }
+  spo::wide_opt_launch_multi(base + L.off_opt, n_replicas, a.P, actor_only ? a.ls_off : 0, st);
+  SPO_LAUNCH_CHECK("spo_wide_rows_ex_step_multi");
   return 0;
 }

@@ -32,6 +32,7 @@
 #include "mlp_mfma.h"
 #include "mlp_small.h"
 #include "gemm_f32.h"
+#include "wide_opt.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -654,7 +655,9 @@ struct WideAdamArgs {
   double* partial; float* scal;      // scal: {coef, l2 * sum p^2 (reward critic), l2 * sum p^2 (cost critic), ||g||}
   float* losses3;
 };
-__global__ __launch_bounds__(256) void wide_prep_kernel(WideAdamArgs a) {
+// (the bodies of the optimiser's kernels are shared by the stand-alone kernels -- `a` their kernel argument -- and the table-driven
+//  ones below -- `a` a run's entry of a device table)
+__device__ __forceinline__ void wide_prep_body(const WideAdamArgs a) {
   __shared__ double red[4][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double gs = 0.0, pr = 0.0, pc = 0.0;
@@ -673,13 +676,13 @@ __global__ __launch_bounds__(256) void wide_prep_kernel(WideAdamArgs a) {
   __syncthreads();
   if (tid < 3) a.partial[(int64_t)blockIdx.x * 3 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
+__global__ __launch_bounds__(256) void wide_prep_kernel(WideAdamArgs a) { wide_prep_body(a); }
 // pow4 (optional): the device-resident optimiser clocks {beta1^t, beta2^t of the critics, of the actor}; the clocks named by
 // adv_critics / adv_actor advance here, between the norm and the Adam pass (spo_wide_clip_adam_dev)
 // loss_log / log_src / cursor (optional, device): the step's three losses log_src[0..2] are stored at loss_log[3 * (*cursor / cursor_step)] and
 // *cursor advances by cursor_step -- the window spo_gather_rows_at reads; a replayed step then needs no host copy in or out
-__global__ __launch_bounds__(64) void wide_coef_kernel(WideAdamArgs a, int nblocks, double* pow4 = nullptr, int adv_critics = 0,
-                                                       int adv_actor = 0, float* loss_log = nullptr, const float* log_src = nullptr,
-                                                       int64_t* cursor = nullptr, int64_t cursor_step = 0) {
+__device__ __forceinline__ void wide_coef_body(const WideAdamArgs a, int nblocks, double* pow4, int adv_critics, int adv_actor,
+                                               float* loss_log, const float* log_src, int64_t* cursor, int64_t cursor_step) {
   // one wave: lane l adds the partials l, l + 64, ... in order, then a fixed butterfly over the lanes
   double gs = 0.0, pr = 0.0, pc = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += 64) { gs += a.partial[b * 3]; pr += a.partial[b * 3 + 1]; pc += a.partial[b * 3 + 2]; }
@@ -703,8 +706,13 @@ __global__ __launch_bounds__(64) void wide_coef_kernel(WideAdamArgs a, int nbloc
     cursor[0] = at + cursor_step;
   }
 }
+__global__ __launch_bounds__(64) void wide_coef_kernel(WideAdamArgs a, int nblocks, double* pow4 = nullptr, int adv_critics = 0,
+                                                       int adv_actor = 0, float* loss_log = nullptr, const float* log_src = nullptr,
+                                                       int64_t* cursor = nullptr, int64_t cursor_step = 0) {
+  wide_coef_body(a, nblocks, pow4, adv_critics, adv_actor, loss_log, log_src, cursor, cursor_step);
+}
 // prep over a sub-range for the joint norm: CUP's second stage clips over the ACTOR's parameters only (cup.py:385)
-__global__ __launch_bounds__(256) void wide_prep_range_kernel(WideAdamArgs a, int64_t n0, int64_t n1) {
+__device__ __forceinline__ void wide_prep_range_body(const WideAdamArgs a, int64_t n0, int64_t n1) {
   __shared__ double red[4][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double gs = 0.0;
@@ -717,6 +725,7 @@ __global__ __launch_bounds__(256) void wide_prep_range_kernel(WideAdamArgs a, in
   __syncthreads();
   if (tid < 3) a.partial[(int64_t)blockIdx.x * 3 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
+__global__ __launch_bounds__(256) void wide_prep_range_kernel(WideAdamArgs a, int64_t n0, int64_t n1) { wide_prep_range_body(a, n0, n1); }
 // clip + Adam with a sub-range: the joint norm spans [norm_begin, P) (wide_prep_kernel, or wide_prep_range_kernel when
 // norm_begin != 0); Adam touches [adam_begin, adam_end) only, with the critics' clock below actor_begin and the actor's above;
 // outside that range the (stale) gradient is multiplied by the clip coefficient in place when scale_rest != 0.
@@ -726,8 +735,25 @@ struct WideAdamExArgs {
 // DEV_CLOCKS = false: the clocks beta^t BEFORE this step come from the host (b.pow_b1 / b.pow_b2: the critics', pow_b1_a /
 // pow_b2_a: the actor's) and advance here; pow4 is not read.
 // DEV_CLOCKS = true: pow4 holds the device-resident clocks, already advanced by wide_coef_kernel, and the learning rates.
-template <bool DEV_CLOCKS>
-__global__ __launch_bounds__(256) void wide_adam_kernel(WideAdamExArgs x, const double* __restrict__ pow4) {
+// MULTI (the table-driven form below): `arg` is a device table of WideOptEntry, run blockIdx.y's x and pow4 are read from its entry.
+struct WideOptEntry;
+template <bool MULTI> struct WideKernArg {
+  typedef WideAdamExArgs AdamEx;
+  static __device__ __forceinline__ const WideAdamExArgs& ex(const WideAdamExArgs& x) { return x; }
+};
+template <> struct WideKernArg<true> {
+  typedef const WideOptEntry* __restrict__ AdamEx;
+  static __device__ __forceinline__ const WideAdamExArgs& ex(const WideOptEntry* __restrict__ t);
+  static __device__ __forceinline__ bool active(const WideOptEntry* __restrict__ t);
+  static __device__ __forceinline__ const double* pow4(const WideOptEntry* __restrict__ t);
+};
+template <bool DEV_CLOCKS, bool MULTI = false>
+__global__ __launch_bounds__(256) void wide_adam_kernel(typename WideKernArg<MULTI>::AdamEx arg, const double* __restrict__ pow4) {
+  if constexpr (MULTI) {
+    if (!WideKernArg<true>::active(arg)) return;
+    pow4 = WideKernArg<true>::pow4(arg);
+  }
+  const WideAdamExArgs x = WideKernArg<MULTI>::ex(arg);   // (a copy: the stand-alone kernel's code is then what it was with `x` its parameter)
   const WideAdamArgs& a = x.b;
   const float coef = a.scal[0];
   float ss_a, ss_c, bc2s_a, bc2s_c;
@@ -753,6 +779,79 @@ __global__ __launch_bounds__(256) void wide_adam_kernel(WideAdamExArgs x, const 
   }
 }
 
+// ---- the table-driven (seed-batched) form of the three launches with device-resident clocks (csrc/wide_opt.h): run blockIdx.y of
+// S independent runs reads what its stand-alone launches receive as kernel arguments from its entry of a device table (uniform
+// index, const __restrict__: scalar loads) and runs the same body on the stand-alone blockIdx.x / gridDim.x.  No block waits for
+// another; a block of a run with active == 0 returns after reading `active` and nothing else.
+struct WideOptEntry {
+  WideAdamExArgs x;
+  int64_t norm_begin;                // the joint norm spans [norm_begin, x.b.P): wide_prep_kernel's pass at 0, else wide_prep_range_kernel's
+  double* pow4;
+  float* loss_log; const float* log_src; int64_t* cursor; int64_t cursor_step;
+  int nblocks, adv_critics, adv_actor;
+  int active;
+};
+static_assert(sizeof(WideOptEntry) % 8 == 0, "WideOptEntry: entries are laid out back to back behind another table");
+__global__ __launch_bounds__(256) void wide_prep_multi_kernel(const WideOptEntry* __restrict__ tab) {
+  if (!tab[blockIdx.y].active) return;
+  wide_prep_body(tab[blockIdx.y].x.b);
+}
+__global__ __launch_bounds__(256) void wide_prep_range_multi_kernel(const WideOptEntry* __restrict__ tab) {
+  if (!tab[blockIdx.y].active) return;
+  const WideOptEntry& e = tab[blockIdx.y];
+  wide_prep_range_body(e.x.b, e.norm_begin, e.x.b.P);
+}
+__global__ __launch_bounds__(64) void wide_coef_multi_kernel(const WideOptEntry* __restrict__ tab) {
+  if (!tab[blockIdx.y].active) return;
+  const WideOptEntry& e = tab[blockIdx.y];
+  wide_coef_body(e.x.b, e.nblocks, e.pow4, e.adv_critics, e.adv_actor, e.loss_log, e.log_src, e.cursor, e.cursor_step);
+}
+__device__ __forceinline__ const WideAdamExArgs& WideKernArg<true>::ex(const WideOptEntry* __restrict__ t) { return t[blockIdx.y].x; }
+__device__ __forceinline__ bool WideKernArg<true>::active(const WideOptEntry* __restrict__ t) { return t[blockIdx.y].active != 0; }
+__device__ __forceinline__ const double* WideKernArg<true>::pow4(const WideOptEntry* __restrict__ t) { return t[blockIdx.y].pow4; }
+
+int64_t wide_opt_blocks(int64_t n_params) {
+  const int64_t blocks = (n_params + 255) / 256;
+  return blocks > 1024 ? 1024 : blocks;
+}
+// The checks and the kernel arguments of a clip + Adam step, in ONE place for the four spo_wide_clip_adam* entry points
+// (wide_clip_adam) and for every run of a seed-batched table (spo::wide_opt_fill).  `who` names the caller in the messages.
+// No HIP call.
+int wide_fill_opt(const char* who, float* theta, float* grad, float* adam_m, float* adam_v, int64_t n_params, int64_t reward_critic_end,
+                  int64_t cost_critic_end, int64_t actor_begin, const spo_ppo_cfg* cfg, bool dev_clocks, int64_t step_critics,
+                  int64_t step_actor, double* pow4_dev, int64_t adam_begin, int64_t adam_end, int64_t norm_begin, int scale_rest,
+                  float* losses3_inout, float* scalars4_out, double* partial_ws, int partial_capacity, float* loss_log_dev,
+                  const float* log_src_dev, int64_t* cursor_dev, int64_t cursor_step, WideOptEntry* out) {
+  SPO_REQUIRE(theta && grad && adam_m && adam_v && cfg && scalars4_out && partial_ws && n_params > 0 &&
+                  (dev_clocks ? pow4_dev != nullptr : (step_critics >= 0 && step_actor >= 0)), "%s: bad args", who);
+  SPO_REQUIRE(0 <= reward_critic_end && reward_critic_end <= cost_critic_end && cost_critic_end <= actor_begin && actor_begin <= n_params,
+              "%s: parameter ranges out of order", who);
+  SPO_REQUIRE(0 <= adam_begin && adam_begin <= adam_end && adam_end <= n_params && 0 <= norm_begin && norm_begin <= n_params,
+              "%s: optimiser range out of order", who);
+  const int64_t blocks = wide_opt_blocks(n_params);
+  SPO_REQUIRE((int64_t)partial_capacity >= blocks * 3, "%s: partial workspace too small", who);
+  double b1 = 0.0, b2 = 0.0;          // the betas the caller meant (csrc/adam_host.h): clocks and weights both come from them
+  float w1, w2;
+  SPO_REQUIRE(adam_beta_host(cfg->beta1, &b1, &w1) && adam_beta_host(cfg->beta2, &b2, &w2), "%s: betas (%g, %g) outside [0, 1)", who,
+              (double)cfg->beta1, (double)cfg->beta2);
+  const WideAdamArgs a{theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin,
+                       cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
+                       cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, w1, w2, b1, b2, dev_clocks ? 1.0 : pow(b1, (double)step_critics),
+                       dev_clocks ? 1.0 : pow(b2, (double)step_critics), partial_ws, scalars4_out, losses3_inout};
+  *out = WideOptEntry{};
+  out->x = WideAdamExArgs{a, adam_begin, adam_end, scale_rest, dev_clocks ? 1.0 : pow(b1, (double)step_actor),
+                          dev_clocks ? 1.0 : pow(b2, (double)step_actor)};
+  out->norm_begin = norm_begin;
+  out->pow4 = dev_clocks ? pow4_dev : (double*)nullptr;
+  out->loss_log = loss_log_dev; out->log_src = log_src_dev; out->cursor = cursor_dev; out->cursor_step = cursor_step;
+  out->nblocks = (int)blocks;
+  // the clocks of the optimisers inside [adam_begin, adam_end) advance on the device
+  out->adv_critics = dev_clocks && adam_begin < actor_begin ? 1 : 0;
+  out->adv_actor = dev_clocks && adam_end > actor_begin ? 1 : 0;
+  out->active = 1;
+  return 0;
+}
+
 // The one host sequence behind the four spo_wide_clip_adam* entry points: checks, prep -> coefficient -> Adam.  `entry` names the
 // caller in the messages (without its spo_ prefix).  pow4_dev == nullptr: host clocks step_critics / step_actor; else the
 // device-resident clocks, and loss_log_dev / log_src_dev / cursor_dev / cursor_step as wide_coef_kernel takes them.
@@ -761,40 +860,45 @@ int wide_clip_adam(const char* entry, float* theta, float* grad, float* adam_m, 
                    int64_t step_critics, int64_t step_actor, double* pow4_dev, int64_t adam_begin, int64_t adam_end, int64_t norm_begin,
                    int scale_rest, float* losses3_inout, float* scalars4_out, double* partial_ws, int partial_capacity,
                    float* loss_log_dev, const float* log_src_dev, int64_t* cursor_dev, int64_t cursor_step, void* stream) {
-  const char* who = entry + 4;
-  SPO_REQUIRE(theta && grad && adam_m && adam_v && cfg && scalars4_out && partial_ws && n_params > 0 &&
-                  (dev_clocks ? pow4_dev != nullptr : (step_critics >= 0 && step_actor >= 0)), "%s: bad args", who);
-  SPO_REQUIRE(0 <= reward_critic_end && reward_critic_end <= cost_critic_end && cost_critic_end <= actor_begin && actor_begin <= n_params,
-              "%s: parameter ranges out of order", who);
-  SPO_REQUIRE(0 <= adam_begin && adam_begin <= adam_end && adam_end <= n_params && 0 <= norm_begin && norm_begin <= n_params,
-              "%s: optimiser range out of order", who);
-  int64_t blocks = (n_params + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  SPO_REQUIRE((int64_t)partial_capacity >= blocks * 3, "%s: partial workspace too small", who);
-  double b1 = 0.0, b2 = 0.0;          // the betas the caller meant (csrc/adam_host.h): clocks and weights both come from them
-  float w1, w2;
-  SPO_REQUIRE(adam_beta_host(cfg->beta1, &b1, &w1) && adam_beta_host(cfg->beta2, &b2, &w2), "%s: betas (%g, %g) outside [0, 1)", who,
-              (double)cfg->beta1, (double)cfg->beta2);
-  WideAdamArgs a{theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin,
-                 cfg->use_critic_norm ? cfg->l2_coef : 0.f, cfg->use_value_coefficient ? 2.f : 1.f, cfg->max_grad_norm, cfg->lr_actor,
-                 cfg->lr_critic, cfg->beta1, cfg->beta2, cfg->adam_eps, w1, w2, b1, b2, dev_clocks ? 1.0 : pow(b1, (double)step_critics),
-                 dev_clocks ? 1.0 : pow(b2, (double)step_critics), partial_ws, scalars4_out, losses3_inout};
-  WideAdamExArgs x{a, adam_begin, adam_end, scale_rest, dev_clocks ? 1.0 : pow(b1, (double)step_actor),
-                   dev_clocks ? 1.0 : pow(b2, (double)step_actor)};
+  WideOptEntry e;
+  if (int rc = wide_fill_opt(entry + 4, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, cfg,
+                             dev_clocks, step_critics, step_actor, pow4_dev, adam_begin, adam_end, norm_begin, scale_rest, losses3_inout,
+                             scalars4_out, partial_ws, partial_capacity, loss_log_dev, log_src_dev, cursor_dev, cursor_step, &e))
+    return rc;
+  const WideAdamArgs& a = e.x.b;
+  const unsigned blocks = (unsigned)e.nblocks;
   hipStream_t st = (hipStream_t)stream;
-  if (norm_begin == 0) hipLaunchKernelGGL(wide_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(wide_prep_range_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, norm_begin, n_params);
-  // the clocks of the optimisers inside [adam_begin, adam_end) advance on the device
-  hipLaunchKernelGGL(wide_coef_kernel, dim3(1), dim3(64), 0, st, a, (int)blocks, dev_clocks ? pow4_dev : (double*)nullptr,
-                     dev_clocks && adam_begin < actor_begin ? 1 : 0, dev_clocks && adam_end > actor_begin ? 1 : 0, loss_log_dev,
-                     log_src_dev, cursor_dev, cursor_step);
-  if (dev_clocks) hipLaunchKernelGGL(wide_adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, x, (const double*)pow4_dev);
-  else hipLaunchKernelGGL(wide_adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, x, (const double*)nullptr);
+  if (norm_begin == 0) hipLaunchKernelGGL(wide_prep_kernel, dim3(blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(wide_prep_range_kernel, dim3(blocks), dim3(256), 0, st, a, norm_begin, n_params);
+  hipLaunchKernelGGL(wide_coef_kernel, dim3(1), dim3(64), 0, st, a, e.nblocks, e.pow4, e.adv_critics, e.adv_actor, loss_log_dev, log_src_dev,
+                     cursor_dev, cursor_step);
+  if (dev_clocks) hipLaunchKernelGGL(wide_adam_kernel<true>, dim3(blocks), dim3(256), 0, st, e.x, (const double*)pow4_dev);
+  else hipLaunchKernelGGL(wide_adam_kernel<false>, dim3(blocks), dim3(256), 0, st, e.x, (const double*)nullptr);
   SPO_LAUNCH_CHECK(entry);
   return 0;
 }
 
 }  // namespace
+
+// ---- csrc/wide_opt.h: the table-driven optimiser launches for callers in other files
+size_t spo::wide_opt_entry_bytes() { return sizeof(WideOptEntry); }
+int spo::wide_opt_fill(const char* entry, void* entry_out, float* theta, float* grad, float* adam_m, float* adam_v, int64_t n_params,
+                       int64_t reward_critic_end, int64_t cost_critic_end, int64_t actor_begin, const spo_ppo_cfg* cfg, double* pow4_dev,
+                       int64_t adam_begin, int64_t adam_end, int64_t norm_begin, int scale_rest, float* losses3_inout,
+                       float* scalars4_out, double* partial_ws, int partial_capacity, float* loss_log_dev, const float* log_src_dev,
+                       int64_t* cursor_dev, int64_t cursor_step) {
+  return wide_fill_opt(entry, theta, grad, adam_m, adam_v, n_params, reward_critic_end, cost_critic_end, actor_begin, cfg, true, 0, 0,
+                       pow4_dev, adam_begin, adam_end, norm_begin, scale_rest, losses3_inout, scalars4_out, partial_ws, partial_capacity,
+                       loss_log_dev, log_src_dev, cursor_dev, cursor_step, static_cast<WideOptEntry*>(entry_out));
+}
+void spo::wide_opt_launch_multi(const void* entries_dev, int n_replicas, int64_t n_params, int64_t norm_begin, hipStream_t st) {
+  const WideOptEntry* tab = static_cast<const WideOptEntry*>(entries_dev);
+  const dim3 grid((unsigned)wide_opt_blocks(n_params), (unsigned)n_replicas);
+  if (norm_begin == 0) hipLaunchKernelGGL(wide_prep_multi_kernel, grid, dim3(256), 0, st, tab);
+  else hipLaunchKernelGGL(wide_prep_range_multi_kernel, grid, dim3(256), 0, st, tab);
+  hipLaunchKernelGGL(wide_coef_multi_kernel, dim3(1, (unsigned)n_replicas), dim3(64), 0, st, tab);
+  hipLaunchKernelGGL((wide_adam_kernel<true, true>), grid, dim3(256), 0, st, tab, (const double*)nullptr);
+}
 
 // ==================================================================================================================== C ABI
 extern "C" int64_t spo_mlp_param_count(const spo_mlp_net* net) {

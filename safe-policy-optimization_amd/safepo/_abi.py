@@ -57,6 +57,12 @@ class WideRowsReplica(Structure):
                 ("cfg", PpoCfg), ("active", c_int)]
 
 
+class WideRowsExReplica(Structure):
+    """spo_wide_rows_ex_replica (include/safepo_hip.h): one run of a seed-batched row-group FOCOPS / CUP step
+    (spo_wide_rows_ex_step_multi)."""
+    _fields_ = WideRowsReplica._fields_ + [("old_mean", c_void_p), ("old_std", c_void_p), ("kl_bound", c_float), ("pg_coef", c_float)]
+
+
 class UpdateExReplica(Structure):
     """spo_update_ex_replica (include/safepo_hip.h): one run of a seed-batched spo_update_iter_ex launch (FOCOPS, CUP)."""
     _fields_ = [("theta", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p), ("adam_step_critics", c_int64),
@@ -145,6 +151,11 @@ PROTOTYPES = {
     "spo_wide_rows_multi_table_bytes": (c_int64, [c_int]),
     "spo_wide_rows_multi_upload": (c_int, [P, POINTER(WideRowsReplica), c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int64, P]),
     "spo_wide_rows_step_multi": (c_int, [P, c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, P]),
+    "spo_wide_rows_ex_multi_supported": (c_int, [POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int, c_int, c_int]),
+    "spo_wide_rows_ex_multi_table_bytes": (c_int64, [c_int]),
+    "spo_wide_rows_ex_multi_upload": (c_int, [P, POINTER(WideRowsExReplica), c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int64,
+                                              c_int, c_int, P]),
+    "spo_wide_rows_ex_step_multi": (c_int, [P, c_int, POINTER(MlpNet), POINTER(MlpNet), c_int64, c_int, c_int, P]),
     "spo_wide_kl_penalty_grad_rows_supported": (c_int, [POINTER(MlpNet), POINTER(MlpNet), c_int64]),
     "spo_wide_kl_penalty_rows_part_floats": (c_int64, [c_int64, c_int64, c_int64]),
     "spo_wide_kl_penalty_grad_rows": (c_int, [P, POINTER(MlpNet), POINTER(MlpNet)] + [P] * 10 + [c_int64, c_float, c_float, c_int, P, P]),

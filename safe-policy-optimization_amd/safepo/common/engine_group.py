@@ -164,9 +164,12 @@ class PPOLagEngineGroup(_EngineGroup):
     [64, 64], act_dim > 32 or obs_dim > 512 --, whose PPO-Lagrangian step is the row-group gradient kernel with the fused
     optimiser (csrc/mlp_rows.hip).  Where _rows_batched holds, the whole minibatches of a learning iteration are replayed from
     one captured graph of spo_wide_rows_step_multi (run r = blockIdx.y of the step's three launches), each run bit for bit its
-    own graph-replayed pass; update() only (FOCOPS / CUP step such a group engine by engine)."""
+    own graph-replayed pass; update() only (FOCOPS / CUP step such a group engine by engine).
+    `klpen_rows=True` (opt-in): such a row-group group also shares the steps of learning_iter_ex_all -- FOCOPS' step and both of
+    CUP's stages -- where _rows_batched_ex holds: one captured graph of spo_wide_rows_ex_step_multi (run r = blockIdx.y of the
+    step's five launches) per (batch, kind), each run bit for bit its own graph-replayed learning_iter_ex pass."""
 
-    def __init__(self, engines, rngs=None):
+    def __init__(self, engines, rngs=None, klpen_rows=False):
         from safepo.common.engine import PPOLagEngine, WidePPOLagEngine
         engines = list(engines)
         if not engines:
@@ -177,6 +180,7 @@ class PPOLagEngineGroup(_EngineGroup):
         self._rows = wide and not any(e._feature_split_kernel_ok(e._cfg_struct()) for e in engines)
         self._ks = wide and not self._rows
         self._rows_graphs = {}
+        self._klpen_rows = bool(klpen_rows)
 
         def check_type(i, e):
             if self._rows:
@@ -323,6 +327,133 @@ class PPOLagEngineGroup(_EngineGroup):
                 es[i].minibatch_step(perms64[i][k * batch:(k + 1) * batch], losses[i][k], cfg=cfgs[i])
         return losses
 
+    def _rows_batched_ex(self, cfgs, actor_loss, actor_only) -> bool:
+        """A klpen_rows group on the row-group kernel: one spo_wide_rows_ex_step_multi per minibatch step of learning_iter_ex_all
+        where every engine's own pass would be the graph-replayed row-group step -- world size 1, _row_group_step_ok(batch,
+        actor_loss, actor_only), 0 < batch <= graph_max_batch with more than two minibatches, not on the feature-split kernel
+        (all read at every call, as the engine reads them) -- and the library takes this many runs of the shape and kind."""
+        if not self._klpen_rows:
+            return False
+        es, c0 = self.engines, cfgs[0]
+        n_mb = (es[0].M + c0.batch - 1) // max(c0.batch, 1)
+        return (n_mb > 2
+                and all(e.comm.world_size == 1 and 0 < c.batch <= e.graph_max_batch
+                        and e._row_group_step_ok(c.batch, actor_loss, actor_only)
+                        and not e._feature_split_kernel_ok(c) for e, c in zip(es, cfgs))
+                and bool(self.lib.spo_wide_rows_ex_multi_supported(es[0].wide.net_c, es[0].wide.net_a, c0.batch, int(actor_loss),
+                                                                   int(bool(actor_only)), len(es))))
+
+    def _rows_learning_iter_ex_all(self, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active):
+        """WidePPOLagEngine.learning_iter_ex's graph-replayed pass for the active runs, as _rows_learning_iter_all does it for the
+        PPO-Lagrangian step: every run's device clocks from its own host step counts (_sync_pow4) and its own PermWindow loaded
+        with its own shuffle, the argument table -- kl_bound, pg_coef and the advantage among its entries, so one capture per
+        (batch, kind) serves every epoch -- uploaded once per pass outside any capture, the whole minibatches replayed from ONE
+        captured graph of spo_wide_rows_ex_step_multi (eight steps per graph launch: SPO_WIDE_GRAPH_UNROLL, as the engine), the
+        ragged last minibatch through each engine's own eager minibatch_step_ex, the host clocks advanced as learning_iter_ex
+        advances them."""
+        from safepo.common.wide import PermWindow
+        es, S, e0, lib = self.engines, len(self.engines), self.engines[0], self.lib
+        batch, M = int(cfgs[0].batch), e0.M
+        n_mb, n_full = (M + batch - 1) // batch, M // batch
+        nc, na = e0.wide.net_c, e0.wide.net_a
+        klpen, actor_only = actor_loss == _abi.ACTOR_LOSS_KL_PENALTY, bool(actor_only)
+        key = ("ex", batch, int(actor_loss), actor_only)
+        ent = self._rows_graphs.get(key)
+        if ent is None:
+            # (the part buffers are the engines' own for this step: what their stand-alone launches fill)
+            def parts_of(e):
+                if klpen:
+                    return e.wide._scratch.setdefault(("klpen_parts", batch, actor_only), torch.zeros(
+                        int(lib.spo_wide_kl_penalty_rows_part_floats(e.wide.P, e.wide.off_ls, batch)), dtype=torch.float32, device=e.dev))
+                return e.wide._scratch.setdefault(("parts", batch, False), torch.zeros(
+                    int(lib.spo_wide_grad_rows_part_floats(e.wide.P, batch)), dtype=torch.float32, device=e.dev))
+            ent = self._rows_graphs[key] = {
+                "wins": [PermWindow(M, batch, e.dev) for e in es],
+                "loss3": [torch.full((3,), float("nan"), dtype=torch.float32, device=e.dev) for e in es],
+                "parts": [parts_of(e) for e in es],
+                "table": torch.zeros(int(lib.spo_wide_rows_ex_multi_table_bytes(S)), dtype=torch.uint8, device=e0.dev),
+                "graphs": None}
+        wins = ent["wins"]
+        perms64, losses, keep = [None] * S, [None] * S, []
+        reps = (_abi.WideRowsExReplica * S)()
+        for i, e in enumerate(es):
+            r = reps[i]
+            r.cfg, r.active = cfgs[i], int(active[i] and perms[i] is not None)
+            if not r.active:
+                continue
+            perms64[i] = _abi.require_gpu_tensor(perms[i], "perm", torch.int32).long()
+            adv = _abi.require_gpu_tensor(advs[i], "adv", torch.float32)
+            keep.append(adv)
+            losses[i] = torch.full((n_mb, 3), float("nan"), dtype=torch.float32, device=e.dev)
+            e._sync_pow4()
+            wins[i].load(perms64[i])
+            d = e.buffer.data
+            r.theta, r.adam_m, r.adam_v = _abi.ptr(e.policy.theta), _abi.ptr(e.adam_m), _abi.ptr(e.adam_v)
+            r.grad, r.parts = _abi.ptr(e.flat_grad), _abi.ptr(ent["parts"][i])
+            r.obs, r.act, r.logp_old = _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"])
+            r.target_r, r.target_c, r.adv = _abi.ptr(d["target_value_r"]), _abi.ptr(d["target_value_c"]), _abi.ptr(adv)
+            r.perm, r.cursor_dev, r.pow4_dev = _abi.ptr(wins[i].perm), _abi.ptr(wins[i].cursor), _abi.ptr(e.pow4)
+            r.losses3_out, r.scalars4_out = _abi.ptr(ent["loss3"][i]), _abi.ptr(e.scal4)
+            r.partial_ws, r.partial_capacity = _abi.ptr(e.loss_partials), e.loss_partials.numel()
+            r.loss_log_dev = _abi.ptr(wins[i].loss_log)
+            if klpen:
+                r.old_mean, r.old_std = _abi.ptr(e.mean_old), _abi.ptr(e.std_old)
+                r.kl_bound, r.pg_coef = float(kl_bounds[i]), float(pg_coefs[i])
+        idx = [i for i in range(S) if reps[i].active]
+        if not idx:
+            return losses
+        table = ent["table"]
+
+        def step():
+            _abi.check(lib.spo_wide_rows_ex_step_multi(_abi.ptr(table), S, nc, na, batch, int(actor_loss), int(actor_only),
+                                                       _abi.stream_ptr()), "spo_wide_rows_ex_step_multi")
+
+        _abi.check(lib.spo_wide_rows_ex_multi_upload(_abi.ptr(table), reps, S, nc, na, batch, batch, int(actor_loss), int(actor_only),
+                                                     _abi.stream_ptr()), "spo_wide_rows_ex_multi_upload")
+        if ent["graphs"] is None:
+            # first use: one eager step for the lazy per-kernel set-up, its effects on every taking-part run's parameters / moments /
+            # clocks / gradient / cursor undone (as _graphed_pass does for one engine), then the captures
+            state = [t for i in idx for t in (es[i].policy.theta, es[i].adam_m, es[i].adam_v, es[i].pow4, es[i].flat_grad, wins[i].cursor)]
+            snap = [t.clone() for t in state]
+            step()
+            for t, b in zip(state, snap):
+                t.copy_(b)
+            torch.cuda.synchronize(e0.dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                step()
+            unroll = max(1, int(os.environ.get("SPO_WIDE_GRAPH_UNROLL", "8")))
+            g_many = None
+            if unroll > 1:
+                g_many = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_many, capture_error_mode="thread_local"):
+                    for _ in range(unroll):
+                        step()
+            ent["graphs"] = (g, g_many, unroll)         # (the table, windows, loss and part buffers live in `ent` beside them)
+        g, g_many, unroll = ent["graphs"]
+        done = 0
+        if g_many is not None:
+            for _ in range(n_full // unroll):
+                g_many.replay()
+            done = (n_full // unroll) * unroll
+        for _ in range(n_full - done):
+            g.replay()
+        for i in idx:
+            e = es[i]
+            losses[i][:n_full].copy_(wins[i].loss_log[:n_full])
+            if actor_only:
+                e.adam_step_actor_extra += n_full
+            else:
+                e.adam_step += n_full
+            for k in range(n_full, n_mb):               # (the ragged last minibatch: eager, host clocks, as stand-alone)
+                e.minibatch_step_ex(perms64[i][k * batch:(k + 1) * batch], advs[i], losses[i][k], actor_loss, kl_bounds[i], pg_coefs[i],
+                                    actor_only, cfg=cfgs[i])
+                if actor_only:
+                    e.adam_step_actor_extra += 1
+                else:
+                    e.adam_step += 1
+        return losses
+
     def _launch_ex(self, entry, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active, nan_fill=True):
         """One launch of `entry` (spo_update_iter_ex_multi or spo_update_iter_ex_ks_multi) for the active runs; the clocks
         advance as learning_iter_ex advances them.  nan_fill=False: the feature-split PPO-Lagrangian step -- loss rows left
@@ -416,7 +547,7 @@ class PPOLagEngineGroup(_EngineGroup):
         return outs
 
     # ------------------------------------------------------------------ FOCOPS / CUP: spo_update_iter_ex of every active run
-    def batched_ex(self, actor_loss: int, cfgs=None) -> bool:
+    def batched_ex(self, actor_loss: int, cfgs=None, actor_only: bool = False) -> bool:
         """Does learning_iter_ex_all run as one launch (spo_update_iter_ex_multi)?  Where the stand-alone spo_update_iter_ex runs
         the four-wave kernel itself (spo_update_ex_multi_matches_single: the library's own routing answers -- always with the
         KL-penalty loss; with the clipped surrogate where the main + helper kernel does not take the launch, i.e. above 64
@@ -428,7 +559,8 @@ class PPOLagEngineGroup(_EngineGroup):
         if any(c.batch != c0.batch for c in cfgs):
             return False
         if self._rows:
-            return False                         # (the KL-penalty loss has no table-driven row-group form)
+            # (without klpen_rows: engine by engine; with it: the table-driven row-group step, spo_wide_rows_ex_step_multi)
+            return self._rows_batched_ex(cfgs, actor_loss, actor_only)
         if self._ks:
             return self._ks_batched(cfgs)
         return bool(self.lib.spo_update_ex_multi_supported(c0.obs_dim, c0.act_dim, c0.batch, int(actor_loss), len(self.engines))
@@ -447,9 +579,11 @@ class PPOLagEngineGroup(_EngineGroup):
         if not (len(perms) == len(advs) == len(active) == len(kl_bounds) == len(pg_coefs) == S):
             raise ValueError("learning_iter_ex_all: one perm, adv, kl_bound, pg_coef and active flag per engine")
         cfgs = [e._cfg_struct() for e in self.engines] if self._native else None
-        if not self.batched_ex(actor_loss, cfgs):
+        if not self.batched_ex(actor_loss, cfgs, actor_only):
             return [e.learning_iter_ex(perms[i], advs[i], actor_loss, kl_bounds[i], pg_coefs[i], actor_only) if active[i] else None
                     for i, e in enumerate(self.engines)]
+        if self._rows:
+            return self._rows_learning_iter_ex_all(cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active)
         entry = "spo_update_iter_ex_ks_multi" if self._ks else "spo_update_iter_ex_multi"
         return self._launch_ex(entry, cfgs, perms, advs, actor_loss, kl_bounds, pg_coefs, actor_only, active)
 

@@ -23,7 +23,7 @@ from safepo.common.lagrange import Lagrange, PIDLagrangian
 from safepo.common.logger import EpochLogger
 from safepo.common.model import ActorVCritic
 from safepo.parallel import dp_epoch_stat, init_from_env, require_equal_shards, shard_envs
-from safepo.utils.config import WIDE_ROWS_NOT_BUILT, fold_overrides, isaac_gym_map, refuse_seed_batch, seed_list
+from safepo.utils.config import KLPEN_ROWS_OTHER_SCRIPTS, WIDE_ROWS_NOT_BUILT, fold_overrides, isaac_gym_map, refuse_seed_batch, seed_list
 
 NO_CLIP = 1e30      # clamp(ratio, 1-1e30, 1+1e30) is the identity: pg's unclipped surrogate on the same kernel
 
@@ -110,6 +110,14 @@ def run(args, cfg_env, default_cfg: dict, multiplier: str | None = "adam", clip:
                          "/ 32 actions: HumanoidVelocity): give both")
     if variant != "ppo" and getattr(args, "batch_wide_rows", False):
         raise SystemExit(WIDE_ROWS_NOT_BUILT.format(what="focops and cup"))
+    if getattr(args, "batch_klpen_rows", False):
+        if variant == "ppo":
+            raise SystemExit(KLPEN_ROWS_OTHER_SCRIPTS.format(what="ppo_lag, ppo, pg and cppo_pid (their row-group step is shared with "
+                                                                  "--batch-wide-rows True)"))
+        if not getattr(args, "batch_update", False):
+            raise SystemExit("--batch-klpen-rows True widens --batch-update True for focops and cup (shapes on the wide-network path's "
+                             "row-group kernel: hidden sizes other than [64, 64], more than 512 observations or more than 32 actions): "
+                             "give both")
     if len(seed_list(args)) > 1:
         if variant != "ppo" and not getattr(args, "batch_update", False):
             refuse_seed_batch(args, "focops and cup",
@@ -268,6 +276,32 @@ def _require_rows_batch(obs_dim: int, act_dim: int, config: dict, rows: int, n_s
                          f"at most SPO_WIDE_GRAPH_MAX_BATCH = {graph_max} rows): nothing to share, one process per seed")
 
 
+def _require_klpen_rows_batch(obs_dim: int, act_dim: int, config: dict, rows: int, n_seeds: int, variant: str) -> None:
+    """--batch-klpen-rows True: SystemExit naming the limit unless `n_seeds` one-GPU WidePPOLagEngines of this shape and config
+    would step FOCOPS' passes (variant "focops") or both of CUP's stages (variant "cup") as seed-batched row-group launches
+    (PPOLagEngineGroup._rows_batched_ex, answered before an engine exists)."""
+    lib = _abi.load()
+    hidden = [int(h) for h in config["hidden_sizes"]]
+    batch = int(config.get("batch_size", max(rows // config.get("num_mini_batch", 1), 1)))
+    shape = f"{obs_dim} observations / {act_dim} actions, hidden_sizes {hidden}, minibatches of {batch} rows"
+    if n_seeds > _abi.WIDE_ROWS_MAX_REPLICAS:
+        raise SystemExit(f"--seeds: at most {_abi.WIDE_ROWS_MAX_REPLICAS} seeds share the row-group KL-penalty step's launches "
+                         f"(--batch-klpen-rows True), got {n_seeds}")
+    if not 1 <= act_dim <= _abi.WIDE_MAX_ACT or not 1 <= len(hidden) <= 4:
+        raise SystemExit(f"--batch-klpen-rows True: {shape} is outside the wide-network path (act_dim <= {_abi.WIDE_MAX_ACT}, up to four "
+                         "hidden layers)")
+    net_c, net_a = _abi.MlpNet.of([obs_dim] + hidden + [1]), _abi.MlpNet.of([obs_dim] + hidden + [act_dim])
+    kinds = [(_abi.ACTOR_LOSS_KL_PENALTY, 0)] if variant == "focops" else [(_abi.ACTOR_LOSS_CLIP, 0), (_abi.ACTOR_LOSS_KL_PENALTY, 1)]
+    if not all(lib.spo_wide_rows_ex_multi_supported(net_c, net_a, batch, loss, actor_only, n_seeds) for loss, actor_only in kinds):
+        raise SystemExit(f"--batch-klpen-rows True: {shape} does not fit the row-group kernel's KL-penalty form (at most 256 rows per "
+                         "minibatch; every level's images of a 16-row group AND the rows' old distribution within one CU's 160 KB of "
+                         "LDS; SPO_WIDE_ROWS not 0): one process per seed")
+    graph_max = int(os.environ.get("SPO_WIDE_GRAPH_MAX_BATCH", "2048"))
+    if not (0 < batch <= graph_max and (rows + batch - 1) // batch > 2):
+        raise SystemExit(f"--batch-klpen-rows True: {shape} over {rows} rows is not a graph-replayed pass (more than two minibatches of "
+                         f"at most SPO_WIDE_GRAPH_MAX_BATCH = {graph_max} rows): nothing to share, one process per seed")
+
+
 class _SeedRun:
     """One run of a seed-batched process: what run() holds in local variables, per seed."""
 
@@ -306,6 +340,7 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
 
     wide_obs = bool(getattr(args, "batch_wide_obs", False))
     wide_rows = bool(getattr(args, "batch_wide_rows", False))
+    klpen_rows = variant != "ppo" and bool(getattr(args, "batch_klpen_rows", False))
     if wide_obs and list(config["hidden_sizes"]) == [64, 64] and len(seeds) > _abi.KS_MAX_REPLICAS:
         raise SystemExit(f"--seeds: at most {_abi.KS_MAX_REPLICAS} seeds share a launch with --batch-wide-obs True (8 above 256 "
                          f"observations), got {len(seeds)}")
@@ -342,6 +377,13 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
                 # the seed count fit is known once the (first) environment tells the dims: checked before anything is logged
                 _require_rows_batch(obs_space.shape[0], act_space.shape[0], config, args.num_envs * local_steps_per_epoch, len(seeds))
                 r.engine = WidePPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
+            elif klpen_rows and not (list(config["hidden_sizes"]) == [64, 64] and _ks_shape_ok(
+                    obs_space.shape[0], act_space.shape[0], config, args.num_envs * local_steps_per_epoch)):
+                # --batch-klpen-rows True (focops, cup): the same shapes, whose FOCOPS / CUP steps share the five launches of
+                # spo_wide_rows_ex_step_multi.  Checked before anything is logged, as above
+                _require_klpen_rows_batch(obs_space.shape[0], act_space.shape[0], config, args.num_envs * local_steps_per_epoch,
+                                          len(seeds), variant)
+                r.engine = WidePPOLagEngine(r.policy, args.num_envs, local_steps_per_epoch, config, device, lr=3e-4)
             else:
                 raise SystemExit(f"--seeds with more than one seed needs the persistent kernels' shapes (hidden_sizes [64, 64], obs_dim <= "
                                  f"128, act_dim <= 16); {args.task} with hidden_sizes {config['hidden_sizes']} runs on the wide-network "
@@ -365,7 +407,8 @@ def run_seed_batch(args, cfg_env, default_cfg: dict, multiplier: str | None, cli
             obs, _ = r.env.reset()
             r.obs = _to_dev(obs, device)
         runs.append(r)
-    group = PPOLagEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs])
+    group = (PPOLagEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs], klpen_rows=True) if klpen_rows
+             else PPOLagEngineGroup([r.engine for r in runs], rngs=[r.rng for r in runs]))
 
     timings = []
     for epoch in range(epochs):

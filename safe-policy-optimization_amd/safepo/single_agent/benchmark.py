@@ -26,7 +26,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from safepo.utils.config import CRITIC_KS_BATCH_FIGURES, CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KS_BATCH_FIGURES, ROWS_BATCH_FIGURES
+from safepo.utils.config import CRITIC_KS_BATCH_FIGURES, CRITIC_SPLIT_BATCH_FIGURES, KLPEN_BATCH_FIGURES, KLPEN_ROWS_BATCH_FIGURES, KS_BATCH_FIGURES, ROWS_BATCH_FIGURES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALGOS = ["pcpo", "ppo_lag", "cup", "focops", "rcpo", "trpo_lag", "cpo", "cppo_pid"]
@@ -97,6 +97,11 @@ def parse_args(argv=None):
                    help="with --seeds-per-run and --hidden-sizes other than 64 64: group ppo_lag / ppo / pg / cppo_pid (up to 32 seeds "
                         "per subprocess, --batch-wide-rows True on those commands): their minibatch steps share the three launches of "
                         "the row-group step.  " + ROWS_BATCH_FIGURES + "  Default off: such widths keep one subprocess per seed")
+    p.add_argument("--batch-klpen-rows", action="store_true",
+                   help="with --seeds-per-run, --batch-focops-cup and --hidden-sizes other than 64 64: group focops / cup (up to 32 seeds "
+                        "per subprocess, --batch-update True --batch-klpen-rows True on those commands): their FOCOPS / CUP steps share "
+                        "the five launches of the row-group KL-penalty step.  " + KLPEN_ROWS_BATCH_FIGURES + "  Default off: such widths "
+                        "keep one subprocess per seed")
     return p.parse_args(argv)
 
 
@@ -184,10 +189,13 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                 hidden = getattr(args, "hidden_sizes", None)
                 custom = hidden is not None and [int(h) for h in hidden] != [64, 64]
                 rows = custom and getattr(args, "batch_wide_rows", False) and algo in SEED_BATCHED_ALGOS
+                # ... and, for focops / cup, the row-group KL-penalty step (--batch-klpen-rows with --batch-focops-cup)
+                klpen_rows = (custom and getattr(args, "batch_klpen_rows", False) and getattr(args, "batch_focops_cup", False)
+                              and algo in KLPEN_BATCHED_ALGOS)
                 if custom:
                     critic = klpen = split = critic_ks = wide = False
                 runs = [[s] for s in group]
-                if len(group) > 1 and rows:
+                if len(group) > 1 and (rows or klpen_rows):
                     runs = [group[i:i + ROWS_BATCH_MAX] for i in range(0, len(group), ROWS_BATCH_MAX)]
                 elif custom:
                     pass
@@ -212,7 +220,8 @@ def build_commands(args, script_dir: str = HERE, n_gpus: int | None = None):
                         + (["--batch-update", "True"] if batched and (klpen or (wide and algo in KLPEN_BATCHED_ALGOS)) else [])
                         + (["--batch-wide-obs", "True"] if batched and wide else [])
                         + (["--hidden-sizes"] + [str(int(h)) for h in hidden] if hidden is not None else [])
-                        + (["--batch-wide-rows", "True"] if batched and rows else []) + [
+                        + (["--batch-wide-rows", "True"] if batched and rows else [])
+                        + (["--batch-update", "True", "--batch-klpen-rows", "True"] if batched and klpen_rows else []) + [
                         "--write-terminal", "False", "--experiment",
                         shlex.quote(args.experiment), "--total-steps", str(total), "--num-envs", str(envs), "--steps-per-epoch",
                         str(per_epoch), "--device-id", str(len(commands) % n_gpus)]))

@@ -77,6 +77,10 @@ WIDE_ROWS_NOT_BUILT = ("--batch-wide-rows True is not available for {what}: the 
                        "the second-order scripts have no such form.  Run one process per seed")
 
 
+KLPEN_ROWS_OTHER_SCRIPTS = ("--batch-klpen-rows True is not available for {what}: the seed-batched row-group KL-penalty step is the "
+                            "FOCOPS / CUP step (focops, cup with --batch-update True)")
+
+
 def refuse_seed_batch(args, what: str, hint: str = "") -> None:
     """For the scripts without a seed-batched form: more than one seed is an error, not a silent single run."""
     if len(seed_list(args)) > 1:
@@ -90,6 +94,8 @@ def critic_seed_batch(args) -> bool:
     --batch-critic-fit True (their critic fits then share one launch per iteration); without it they are refused as ever."""
     if getattr(args, "batch_wide_rows", False):
         raise SystemExit(WIDE_ROWS_NOT_BUILT.format(what="the second-order scripts"))
+    if getattr(args, "batch_klpen_rows", False):
+        raise SystemExit(KLPEN_ROWS_OTHER_SCRIPTS.format(what="the second-order scripts"))
     if getattr(args, "batch_critic_fit_split", False) and not getattr(args, "batch_critic_fit", False):
         raise SystemExit("--batch-critic-fit-split True widens --batch-critic-fit True (65-128 observations, up to 32 seeds): give both")
     if getattr(args, "batch_critic_fit_feature_split", False) and not getattr(args, "batch_critic_fit", False):
@@ -151,6 +157,10 @@ ROWS_BATCH_FIGURES = ("Measured at 60 / 8, 4096 x 128 rows, batch 64: with hidde
                       "which is why one seed stays `--seed` (profiles/seed_batch_rows/step_times.txt).")
 
 
+# (quoted by --help here and in single_agent/benchmark.py; source: profiles/seed_batch_klpen_rows/step_times.txt)
+KLPEN_ROWS_BATCH_FIGURES = "Not measured (profiles/seed_batch_klpen_rows/step_times.txt)."
+
+
 def single_agent_args(argv=None):
     """-> (args, cfg_env).  cfg_env is {} for non-Isaac tasks (reference config.py:172-191)."""
     parser = build_parser()
@@ -202,6 +212,15 @@ def single_agent_args(argv=None):
                              "per-XCD budget: no workgroup waits for another), each seed the run its `--seed` would be.  "
                              + ROWS_BATCH_FIGURES + "  Default False: such shapes are refused with several seeds; focops, cup and the "
                              "second-order scripts refuse the flag (not built)")
+    parser.add_argument("--batch-klpen-rows", type=_bool, default=False,
+                        help="focops and cup with --seeds and --batch-update True: also take shapes that step on the wide-network "
+                             "path's row-group kernel -- hidden sizes other than [64, 64] (--hidden-sizes), more than 512 observations "
+                             "or more than 32 actions, minibatches of up to 256 rows whose images and old distribution fit one CU's "
+                             "LDS -- whose FOCOPS steps and both of CUP's stages then share the step's five launches "
+                             "(spo_wide_rows_ex_step_multi: up to 32 seeds of one shape, run r a slice of each grid; world size 1; "
+                             "graph-replayed passes only; no workgroup waits for another), each seed the run its `--seed` would be.  "
+                             + KLPEN_ROWS_BATCH_FIGURES + "  Default False: such shapes are refused with several seeds; the other ten "
+                             "scripts refuse the flag")
     args = parser.parse_args(argv)
     if args.task in isaac_gym_map:
         raise Exception("Please install isaacgym to run Isaac Gym tasks!")
