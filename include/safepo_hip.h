@@ -1255,6 +1255,34 @@ int spo_wide_linesearch_sums(const float* mean_new, const float* log_std_new, co
                              const float* adv_a, const float* adv_b, const float* mean_old, const float* log_std_old, int64_t rows,
                              int act_dim, double* partial_ws, int partial_capacity, double* sums3_inout, int accumulate,
                              void* stream);
+
+/* ---- CPO full-batch primitives for hidden widths other than [64, 64] (csrc/cpo_rows.hip): a tanh MLP actor described by `net`
+ * with two hidden layers of width 1..128, obs_dim 1..128 and act_dim 1..16.  Same meaning and workspaces as the spo_cpo512_*
+ * namesakes, with `net` in place of (obs_dim, act_dim); theta, vec, grad_out and out use the wide engine's ACTOR layout
+ * [log_std | W_0 b_0 | W_1 b_1 | W_2 b_2] (Pa = act_dim + spo_mlp_param_count(net) floats), mean_old is [rows, act_dim].
+ * A net outside the envelope fails with -2 before any device work, naming the dimension (obs_dim, hidden width / hidden
+ * layers, act_dim).
+ *   spo_cpo_rows_supported        1 exactly inside the envelope (host code, no GPU needed)
+ *   spo_cpo_rows_num_partials     workgroups = partial vectors for `rows` rows (sizes partial_ws [n * Pa] / loss_ws [n])
+ *   spo_cpo_rows_chunk_rows       rows one workgroup takes per pass of its chunk loop (host code)
+ *   spo_cpo_rows_surrogate_grad   cpo.py:356-365, :372-381
+ *   spo_cpo_rows_fvp              cpo.py:132-157: J^T diag(1/sigma^2) J vec / (rows * act_dim), 0 on the log_std entries
+ *   spo_cpo_rows_linesearch_eval  cpo.py:473-491
+ *   spo_cpo_rows_actor_mean       the forward pass of spo_cpo_rows_linesearch_eval (KL == 0.0 at unchanged parameters) */
+int spo_cpo_rows_supported(const spo_mlp_net* net);
+int spo_cpo_rows_num_partials(int64_t rows);
+int spo_cpo_rows_chunk_rows(void);
+int spo_cpo_rows_surrogate_grad(const float* theta, const float* obs, const float* act, const float* logp_old, const float* adv,
+                                float sign, int64_t rows, const spo_mlp_net* net, float* partial_ws, double* loss_ws,
+                                float* grad_out, double* loss_sum_out, void* stream);
+int spo_cpo_rows_fvp(const float* theta, const float* obs, const float* vec, int64_t rows, const spo_mlp_net* net,
+                     float* partial_ws, double* loss_ws, float* out, void* stream);
+int spo_cpo_rows_linesearch_eval(const float* theta, const float* obs, const float* act, const float* logp_old,
+                                 const float* adv_r, const float* adv_c, const float* mean_old, const float* log_std_old,
+                                 int64_t rows, const spo_mlp_net* net, double* partial_ws, int partial_capacity,
+                                 double* sums3_out, void* stream);
+int spo_cpo_rows_actor_mean(const float* theta, const float* obs, float* mean_out, int64_t rows, const spo_mlp_net* net,
+                            void* stream);
 /* spo_wide_clip_adam_dev -- spo_wide_clip_adam_ex with the optimiser clocks on the DEVICE: pow4_dev = double[6] = {beta1^t, beta2^t of
  * the critics' optimisers, beta1^t, beta2^t of the actor's} before this step, then {lr_actor, lr_critic} (each: >= 0 overrides the
  * cfg's value, so a schedule does not change a captured launch's arguments; negative: the cfg's -- ABI 2); the clocks of the optimisers inside the Adam range

@@ -221,6 +221,13 @@ PROTOTYPES = {
     "spo_cpo512_fvp": (c_int, [P, P, P, c_int64, c_int, c_int, P, P, P, P]),
     "spo_cpo512_linesearch_eval": (c_int, [P] * 8 + [c_int64, c_int, c_int, P, c_int, P, P]),
     "spo_cpo512_actor_mean": (c_int, [P, P, P, c_int64, c_int, c_int, P]),
+    "spo_cpo_rows_supported": (c_int, [POINTER(MlpNet)]),
+    "spo_cpo_rows_num_partials": (c_int, [c_int64]),
+    "spo_cpo_rows_chunk_rows": (c_int, []),
+    "spo_cpo_rows_surrogate_grad": (c_int, [P] * 5 + [c_float, c_int64, POINTER(MlpNet), P, P, P, P, P]),
+    "spo_cpo_rows_fvp": (c_int, [P, P, P, c_int64, POINTER(MlpNet), P, P, P, P]),
+    "spo_cpo_rows_linesearch_eval": (c_int, [P] * 8 + [c_int64, POINTER(MlpNet), P, c_int, P, P]),
+    "spo_cpo_rows_actor_mean": (c_int, [P, P, P, c_int64, POINTER(MlpNet), P]),
     "spo_critic_fit_iter": (c_int, [P, P, P, c_int64, P, P, P, P, c_int64, POINTER(PpoCfg), P, P, P, P]),
     "spo_update_iter_ex": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P, P, c_int64, POINTER(PpoCfg), c_int, P, P,
                                    c_float, c_float, c_int, P, P, P]),

@@ -543,6 +543,10 @@ class WideCPOEngine(_WideOps, CPOEngine):
     `_actor_on_full_batch_kernels`; SPO_CPO_OBS128=0 keeps the chunked wide path).  With hidden [64, 64], 129 <= obs_dim <= 512
     and act_dim <= 32 (HumanoidVelocity: 376 / 17) they run on the streamed-W1 forms (spo_cpo512_*: W1 in 64-feature slices through
     LDS, two output tiles; `_actor_on_streamed_kernels`; SPO_CPO_OBS512=0 keeps the chunked wide path).
+    With any OTHER two hidden widths up to 128 (e.g. [128, 128]), obs_dim <= 128 and act_dim <= 16 they -- and the snapshot of the
+    old means -- run on the row-chunk kernels of csrc/cpo_rows.hip (spo_cpo_rows_*: one persistent launch per primitive, weights
+    read as MFMA operands from L2, weight gradients kept in accumulators across the chunks; `_actor_on_row_group_kernels`;
+    SPO_CPO_ROWS=0 keeps the chunked wide path).
     The critic fit keeps the persistent two-critic kernel whenever the CRITICS fit it (hidden [64, 64], obs_dim <= 128: their
     layout does not depend on act_dim), else runs minibatch by minibatch on the wide kernels with the actor's stale gradient
     kept in the flat gradient vector so the joint clip sees and rescales it (cpo.py:557).  Data-parallel like CPOEngine: the
@@ -575,6 +579,13 @@ class WideCPOEngine(_WideOps, CPOEngine):
                       else self.lib.spo_cpo128_num_partials)(self.M)
             self.partial_ws = torch.empty(nparts * self.Pa, dtype=torch.float32, device=self.dev)
             self.loss_ws = torch.empty(nparts, dtype=torch.float64, device=self.dev)
+        self._actor_on_row_group_kernels = (not self._actor_on_full_batch_kernels and not self._actor_on_streamed_kernels
+                                            and bool(self.lib.spo_cpo_rows_supported(w.net_a))
+                                            and os.environ.get("SPO_CPO_ROWS", "1") != "0")
+        if self._actor_on_row_group_kernels:
+            nparts = self.lib.spo_cpo_rows_num_partials(self.M)
+            self.partial_ws = torch.empty(nparts * self.Pa, dtype=torch.float32, device=self.dev)
+            self.loss_ws = torch.empty(nparts, dtype=torch.float64, device=self.dev)
 
     def _alloc_full_batch_workspaces(self) -> None:
         self.partial_ws = self.loss_ws = None           # allocated in __init__ when the full-batch kernels are used
@@ -590,6 +601,14 @@ class WideCPOEngine(_WideOps, CPOEngine):
                        "spo_cpo512_actor_mean")
             off = self.policy.log_std_offset
             self.logstd_old.copy_(self.policy.theta[off:off + self.A])
+            torch.exp(self.logstd_old, out=self.std_old)
+            return None
+        if self._actor_on_row_group_kernels:
+            # ... and here by the forward body spo_cpo_rows_linesearch_eval shares with spo_cpo_rows_actor_mean
+            _abi.check(self.lib.spo_cpo_rows_actor_mean(_abi.ptr(self._theta_ls()), _abi.ptr(self.buffer.data["obs"]),
+                                                        _abi.ptr(self.mean_old), self.M, self.wide.net_a, _abi.stream_ptr()),
+                       "spo_cpo_rows_actor_mean")
+            self.logstd_old.copy_(self._log_std())
             torch.exp(self.logstd_old, out=self.std_old)
             return None
         return super().snapshot_old_distribution()
@@ -612,6 +631,10 @@ class WideCPOEngine(_WideOps, CPOEngine):
     def _log_std(self):
         return self.policy.theta[self.ls_off:self.ls_off + self.A]
 
+    def _theta_ls(self):
+        """The actor layout the spo_cpo_rows_* kernels take: log_std, then the mean network."""
+        return self.policy.theta[self.ls_off:]
+
     def _surrogate_grad_local(self, adv: torch.Tensor, sign: float) -> torch.Tensor:
         if self._actor_on_full_batch_kernels or self._actor_on_streamed_kernels:
             fn, name = ((self.lib.spo_cpo512_surrogate_grad, "spo_cpo512_surrogate_grad") if self._actor_on_streamed_kernels
@@ -622,6 +645,14 @@ class WideCPOEngine(_WideOps, CPOEngine):
                 _abi.ptr(self.policy.theta), _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"]),
                 _abi.ptr(adv), float(sign), self.M, self.D, self.A, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws),
                 _abi.ptr(g), _abi.ptr(self.loss_sum), _abi.stream_ptr()), name)
+            return g
+        if self._actor_on_row_group_kernels:
+            d = self.buffer.data
+            g = torch.empty(self.Pa, dtype=torch.float32, device=self.dev)
+            _abi.check(self.lib.spo_cpo_rows_surrogate_grad(
+                _abi.ptr(self._theta_ls()), _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"]), _abi.ptr(adv),
+                float(sign), self.M, self.wide.net_a, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws), _abi.ptr(g),
+                _abi.ptr(self.loss_sum), _abi.stream_ptr()), "spo_cpo_rows_surrogate_grad")
             return g
         w, lib, d = self.wide, self.lib, self.buffer.data
         adv, logp_old = adv.reshape(-1), d["log_prob"].view(-1)
@@ -649,6 +680,12 @@ class WideCPOEngine(_WideOps, CPOEngine):
                                                self.M, self.D, self.A, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws),
                                                _abi.ptr(out), _abi.stream_ptr()), name)
             return out
+        if self._actor_on_row_group_kernels:
+            out = torch.empty(self.Pa, dtype=torch.float32, device=self.dev)
+            _abi.check(self.lib.spo_cpo_rows_fvp(_abi.ptr(self._theta_ls()), _abi.ptr(self.buffer.data["obs"]), _abi.ptr(v), self.M,
+                                                 self.wide.net_a, _abi.ptr(self.partial_ws), _abi.ptr(self.loss_ws), _abi.ptr(out),
+                                                 _abi.stream_ptr()), "spo_cpo_rows_fvp")
+            return out
         w, lib = self.wide, self.lib
         tangent = v[self.A:].contiguous()
         out = torch.zeros(self.Pa, dtype=torch.float32, device=self.dev)
@@ -675,6 +712,14 @@ class WideCPOEngine(_WideOps, CPOEngine):
                 _abi.ptr(adv_a), _abi.ptr(adv_b), _abi.ptr(self.mean_old), _abi.ptr(self.logstd_old),
                 self.M, self.D, self.A, _abi.ptr(self.ls_partials), self.ls_partials.numel(), _abi.ptr(self.ls_sums),
                 _abi.stream_ptr()), name)
+            return
+        if self._actor_on_row_group_kernels:
+            d = self.buffer.data
+            _abi.check(self.lib.spo_cpo_rows_linesearch_eval(
+                _abi.ptr(self._theta_ls()), _abi.ptr(d["obs"]), _abi.ptr(d["act"]), _abi.ptr(d["log_prob"]), _abi.ptr(adv_a),
+                _abi.ptr(adv_b), _abi.ptr(self.mean_old), _abi.ptr(self.logstd_old), self.M, self.wide.net_a,
+                _abi.ptr(self.ls_partials), self.ls_partials.numel(), _abi.ptr(self.ls_sums), _abi.stream_ptr()),
+                "spo_cpo_rows_linesearch_eval")
             return
         w, lib, d = self.wide, self.lib, self.buffer.data
         adv_a, adv_b, logp_old = adv_a.reshape(-1), adv_b.reshape(-1), d["log_prob"].view(-1)
