@@ -884,6 +884,22 @@ int spo_ma_backward(const float* theta, const spo_ma_net* net, const float* x, i
 int64_t spo_ma_jvp_scratch_floats(const spo_ma_net* net, int64_t rows);
 int spo_ma_jvp(const float* theta, const spo_ma_net* net, const float* tangent, int64_t rows, const float* ws, float* dout,
                float* scratch, void* stream);
+/* MACPO's Fisher-vector product in one fused pass (csrc/ma_fvp.hip; replaces the double torch.autograd.grad of
+ * safepo/multi_agent/macpo.py:187-199, and spo_ma_jvp + the scaling + spo_ma_backward above: 4 launches instead of 26):
+ *   out = J^T diag(m) J vec,   m[j] = m_diag[j] / rows_global,   J = d(head output)/d(theta) over this rank's `rows` rows,
+ * at the point whose activations spo_ma_forward left in ws.  out is flat, laid out like theta, every entry written; the log_std
+ * slot is 0 (macpo.py:187-199: the caller adds the log_std block of the Hessian and the 0.1 p damping after its all-reduce).
+ *   spo_ma_fvp_supported      1 for an actor with in_dim 1..128, hidden 1..128, out_dim 1..16 and 1 or 2 blocks, else 0
+ *   spo_ma_fvp_num_partials   workgroups = partial vectors for `rows` rows (32-row chunks, at most 256)
+ *   spo_ma_fvp_scratch_floats floats of scratch for `rows` rows; -1 outside the envelope or for rows < 1
+ *   spo_ma_fvp                (macpo.py:187-199) vec, out: float[spo_ma_param_count]; m_diag: float[out_dim]; -2 with the dimension
+ *                             named for a net outside the envelope.  No allocation, no synchronisation, no atomics (repeats are
+ *                             bit-identical); capturable. */
+int spo_ma_fvp_supported(const spo_ma_net* net);
+int spo_ma_fvp_num_partials(int64_t rows);
+int64_t spo_ma_fvp_scratch_floats(const spo_ma_net* net, int64_t rows);
+int spo_ma_fvp(const float* theta, const spo_ma_net* net, const float* vec, const float* m_diag, int64_t rows,
+               int64_t rows_global, const float* ws, float* scratch, float* out, void* stream);
 /* Insert of one environment step into the per-agent buffers (Runner.insert, mappolag.py:449-492) as ONE launch: the
  * environment's [threads, agents, ...] observations / shared observations / rewards / costs are written to every agent's
  * time-major buffer row, masks and active masks are formed from the done flags (dones: [threads, agents] bytes, non-zero =

@@ -38,21 +38,13 @@
 // theta / vec / out: the wide engine's actor layout [log_std | W_0 b_0 | W_1 b_1 | ...], W row-major [out, in].
 #include "common.h"
 #include "mlp_mfma.h"
+#include "rows_frag.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
 using namespace spo;
+using namespace spo::rows;
 
-constexpr int ROWS = 32;                   // rows per chunk: two 16-row MFMA tiles
-constexpr int NTHR = 256;                 // 4 waves, one per SIMD: 512 registers each
-constexpr int VW = 2;                      // every wave plays two of the eight tile owners ("virtual waves" w and w + 4)
-constexpr int MAXT = 8;                    // 16-wide tiles per layer dimension: widths and obs_dim up to 128
-constexpr int MAXW = 16 * MAXT;
-constexpr int MAXA = 16;
-constexpr int LDI = MAXW + 4;
-constexpr int LDO = MAXA + 4;
-constexpr int IMG = ROWS * LDI;
-constexpr int MAX_GRID = 256;              // one workgroup per CU
 enum { M_SURR = 0, M_FVP = 1, M_LS = 2, M_MEAN = 3 };
 
 struct RowsNet {
@@ -73,84 +65,6 @@ struct RowsArgs {
 template <int NL, int MODE>
 constexpr int lds_floats() {
   return ((MODE == M_SURR || MODE == M_FVP) ? 3 + NL : 1 + NL) * IMG + ROWS * LDO;
-}
-
-struct __attribute__((packed, aligned(4))) F4U { float v[4]; };      // a row fragment: the flat vector is only 4-byte aligned
-
-// W[row][c0 .. c0 + 3], zero outside [nrows, ncols]; addresses clamped, never predicated.  Offsets are unsigned 32-bit values
-// on a uniform base: one address register per load instead of a 64-bit pair.
-__device__ __forceinline__ f4 ld_row4(const float* __restrict__ W, int ld, int row, int nrows, int c0, int ncols) {
-  const bool rok = row < nrows;
-  const unsigned base = (unsigned)((rok ? row : 0) * ld);
-  f4 v;
-  if ((ncols & 3) == 0) {
-    const bool ok = rok && c0 < ncols;
-    const F4U t = *reinterpret_cast<const F4U*>(&W[base + (unsigned)(c0 < ncols ? c0 : 0)]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ok ? t.v[e] : 0.f;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = c0 + e;
-      const float t = W[base + (unsigned)(c < ncols ? c : 0)];
-      v[e] = (rok && c < ncols) ? t : 0.f;
-    }
-  }
-  return v;
-}
-
-// W[r0 .. r0 + 3][col]
-__device__ __forceinline__ f4 ld_col4(const float* __restrict__ W, int ld, int r0, int nrows, int col, int ncols) {
-  const bool cok = col < ncols;
-  const unsigned base = (unsigned)(cok ? col : 0);
-  f4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r = r0 + e;
-    const float t = W[base + (unsigned)((r < nrows ? r : 0) * ld)];
-    v[e] = (cok && r < nrows) ? t : 0.f;
-  }
-  return v;
-}
-
-// which tile of `ntiles` 16-feature tiles, and which row tiles of the chunk, a wave computes in a forward / dH sub-phase
-struct Unit { int t, r0, nr; bool on; };
-__device__ __forceinline__ Unit unit_of(int wave, int ntiles) {
-  if (ntiles > 4) return Unit{wave, 0, 2, wave < ntiles};
-  return Unit{wave >> 1, wave & 1, 1, (wave >> 1) < ntiles};
-}
-
-// acc[i] += W[16 t + j][:] . IN[row tile r0 + i][:]   (every fragment of the row band in flight before the first product)
-__device__ __forceinline__ void mm_rows(const float* __restrict__ Wg, int out, int in, const float* IN, const Unit u, int j, int q,
-                                        f4 (&acc)[2]) {
-  const int nk = (in + 15) >> 4;
-  f4 af[MAXT];
-#pragma unroll
-  for (int nt = 0; nt < MAXT; ++nt)
-    if (nt < nk) af[nt] = ld_row4(Wg, in, 16 * u.t + j, out, 16 * nt + 4 * q, in);
-#pragma unroll
-  for (int nt = 0; nt < MAXT; ++nt)
-    if (nt < nk) {
-      f4 b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        if (i < u.nr) b[i] = *reinterpret_cast<const f4*>(IN + (16 * (u.r0 + i) + j) * LDI + 16 * nt + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          if (i < u.nr) acc[i] = mfma4(af[nt][r], b[i][r], acc[i]);
-    }
-}
-
-__device__ __forceinline__ f4 bias4(const float* __restrict__ b, int f0, int out) {
-  f4 v;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float t = b[(unsigned)(f0 + r < out ? f0 + r : 0)];
-    v[r] = f0 + r < out ? t : 0.f;
-  }
-  return v;
 }
 
 template <int NL, int MODE>

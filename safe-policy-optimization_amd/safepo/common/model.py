@@ -251,6 +251,27 @@ class _MAFlatNet(nn.Module):
                                   _abi.ptr(scratch), _abi.stream_ptr()), "spo_ma_jvp")
         return dout
 
+    def fvp_supported(self) -> bool:
+        """The fused Fisher-vector product (spo_ma_fvp) takes this network: an actor, dims up to 128 / 128 / 16, 1 or 2 blocks."""
+        return bool(_abi.load().spo_ma_fvp_supported(self._net))
+
+    def net_fvp(self, saved, vec: torch.Tensor, m_diag: torch.Tensor, rows_global: int, out: torch.Tensor) -> None:
+        """out <- J^T diag(m_diag / rows_global) J vec at the point of `saved` (spo_ma_fvp: one fused pass in place of net_jvp, the
+        scaling and net_backward); flat like theta, the log_std slot 0.  The scratch is kept with the network and only grows."""
+        x, ws = saved
+        lib = _abi.load()
+        rows = x.shape[0]
+        vec = _abi.require_gpu_tensor(vec.contiguous(), "vec", torch.float32)
+        m_diag = _abi.require_gpu_tensor(m_diag.reshape(-1).contiguous(), "m_diag", torch.float32)
+        out = _abi.require_gpu_tensor(out, "out", torch.float32)
+        assert vec.numel() == out.numel() == self.theta.numel() and m_diag.numel() == self._net.out_dim and out.is_contiguous()
+        need = int(lib.spo_ma_fvp_scratch_floats(self._net, rows))
+        scratch = getattr(self, "_fvp_scratch", None)
+        if scratch is None or scratch.numel() < need or scratch.device != x.device:
+            scratch = self._fvp_scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+        _abi.check(lib.spo_ma_fvp(_abi.ptr(self.theta), self._net, _abi.ptr(vec), _abi.ptr(m_diag), rows, int(rows_global), _abi.ptr(ws),
+                                  _abi.ptr(scratch), _abi.ptr(out), _abi.stream_ptr()), "spo_ma_fvp")
+
     def net_backward(self, saved, dout: torch.Tensor, grad: torch.Tensor) -> None:
         x, ws = saved
         lib = _abi.load()

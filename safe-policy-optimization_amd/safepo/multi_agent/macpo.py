@@ -8,8 +8,9 @@ agent (macpo.py:201-371) instead of clipped-surrogate Adam steps:
   * two conjugate-gradient solves against the Fisher matrix.  The reference differentiates its KL expression twice
     (macpo.py:187-199).  At theta = theta_old the mean enters that expression only through (mu_old - mu)^2, so its
     Hessian is exactly J^T M J with M = 2 / (1e-8 + 2 sigma^2) per action dimension, plus a diagonal block for
-    log_std (sigma is state-independent) -- no second-order autograd: one forward-mode pass (spo_ma_jvp: in-tree MFMA
-    GEMMs + a LayerNorm/ELU tangent kernel) and one ordinary backward pass per product;
+    log_std (sigma is state-independent) -- no second-order autograd: one fused pass per product for hidden widths up to 128
+    (spo_ma_fvp, csrc/ma_fvp.hip), otherwise one forward-mode pass (spo_ma_jvp: in-tree MFMA GEMMs + a LayerNorm/ELU
+    tangent kernel) and one ordinary backward pass;
   * the case analysis for (lam, nu), the step and the backtracking line search on the host, as written.
 
 Data parallel (torchrun, as mappolag.train: equal shards of n_rollout_threads, rank-0 logging).  Every quantity of the
@@ -26,6 +27,8 @@ read.  world_size == 1 keeps the host-driven arithmetic below unless config["mac
 Surface: MACPO_Policy, MACPO_Trainer, Runner, train(args, cfg_train).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -135,9 +138,14 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
         mean); the log_std block and the damping are not, and are added afterwards on every replica."""
         a = self.policy.actor
         rows_g = saved[0].shape[0] * self.comm.world_size
-        dmu = a.net_jvp(saved, p)
-        out = torch.zeros_like(p)
-        a.net_backward(saved, dmu * (m_diag / rows_g), out)
+        # SPO_MA_FVP=0 (read at every call: an A/B knob) keeps the forward-mode + backward pair for a network the fused kernel takes
+        if os.environ.get("SPO_MA_FVP", "1") != "0" and a.fvp_supported():
+            out = torch.empty_like(p)
+            a.net_fvp(saved, p, m_diag, rows_g, out)
+        else:
+            dmu = a.net_jvp(saved, p)
+            out = torch.zeros_like(p)
+            a.net_backward(saved, dmu * (m_diag / rows_g), out)
         self.comm.all_reduce_sum_(out)
         ls = a.offset(6)
         out[ls:ls + a.act_dim] = h_ls * p[ls:ls + a.act_dim]
