@@ -984,6 +984,23 @@ int spo_ma_trpo_linesearch_sums(const float* mean, const float* log_std, float s
                                 const float* old_logp, const float* adv, const float* cost_adv, const float* factor,
                                 const float* mu_old, const float* std_old, int64_t rows, int act_dim, double* sums4_out,
                                 float* ratio_out_or_null, double* partial_ws, void* stream);
+/* One line-search candidate of MACPO's actor in two launches (csrc/ma_ls_eval.hip; macpo.py:329-366 up to the accept test): what
+ * spo_ma_forward + spo_ma_trpo_linesearch_sums give (7 launches at hidden 128 / two blocks, every activation of every row written
+ * to the workspace), from the raw observations: theta (the candidate, already written by the caller) and obs [rows, in_dim] go
+ * through input LayerNorm -> blocks -> head on chip, 32 rows per workgroup trip, and the row terms are formed with the device
+ * functions spo_ma_trpo_linesearch_sums uses (csrc/ma_ls_row.h).  sums4_out, ratio_out_or_null, partial_ws and the remaining
+ * arguments have the meaning and order of spo_ma_trpo_linesearch_sums; act_dim is net->out_dim.  One fp64 quadruple per workgroup
+ * (at most 256) in partial_ws, added in a fixed order by a second launch: no atomics, repeats are bit-identical; no allocation, no
+ * synchronisation; capturable.  No workspace: nothing is kept for a backward pass.  MACPO_Trainer.trpo_update takes it with
+ * SPO_MA_LS_FUSED=1 (opt-in: at 10 000 rows its gain per candidate is inside the timing's spread, profiles/ma_ls_eval/step_times.txt).
+ *   spo_ma_ls_eval_supported  1 for an actor with in_dim 1..128, hidden 1..128, out_dim 1..16 and 1 or 2 blocks (the envelope of
+ *                             spo_ma_fvp), else 0
+ *   spo_ma_ls_eval            -2 with the dimension named for a net outside the envelope, -1 "bad args" for a null pointer or
+ *                             rows < 1, both before any HIP call */
+int spo_ma_ls_eval_supported(const spo_ma_net* net);
+int spo_ma_ls_eval(const float* theta, const spo_ma_net* net, const float* obs, float std_x_coef, float std_y_coef, const float* act,
+                   const float* old_logp, const float* adv, const float* cost_adv, const float* factor, const float* mu_old,
+                   const float* std_old, int64_t rows, double* sums4_out, float* ratio_out_or_null, double* partial_ws, void* stream);
 int spo_ma_cg_init(const float* b, float* x, float* r, float* p, float* state4, double* ws, int64_t n, void* stream);
 int spo_ma_cg_update(const float* avp, float* x, float* r, float* p, float* state4, double* ws, int64_t n, float residual_tol,
                      void* stream);

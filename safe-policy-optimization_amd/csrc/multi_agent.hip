@@ -11,6 +11,7 @@
 // so results are BIT-IDENTICAL to the reference; every row access is coalesced across rollout threads.
 // HBM-bound: 20 B read (r, c, v_r, v_c, mask) + 8 B written per (thread, step); loads are issued UNROLL steps ahead.
 #include "common.h"
+#include "ma_ls_row.h"
 #include "../../include/safepo_hip.h"
 
 namespace {
@@ -141,9 +142,10 @@ extern "C" int spo_ma_insert_step(const float* obs, const float* share_obs, cons
 // row count).  ratio = prod_d exp(logp_d - old_logp_d) with logp_d exactly as ma_logp_kernel (csrc/ma_net.hip) forms it;
 // KL_row = sum_d [log s_old - log s + (s_old^2 + (mu_old - mu)^2) / (1e-8 + 2 s^2) - 0.5]  (macpo.py:153-166, as written).
 // Fixed-order reduction: wave shuffle tree -> four waves -> per-block partial -> one workgroup per sum over the partials.
+// The row's arithmetic is csrc/ma_ls_row.h, shared with the fused candidate evaluation (ma_ls_eval.hip).
 namespace {
-constexpr float MA_LOG_SQRT_2PI_F = 0.91893853320467274178f;
-constexpr int LS_NS = 4;
+using spo::ma_ls_dim_consts; using spo::ma_ls_dim_term; using spo::ma_ls_row_add;
+constexpr int LS_NS = spo::MA_LS_NS;
 constexpr int LS_MAX_BLOCKS = 1024;
 
 __global__ __launch_bounds__(256) void ma_trpo_ls_kernel(
@@ -154,28 +156,13 @@ __global__ __launch_bounds__(256) void ma_trpo_ls_kernel(
   __shared__ double sh[LS_NS][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float sd[SPO_MAX_ACT], so2[SPO_MAX_ACT], dlog[SPO_MAX_ACT];
-  for (int a = 0; a < A; ++a) {
-    sd[a] = yc / (1.f + expf(-log_std[a] / xc));
-    const float so = std_old[a];
-    so2[a] = so * so;
-    dlog[a] = logf(so) - logf(sd[a]);
-  }
+  for (int a = 0; a < A; ++a) ma_ls_dim_consts(log_std[a], std_old[a], xc, yc, sd[a], so2[a], dlog[a]);
   double acc[LS_NS] = {0, 0, 0, 0};
   for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < B; r += (int64_t)gridDim.x * 256) {
     float ratio = 1.f, kl = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float mu = mean[r * A + a];
-      const float d = act[r * A + a] - mu;
-      const float lp = -(d * d) / (2.f * sd[a] * sd[a]) - logf(sd[a]) - MA_LOG_SQRT_2PI_F;
-      ratio *= expf(lp - old_logp[r * A + a]);                 // torch.exp per dimension, then torch.prod
-      const float dm = mu_old[r * A + a] - mu;
-      kl += dlog[a] + (so2[a] + dm * dm) / (1e-8f + 2.f * sd[a] * sd[a]) - 0.5f;
-    }
-    const float w = ratio * factor[r];
-    acc[0] += (double)(w * adv[r]);
-    acc[1] += (double)(w * cost_adv[r]);
-    acc[2] += (double)kl;
-    acc[3] += (double)ratio;
+    for (int a = 0; a < A; ++a)
+      ma_ls_dim_term(mean[r * A + a], act[r * A + a], old_logp[r * A + a], mu_old[r * A + a], sd[a], so2[a], dlog[a], ratio, kl);
+    ma_ls_row_add(ratio, kl, factor[r], adv[r], cost_adv[r], acc);
     if (ratio_out) ratio_out[r] = ratio;
   }
   for (int k = 0; k < LS_NS; ++k) {

@@ -289,6 +289,8 @@ PROTOTYPES = {
     "spo_ma_value_loss": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P, P, P]),
     "spo_ma_clip_adam": (c_int, [P, P, P, P, c_int64, c_int64, c_float, c_float, c_float, c_float, c_int, P, P, P]),
     "spo_ma_trpo_linesearch_sums": (c_int, [P, P, c_float, c_float] + [P] * 7 + [c_int64, c_int, P, P, P, P]),
+    "spo_ma_ls_eval_supported": (c_int, [POINTER(MaNet)]),
+    "spo_ma_ls_eval": (c_int, [P, POINTER(MaNet), P, c_float, c_float] + [P] * 7 + [c_int64, P, P, P, P]),
     "spo_ma_cg_init": (c_int, [P] * 6 + [c_int64, P]),
     "spo_ma_cg_update": (c_int, [P] * 6 + [c_int64, c_float, P]),
     "spo_ma_gae": (c_int, [P] * 7 + [c_int64, c_int64, c_double, c_double, c_float, c_float, c_float, c_float, P]),

@@ -272,6 +272,30 @@ class _MAFlatNet(nn.Module):
         _abi.check(lib.spo_ma_fvp(_abi.ptr(self.theta), self._net, _abi.ptr(vec), _abi.ptr(m_diag), rows, int(rows_global), _abi.ptr(ws),
                                   _abi.ptr(scratch), _abi.ptr(out), _abi.stream_ptr()), "spo_ma_fvp")
 
+    def ls_eval_supported(self) -> bool:
+        """The fused line-search candidate evaluation (spo_ma_ls_eval) takes this network: the envelope of fvp_supported."""
+        return bool(_abi.load().spo_ma_ls_eval_supported(self._net))
+
+    def net_ls_eval(self, x: torch.Tensor, act, old_logp, adv, cost_adv, factor, mu_old, std_old, sums4: torch.Tensor,
+                    ratio: torch.Tensor | None, partial_ws: torch.Tensor) -> None:
+        """sums4 (float64[4]) <- this rank's row sums {ratio*factor*adv, ratio*factor*cost_adv, KL_row, ratio} at the current
+        theta for the raw observations x [rows, in], ratio <- the per-row ratio (spo_ma_ls_eval: one fused pass in place of
+        net_forward + spo_ma_trpo_linesearch_sums; no workspace, nothing is kept).  partial_ws: float64[MA_LS_WS_DOUBLES]."""
+        x = _abi.require_gpu_tensor(x.reshape(-1, self._net.in_dim).contiguous(), "x", torch.float32)
+        rows, A = x.shape[0], self._net.out_dim
+        per_dim = [_abi.require_gpu_tensor(t.contiguous(), n, torch.float32) for t, n in ((act, "act"), (old_logp, "old_logp"), (mu_old, "mu_old"))]
+        per_row = [_abi.require_gpu_tensor(t.contiguous(), n, torch.float32) for t, n in ((adv, "adv"), (cost_adv, "cost_adv"), (factor, "factor"))]
+        std_old = _abi.require_gpu_tensor(std_old.reshape(-1).contiguous(), "std_old", torch.float32)
+        assert all(t.numel() == rows * A for t in per_dim) and all(t.numel() == rows for t in per_row) and std_old.numel() == A
+        assert sums4.dtype == partial_ws.dtype == torch.float64 and sums4.numel() == 4 and partial_ws.numel() >= _abi.MA_LS_WS_DOUBLES
+        assert ratio is None or (ratio.dtype == torch.float32 and ratio.numel() == rows and ratio.is_contiguous())
+        act, old_logp, mu_old = per_dim
+        adv, cost_adv, factor = per_row
+        _abi.check(_abi.load().spo_ma_ls_eval(
+            _abi.ptr(self.theta), self._net, _abi.ptr(x), self.std_x_coef, self.std_y_coef, _abi.ptr(act), _abi.ptr(old_logp),
+            _abi.ptr(adv), _abi.ptr(cost_adv), _abi.ptr(factor), _abi.ptr(mu_old), _abi.ptr(std_old), rows, _abi.ptr(sums4),
+            _abi.ptr(ratio) if ratio is not None else None, _abi.ptr(partial_ws), _abi.stream_ptr()), "spo_ma_ls_eval")
+
     def net_backward(self, saved, dout: torch.Tensor, grad: torch.Tensor) -> None:
         x, ws = saved
         lib = _abi.load()

@@ -281,6 +281,10 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
         ratio = None
         lib = _abi.load()
         accepted = -1
+        # SPO_MA_LS_FUSED=1 (read at every update: an A/B knob) takes the fused candidate evaluation for a network it supports
+        # (spo_ma_ls_eval: two launches per candidate, no activations written).  Opt-in: at 10 000 rows its gain per candidate is
+        # inside the timing's spread (profiles/ma_ls_eval/step_times.txt); unset or 0 keeps net_forward + the row pass bit for bit.
+        fused = os.environ.get("SPO_MA_LS_FUSED", "0") == "1" and actor.ls_eval_supported()
         if self.sharded:
             # one kernel call, one all-reduce of four doubles and one host read per candidate; the means are over the rows of
             # all ranks, so every rank takes the same exit.  |x| of the next candidate rides along with the sums.
@@ -295,11 +299,15 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
                     x = x * 0.5 / x_norm_t
                     x_norm_t = torch.norm(x)
                 actor.theta.copy_(params - fraction_coef * (fraction ** i) * x)
-                mu = actor.net_forward(obs_batch)
-                _abi.check(lib.spo_ma_trpo_linesearch_sums(
-                    _abi.ptr(mu), _abi.ptr(actor.log_std), actor.std_x_coef, actor.std_y_coef, _abi.ptr(actions_batch), _abi.ptr(old_lp),
-                    _abi.ptr(adv), _abi.ptr(cadv), _abi.ptr(factor), _abi.ptr(mu_old), _abi.ptr(std_old_vec), rows, actor.act_dim,
-                    _abi.ptr(self._ls_sums), _abi.ptr(ratio), _abi.ptr(self._ls_ws), _abi.stream_ptr()), "spo_ma_trpo_linesearch_sums")
+                if fused:
+                    actor.net_ls_eval(obs_batch, actions_batch, old_lp, adv, cadv, factor, mu_old, std_old_vec, self._ls_sums, ratio,
+                                      self._ls_ws)
+                else:
+                    mu = actor.net_forward(obs_batch)
+                    _abi.check(lib.spo_ma_trpo_linesearch_sums(
+                        _abi.ptr(mu), _abi.ptr(actor.log_std), actor.std_x_coef, actor.std_y_coef, _abi.ptr(actions_batch), _abi.ptr(old_lp),
+                        _abi.ptr(adv), _abi.ptr(cadv), _abi.ptr(factor), _abi.ptr(mu_old), _abi.ptr(std_old_vec), rows, actor.act_dim,
+                        _abi.ptr(self._ls_sums), _abi.ptr(ratio), _abi.ptr(self._ls_ws), _abi.stream_ptr()), "spo_ma_trpo_linesearch_sums")
                 self.comm.all_reduce_sum_(self._ls_sums)
                 means = self._ls_sums / rows_g
                 kl, loss_improve = means[2].float(), (-means[0]).float() - reward_loss
@@ -308,6 +316,27 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
                 self._ratio_mean = sum_ratio / rows_g
                 if (sum_kl / rows_g < tkl and (-sum_r / rows_g - reward_loss_h < 0 if optim_case > 1 else True)
                         and sum_c / rows_g - cost_loss_h <= max(-rescale_constraint_val, 0)):
+                    flag, accepted = True, i
+                    break
+                expected_improve = expected_improve * fraction
+        elif fused:
+            # the host-driven exits on the fused evaluation: the means are fp64 row sums over this process's rows (the sharded
+            # form's with rows_g = rows), and the three numbers of the accept test come back in ONE host transfer
+            rows = mean.shape[0]
+            std_old_vec = std_old.reshape(-1).contiguous()
+            ratio = torch.empty((rows, 1), **self.tpdv)
+            for i in range(int(c["searching_steps"])):
+                x_norm = torch.norm(x)
+                if float(x_norm) > 0.5:
+                    x = x * 0.5 / x_norm
+                actor.theta.copy_(params - fraction_coef * (fraction ** i) * x)
+                actor.net_ls_eval(obs_batch, actions_batch, old_lp, adv, cadv, factor, mu_old, std_old_vec, self._ls_sums, ratio,
+                                  self._ls_ws)
+                means = (self._ls_sums / rows).float()
+                kl, loss_improve, new_cost_loss = means[2], -means[0] - reward_loss, means[1]
+                dist_entropy = entropy_of(self._std())
+                kl_h, improve_h, cost_h = torch.stack([kl, loss_improve, new_cost_loss - cost_loss]).tolist()
+                if (kl_h < tkl and (improve_h < 0 if optim_case > 1 else True) and cost_h <= max(-rescale_constraint_val, 0)):
                     flag, accepted = True, i
                     break
                 expected_improve = expected_improve * fraction
