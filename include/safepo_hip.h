@@ -900,6 +900,32 @@ int spo_ma_fvp_num_partials(int64_t rows);
 int64_t spo_ma_fvp_scratch_floats(const spo_ma_net* net, int64_t rows);
 int spo_ma_fvp(const float* theta, const spo_ma_net* net, const float* vec, const float* m_diag, int64_t rows,
                int64_t rows_global, const float* ws, float* scratch, float* out, void* stream);
+/* MACPO's two surrogate gradients in one fused pass (csrc/ma_trpo_grads.hip; replaces the two torch.autograd.grad calls of
+ * safepo/multi_agent/macpo.py:238-249, and spo_ma_actor_loss + spo_ma_backward run once per gradient: 4 launches instead of 24 at
+ * two blocks).  At the point whose activations spo_ma_forward left in ws and whose head output is `mean`:
+ *   losses2[0] = this rank's share of -mean(factor * ratio * adv),       grad_r = its gradient,
+ *   losses2[1] = this rank's share of -mean(factor * ratio * cost_adv),  grad_c = its gradient,
+ * the means over rows_global rows, ratio = prod_d exp(logp_d - old_logp_d): scalars5_out[0] and the gradient of two
+ * spo_ma_actor_loss calls with the clip off, no entropy term, no active masks and no multiplier.  Both gradients are flat, laid out
+ * like theta, every entry written; their log_std slots hold what spo_ma_actor_loss's dlogstd_out would.  The per-row delta chain is
+ * walked once on the cotangent per unit advantage; nothing is divided by an advantage (adv == 0 rows add exactly 0 to grad_r).
+ *   spo_ma_trpo_grads_supported      1 for an actor with in_dim 1..128, hidden 1..128, out_dim 1..16 and 1 or 2 blocks (the
+ *                                    envelope of spo_ma_fvp), else 0
+ *   spo_ma_trpo_grads_num_partials   workgroups along x for `rows` rows: min(ceil(rows / 32), 256)
+ *   spo_ma_trpo_grads_scratch_floats num_partials * 2 * (2 * 17 + spo_ma_param_count): per workgroup and gradient one fp64 record
+ *                                    {row-loss sum, log_std row sums[16]} and one partial vector; -1 outside the envelope or rows < 1
+ *   spo_ma_trpo_grads                (macpo.py:238-249) mean, act, old_logp: [rows, out_dim]; adv, cost_adv, factor: [rows]; scratch
+ *                                    8-byte aligned.  -2 with the dimension named for a net outside the envelope, -1 "bad args" for a
+ *                                    null pointer, rows < 1, rows_global < rows or a scratch pointer that is not 8-byte aligned,
+ *                                    all before any HIP call.  No allocation, no synchronisation, no
+ *                                    atomics (repeats are bit-identical); capturable. */
+int spo_ma_trpo_grads_supported(const spo_ma_net* net);
+int spo_ma_trpo_grads_num_partials(int64_t rows);
+int64_t spo_ma_trpo_grads_scratch_floats(const spo_ma_net* net, int64_t rows);
+int spo_ma_trpo_grads(const float* theta, const spo_ma_net* net, const float* ws, const float* mean, const float* act,
+                      const float* old_logp, const float* adv, const float* cost_adv, const float* factor, float std_x_coef,
+                      float std_y_coef, int64_t rows, int64_t rows_global, float* scratch, float* grad_r, float* grad_c,
+                      float* losses2, void* stream);
 /* Insert of one environment step into the per-agent buffers (Runner.insert, mappolag.py:449-492) as ONE launch: the
  * environment's [threads, agents, ...] observations / shared observations / rewards / costs are written to every agent's
  * time-major buffer row, masks and active masks are formed from the done flags (dones: [threads, agents] bytes, non-zero =

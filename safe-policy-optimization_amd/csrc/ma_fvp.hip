@@ -61,60 +61,6 @@ struct FvpArgs {
 template <int NB>
 constexpr int lds_floats() { return (3 + 2 * NB) * IMG + ROWS * LDO + (NB + 1) * ROWS * 2; }
 
-__device__ __forceinline__ float elu_grad(float a) { return a > 0.f ? 1.f : a + 1.f; }      // ELU' = exp(z) = a + 1 for z <= 0
-
-// dst[32][LDI] <- rows c * 32 .. of src[B][W]; zero beyond W and past the batch (all 128 columns are written)
-__device__ __forceinline__ void load_image(float* dst, const float* __restrict__ src, int W, int64_t row0, int64_t B, bool vec, int tid) {
-  const int c0 = 4 * (tid & 31);
-#pragma unroll
-  for (int hh = 0; hh < ROWS / 8; ++hh) {
-    const int lrow = (tid >> 5) + 8 * hh;
-    const int64_t grow = row0 + lrow;
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (grow < B && c0 < W) {
-      const float* p = src + grow * W + c0;
-      if (vec) {
-        v = *reinterpret_cast<const f4*>(p);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c0 + e < W) v[e] = p[e];
-      }
-    }
-    *reinterpret_cast<f4*>(dst + lrow * LDI + c0) = v;
-  }
-}
-
-// acc[i] += sum over the feature tiles nt of layer l of  W[16 nt + 4 q ..][16 t + j] . DZ[row tile r0 + i][16 nt + 4 q ..]
-__device__ __forceinline__ void mm_cols(const float* __restrict__ Wg, int out, int in, const float* DZ, int ldz, const Unit u, int j,
-                                        int q, f4 (&acc)[2]) {
-  const int ntm = (out + 15) >> 4;
-  f4 af[MAXT];
-#pragma unroll
-  for (int nt = 0; nt < MAXT; ++nt)
-    if (nt < ntm) af[nt] = ld_col4(Wg, in, 16 * nt + 4 * q, out, 16 * u.t + j, in);
-#pragma unroll
-  for (int nt = 0; nt < MAXT; ++nt)
-    if (nt < ntm) {
-      f4 b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        if (i < u.nr) b[i] = *reinterpret_cast<const f4*>(DZ + (16 * (u.r0 + i) + j) * ldz + 16 * nt + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          if (i < u.nr) acc[i] = mfma4(af[nt][r], b[i][r], acc[i]);
-    }
-}
-
-__device__ __forceinline__ float sum8(float v) {      // over the 8 lanes of a row, the same order in every lane
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
-
 template <int NB>
 __global__ __launch_bounds__(NTHR, 1) void ma_fvp_kernel(FvpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];

@@ -62,13 +62,6 @@ struct LsArgs {
 
 constexpr int LDS_FLOATS = 3 * IMG + ROWS * LDO + MAXW + 3 * MAXA;
 
-__device__ __forceinline__ float sum8(float v) {      // over the 8 lanes of a row, the same order in every lane
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
-
 __device__ __forceinline__ float elu(float z) { return z > 0.f ? z : expm1f(z); }      // nn.ELU(alpha=1)
 
 // mm_rows (rows_frag.h) on W diag(gam): the fold of the input LayerNorm's weight, formed on the fragments

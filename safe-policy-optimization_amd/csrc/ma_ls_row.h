@@ -28,6 +28,13 @@ __device__ __forceinline__ void ma_ls_dim_term(float mu, float act, float old_lo
   kl += dlog + (so2 + dm * dm) / (1e-8f + 2.f * sd * sd) - 0.5f;
 }
 
+// one action dimension's log-probability as ma_ls_dim_term forms it, and d = act - mu: the row terms of the surrogate loss and of
+// its cotangent (spo_ma_trpo_grads, ma_trpo_grads.hip)
+__device__ __forceinline__ float ma_logp_dim(float mu, float act, float sd, float& d) {
+  d = act - mu;
+  return -(d * d) / (2.f * sd * sd) - logf(sd) - MA_LOG_SQRT_2PI_F;
+}
+
 // the row's four terms, rounded to fp32 as the reference's products are, added in fp64
 __device__ __forceinline__ void ma_ls_row_add(float ratio, float kl, float factor, float adv, float cost_adv, double (&acc)[MA_LS_NS]) {
   const float w = ratio * factor;

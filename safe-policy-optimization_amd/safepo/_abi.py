@@ -5,7 +5,9 @@ safepo/_lib/.  Loading fails LOUDLY: there is no Python/CPU implementation behin
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
@@ -286,6 +288,10 @@ PROTOTYPES = {
     "spo_ma_fvp_num_partials": (c_int, [c_int64]),
     "spo_ma_fvp_scratch_floats": (c_int64, [POINTER(MaNet), c_int64]),
     "spo_ma_fvp": (c_int, [P, POINTER(MaNet), P, P, c_int64, c_int64, P, P, P, P]),
+    "spo_ma_trpo_grads_supported": (c_int, [POINTER(MaNet)]),
+    "spo_ma_trpo_grads_num_partials": (c_int, [c_int64]),
+    "spo_ma_trpo_grads_scratch_floats": (c_int64, [POINTER(MaNet), c_int64]),
+    "spo_ma_trpo_grads": (c_int, [P, POINTER(MaNet)] + [P] * 7 + [c_float, c_float, c_int64, c_int64, P, P, P, P, P]),
     "spo_ma_value_loss": (c_int, [P, P, P, P, P, c_float, c_float, c_float, c_float, c_int64, c_int64, P, P, P, P]),
     "spo_ma_clip_adam": (c_int, [P, P, P, P, c_int64, c_int64, c_float, c_float, c_float, c_float, c_int, P, P, P]),
     "spo_ma_trpo_linesearch_sums": (c_int, [P, P, c_float, c_float] + [P] * 7 + [c_int64, c_int, P, P, P, P]),
@@ -382,6 +388,23 @@ def ptr(t):
 def stream_ptr():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+@contextlib.contextmanager
+def graph_capture(graph, **kw):
+    """torch.cuda.graph(graph, **kw) with Python's cycle collector off until the capture has ended.  An automatic collection INSIDE
+    a capture can finalise a dead cycle that owns device objects (an evicted engine with its captured graphs and their memory
+    pools); releasing those while the thread's stream captures is an error raised in a destructor, i.e. an abort of the process.
+    Such cycles are collected, as ever, by the first automatic collection after the capture."""
+    import torch
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def require_gpu_tensor(t, name: str, dtype=None):

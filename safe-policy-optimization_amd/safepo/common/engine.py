@@ -314,7 +314,7 @@ class PPOLagEngine:
         try:
             # (thread_local: another thread of the process -- the RCCL watchdog of a data-parallel run polling its events -- must
             #  not invalidate the capture; this thread only launches kernels inside it)
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with _abi.graph_capture(g, capture_error_mode="thread_local"):
                 cur = obs
                 eps_all = self._epoch_noise()
                 for t in range(self.T):
@@ -766,7 +766,7 @@ class _WideOps:
                 t.copy_(b)
             torch.cuda.synchronize(self.dev)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with _abi.graph_capture(g, capture_error_mode="thread_local"):
                 body(win, loss_static)
             # a second capture of `unroll` consecutive steps (round 6): a graph launch costs ~8 us of GPU idle time between the last
             # kernel of one replay and the first of the next -- a quarter of a 3-kernel step -- and nothing in a step's launches
@@ -775,7 +775,7 @@ class _WideOps:
             g_many = None
             if unroll > 1:
                 g_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_many, capture_error_mode="thread_local"):
+                with _abi.graph_capture(g_many, capture_error_mode="thread_local"):
                     for _ in range(unroll):
                         body(win, loss_static)
             # everything the captured kernels address stays alive with the graph: the static loss buffer, and the workspaces the

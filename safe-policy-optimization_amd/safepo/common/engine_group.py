@@ -302,13 +302,13 @@ class PPOLagEngineGroup(_EngineGroup):
                 t.copy_(b)
             torch.cuda.synchronize(e0.dev)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with _abi.graph_capture(g, capture_error_mode="thread_local"):
                 step()
             unroll = max(1, int(os.environ.get("SPO_WIDE_GRAPH_UNROLL", "8")))
             g_many = None
             if unroll > 1:
                 g_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_many, capture_error_mode="thread_local"):
+                with _abi.graph_capture(g_many, capture_error_mode="thread_local"):
                     for _ in range(unroll):
                         step()
             ent["graphs"] = (g, g_many, unroll)         # (the table, windows, loss and part buffers live in `ent` beside them)
@@ -420,13 +420,13 @@ class PPOLagEngineGroup(_EngineGroup):
                 t.copy_(b)
             torch.cuda.synchronize(e0.dev)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with _abi.graph_capture(g, capture_error_mode="thread_local"):
                 step()
             unroll = max(1, int(os.environ.get("SPO_WIDE_GRAPH_UNROLL", "8")))
             g_many = None
             if unroll > 1:
                 g_many = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g_many, capture_error_mode="thread_local"):
+                with _abi.graph_capture(g_many, capture_error_mode="thread_local"):
                     for _ in range(unroll):
                         step()
             ent["graphs"] = (g, g_many, unroll)         # (the table, windows, loss and part buffers live in `ent` beside them)

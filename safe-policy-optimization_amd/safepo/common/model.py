@@ -272,6 +272,34 @@ class _MAFlatNet(nn.Module):
         _abi.check(lib.spo_ma_fvp(_abi.ptr(self.theta), self._net, _abi.ptr(vec), _abi.ptr(m_diag), rows, int(rows_global), _abi.ptr(ws),
                                   _abi.ptr(scratch), _abi.ptr(out), _abi.stream_ptr()), "spo_ma_fvp")
 
+    def trpo_grads_supported(self) -> bool:
+        """The fused surrogate-gradient pair (spo_ma_trpo_grads) takes this network: the envelope of fvp_supported."""
+        return bool(_abi.load().spo_ma_trpo_grads_supported(self._net))
+
+    def net_trpo_grads(self, saved, mean, act, old_logp, adv, cost_adv, factor, rows_global: int, grad_r: torch.Tensor,
+                       grad_c: torch.Tensor, losses: torch.Tensor) -> None:
+        """grad_r, grad_c <- this rank's share of the flat gradients of -mean(factor * ratio * adv) and of the same with cost_adv
+        (means over rows_global rows) at the point of `saved` and its head output `mean`; losses (float32[2]) <- the two shares of
+        the losses (spo_ma_trpo_grads: one fused pass in place of spo_ma_actor_loss + net_backward per gradient; every entry of
+        both gradients is written).  The scratch is kept with the network and only grows."""
+        x, ws = saved
+        lib = _abi.load()
+        rows, A = x.shape[0], self._net.out_dim
+        per_dim = [_abi.require_gpu_tensor(t.contiguous(), n, torch.float32) for t, n in ((mean, "mean"), (act, "act"), (old_logp, "old_logp"))]
+        per_row = [_abi.require_gpu_tensor(t.contiguous(), n, torch.float32) for t, n in ((adv, "adv"), (cost_adv, "cost_adv"), (factor, "factor"))]
+        outs = [_abi.require_gpu_tensor(t, n, torch.float32) for t, n in ((grad_r, "grad_r"), (grad_c, "grad_c"), (losses, "losses"))]
+        assert all(t.numel() == rows * A for t in per_dim) and all(t.numel() == rows for t in per_row)
+        assert grad_r.numel() == grad_c.numel() == self.theta.numel() and losses.numel() == 2 and all(t.is_contiguous() for t in outs)
+        need = int(lib.spo_ma_trpo_grads_scratch_floats(self._net, rows))
+        scratch = getattr(self, "_grads_scratch", None)
+        if scratch is None or scratch.numel() < need or scratch.device != x.device:
+            scratch = self._grads_scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+        assert scratch.data_ptr() % 8 == 0 and rows_global >= rows          # the scratch leads with fp64 records
+        _abi.check(lib.spo_ma_trpo_grads(
+            _abi.ptr(self.theta), self._net, _abi.ptr(ws), *(_abi.ptr(t) for t in per_dim + per_row), self.std_x_coef, self.std_y_coef,
+            rows, int(rows_global), _abi.ptr(scratch), _abi.ptr(grad_r), _abi.ptr(grad_c), _abi.ptr(losses), _abi.stream_ptr()),
+            "spo_ma_trpo_grads")
+
     def ls_eval_supported(self) -> bool:
         """The fused line-search candidate evaluation (spo_ma_ls_eval) takes this network: the envelope of fvp_supported."""
         return bool(_abi.load().spo_ma_ls_eval_supported(self._net))

@@ -4,7 +4,8 @@ Same networks, buffers, PopArt critics and Runner as MAPPO-L (mappolag.py); the 
 agent (macpo.py:201-371) instead of clipped-surrogate Adam steps:
 
   * gradients of the reward / cost surrogates mean(factor * prod_a ratio_a * adv) through the loss kernel
-    (spo_ma_actor_loss with the clip switched off) and spo_ma_backward;
+    (spo_ma_actor_loss with the clip switched off) and spo_ma_backward, or with SPO_MA_GRADS_FUSED=1 for hidden widths up to 128
+    both from one fused pass that walks the delta chain once (spo_ma_trpo_grads, csrc/ma_trpo_grads.hip);
   * two conjugate-gradient solves against the Fisher matrix.  The reference differentiates its KL expression twice
     (macpo.py:187-199).  At theta = theta_old the mean enters that expression only through (mu_old - mu)^2, so its
     Hessian is exactly J^T M J with M = 2 / (1e-8 + 2 sigma^2) per action dimension, plus a diagonal block for
@@ -119,6 +120,19 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
             self.comm.all_reduce_sum_(loss)
         return loss, grad
 
+    def _surrogate_grads_fused(self, saved, mean, actions, old_lp, adv, cost_adv, factor):
+        """Both calls of _surrogate_grad in one pass (spo_ma_trpo_grads): (reward loss, its gradient, the loss with cost_adv, its
+        gradient).  The all-reduce of the shares stays here."""
+        actor = self.policy.actor
+        grads = torch.empty((2, actor.theta.numel()), **self.tpdv)
+        losses = torch.empty(2, **self.tpdv)
+        actor.net_trpo_grads(saved, mean, actions, old_lp, adv, cost_adv, factor, mean.shape[0] * self.comm.world_size, grads[0], grads[1],
+                             losses)
+        if self.comm.world_size > 1:
+            self.comm.all_reduce_sum_(grads)
+            self.comm.all_reduce_sum_(losses)
+        return losses[0], grads[0], losses[1], grads[1]
+
     def _kl_hessian_logstd(self):
         """d^2/d log_std^2 of  -log s + s_old^2 / (1e-8 + 2 s^2)  at s = s_old, with s = y * sigmoid(log_std / x): the
         log_std block of the Hessian of macpo.py:160-166 (identical in every row, so the row mean changes nothing)."""
@@ -214,8 +228,18 @@ class MACPO_Trainer(_base.MAPPO_L_Trainer):
             ent = 0.5 + 0.5 * np.log(2 * np.pi) + torch.log(std)
             return ent.sum() if c["use_policy_active_masks"] else ent.mean()
         dist_entropy = entropy_of(std_vec)
-        reward_loss, reward_loss_grad = self._surrogate_grad(saved, mean, actions_batch, old_lp, adv, factor, active)
-        neg_cost_loss, neg_cost_grad = self._surrogate_grad(saved, mean, actions_batch, old_lp, cadv, factor, active)
+        # SPO_MA_GRADS_FUSED=1 (read at every update: an A/B knob) takes both gradients from one fused pass for a network it supports
+        # (spo_ma_trpo_grads: the delta chain once, four launches; at 10 000 rows 0.233 against 0.326 ms,
+        # profiles/ma_trpo_grads/step_times.txt).  Opt-in although the pair's gain is outside the timing's spread: with it on, the
+        # recorded MACPO runner trace's Loss_actor_expected_improve misses its gate (same file; the cause is not established, a dot
+        # product with a ten-iteration CG solution amplifying the gradients' other summation order is only supposed).  Unset or 0
+        # keeps the two loss + backward passes bit for bit.
+        if os.environ.get("SPO_MA_GRADS_FUSED", "0") == "1" and actor.trpo_grads_supported():
+            reward_loss, reward_loss_grad, neg_cost_loss, neg_cost_grad = self._surrogate_grads_fused(
+                saved, mean, actions_batch, old_lp, adv, cadv, factor)
+        else:
+            reward_loss, reward_loss_grad = self._surrogate_grad(saved, mean, actions_batch, old_lp, adv, factor, active)
+            neg_cost_loss, neg_cost_grad = self._surrogate_grad(saved, mean, actions_batch, old_lp, cadv, factor, active)
         cost_loss, cost_loss_grad = -neg_cost_loss, -neg_cost_grad
         B_cost_loss_grad = cost_loss_grad
         m_diag = (2.0 / (1e-8 + 2.0 * std_vec * std_vec)).reshape(1, -1)
